@@ -2,6 +2,8 @@
 8 workers x 25.6M fp32 params on graph 0 (util.py:281-285), with HBM / xGMI rooflines.
 
     python bench.py [--gpus N] [--steps K] [--warmup W]            # N = 1: all 8 workers on 1 GPU
+    python bench.py ... --full                                      # + every secondary figure and self-check
+    python bench.py ... --dump-outputs DIR                          # + DIR/rows.npy: the rows after the last step
     torchrun --nproc-per-node N ... bench.py --gpus N               # workers split over N GPUs
 
 A "step" is one gossip round of the whole 8-worker job (flatten + partner exchange + FMA-chain
@@ -10,12 +12,17 @@ active -- the worst case, 2 * 8 * P * 4 bytes of HBM traffic per round on one GP
 synthetic (splitmix64 uniform[-1,1)) and resident in HBM before timing starts.  Rank 0 prints
 one JSON line.
 
-Parity: after the timed region every figure is checked against the CPU oracle (oracle/, the
-restatement pinned to the reference's own outputs) -- the oracle is the checker only, loaded
+A plain run does what the headline needs and no more: set up, W warmup rounds, the settling
+rounds (a count fixed by the arguments, so every run applies the same rounds), the K timed
+rounds, the --dump-outputs files, the line.  Everything below runs only with --full.
+
+Parity (--full): after the timed region every figure is checked against the CPU oracle (oracle/,
+the restatement pinned to the reference's own outputs) -- the oracle is the checker only, loaded
 after the measurements, never timed and never on the measured path.
 
-Secondary figures (MATCHA C_b = 0.5, all-reduce, ChocoSGD, host-resident models, the WRN-28-10 /
-CIFAR-ResNet configs, the ER(64) budget sweep) each run under a watchdog deadline
+Secondary figures (--full: the mixing-alone launches and the same-box copy behind the roofline's
+context, the CPU baseline, MATCHA C_b = 0.5, all-reduce, ChocoSGD, host-resident models, the
+WRN-28-10 / CIFAR-ResNet configs, the ER(64) budget sweep) each run under a watchdog deadline
 (--figure-timeout) and a total budget (--figures-budget): a figure that hangs (e.g. a peer rank
 gone) makes rank 0 print the line measured so far with an "error" field and every rank exit with
 status 3 (EXIT_ABORTED), instead of losing the headline or hanging.
@@ -78,11 +85,46 @@ def settle_rounds(bytes_per_round, settle_ms):
     return int(min(SETTLE_MAX_ROUNDS, -(-settle_ms * 1e-3 // per_round_s)))
 
 
+def headline_settle_blocks(bytes_per_round, settle_ms, K, lb_rounds, dmax):
+    """Blocks of K diagnostic rounds between the headline's warmup and its timed region -- a count
+    fixed by the arguments, never by the clock, so every run with the same arguments applies the
+    same rounds and ends with the same rows (--dump-outputs).  Streaming rows: settle_rounds;
+    launch-bound rows (below SETTLE_MIN_BYTES per round): `lb_rounds`, as the launch-bound configs'
+    measurements; nothing to settle (--settle-ms 0): one block.  At least one block, at most `dmax`
+    rounds (the schedule built for them).  The same on every rank (bytes-only, as settle_rounds)."""
+    rounds = settle_rounds(bytes_per_round, settle_ms) or (lb_rounds if settle_ms > 0 else 0)
+    return max(1, min(-(-rounds // K), dmax // K))
+
+
+DUMP_BYTES = 32 << 20      # --dump-outputs: most bytes of rows.npy (all workers' sampled columns, fp32)
+DUMP_SEED = 1234
+
+
+def dump_columns(P, n):
+    """The columns of every row --dump-outputs writes: all of them while n rows of them fit in
+    DUMP_BYTES, else a fixed seeded sample -- one column from each of m equal strata of the row
+    (sorted, distinct), with both ends of the row."""
+    m = max(2, DUMP_BYTES // (4 * n))
+    if P <= m:
+        return np.arange(P, dtype=np.int64)
+    edges = (np.arange(m + 1, dtype=np.int64) * P) // m
+    jitter = np.random.default_rng(DUMP_SEED).random(m)
+    cols = edges[:-1] + (jitter * (edges[1:] - edges[:-1])).astype(np.int64)
+    cols[0], cols[-1] = 0, P - 1
+    return cols
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the oracle "
+                    "self-checks, the roofline's mixing-alone launches and same-box copy, the CPU baseline and every "
+                    "secondary figure (the options below that select or size them take effect only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write DIR/rows.npy: "
+                    "every worker's row as the last timed step left it (fp32, [workers, columns]; rows too large "
+                    "for 32 MiB: a fixed seeded sample of columns, dump_columns)")
     ap.add_argument("--params", type=int, default=25_600_000)
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--graph", type=int, default=0)
@@ -95,7 +137,8 @@ def parse():
                          "(tests/gloo_transport.py: host staging, lets N ranks share one GPU to test "
                          "the multi-process path; never a performance number)")
     ap.add_argument("--settle-ms", type=float, default=50.0, help="diagnostic rounds (per-round HIP events) "
-                    "run for at least this long between the warmup and the timed region")
+                    "run between the warmup and the timed region: about this long at the settled rate, a count "
+                    "fixed by the arguments (headline_settle_blocks)")
     ap.add_argument("--configs", type=int, default=1, help="also time the WRN-28-10 and CIFAR-ResNet configs' "
                     "rounds (BASELINE configs 2-3) on the same GPUs")
     ap.add_argument("--wrn-params", type=int, default=36_546_980, help="config 3 row size (WRN-28-10)")
@@ -1501,21 +1544,16 @@ def run(args, world, rank, line, wd, status=None):
         if overlap is not None:
             overlap.update(ipc)
     # per-round HIP events of the whole round (diagnostic): real rounds run BEFORE the timed region,
-    # in blocks of K, for at least --settle-ms (an idle MI355X takes ~10 ms of streaming to reach
-    # its steady clocks: profiles/r02_clock_ramp.log), so the timed rounds measure the steady state of the loop
+    # in blocks of K, about --settle-ms of them (an idle MI355X takes ~10 ms of streaming to reach
+    # its steady clocks: profiles/r02_clock_ramp.log), so the timed rounds measure the steady state of
+    # the loop -- a count fixed by the arguments, the same on every rank and in every run
     step_ms = []
     it = W
-    t_settle = time.perf_counter()
-    while True:
+    for _ in range(headline_settle_blocks(2 * -(-n // world) * P * 4, args.settle_ms, K, args.lb_rounds, DMAX)):
         ev = timed_rounds(run, timed, it, K)
         torch.cuda.synchronize()
         step_ms += [a.elapsed_time(b) for a, b in ev]
         it += K
-        done = (time.perf_counter() - t_settle) * 1e3 >= args.settle_ms or it - W + K > DMAX
-        if world > 1:                            # every rank leaves after the same block
-            done = max_over_ranks(float(done), world, dev) > 0
-        if done:
-            break
     diag_rounds = it - W
     step_ms = np.array(step_ms)
     barrier(world)
@@ -1538,20 +1576,32 @@ def run(args, world, rank, line, wd, status=None):
         # when this is >= 6); parity_ok below covers every one of them
         overlap["pull_rounds"] = int(timed._pull.round)
         overlap["pull_gate_error"] = timed._pull.error()   # an expired device wait (None: every gate passed)
-    final_cols = gather_columns(timed, cols_dev, world, dev)
+    full = args.full
+    final_cols = gather_columns(timed, cols_dev, world, dev) if full else None
+    if args.dump_outputs:
+        # what the timed path computed: every worker's row as the last timed round left it
+        dcols = dump_columns(P, n)
+        dumped = gather_columns(timed, torch.from_numpy(dcols).cuda(), world, dev)
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "rows.npy"),
+                    np.stack([dumped[w] for w in range(n)]).astype(np.float32))
+        del dumped
     # mixing kernel alone (N > 1: without the RCCL exchange, so rows go stale) -> its HBM roofline
     stream = torch.cuda.current_stream()
-    mev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(K)]
-    for j in range(K):
-        mev[j][0].record(stream)
-        group.engine.mix(timed_first + K + j, group.layout)
-        mev[j][1].record(stream)
-    torch.cuda.synchronize()
-    mix_ms = np.array([a.elapsed_time(b) for a, b in mev])
+    mix_ms = None
+    if full:
+        mev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(K)]
+        for j in range(K):
+            mev[j][0].record(stream)
+            group.engine.mix(timed_first + K + j, group.layout)
+            mev[j][1].record(stream)
+        torch.cuda.synchronize()
+        mix_ms = np.array([a.elapsed_time(b) for a, b in mev])
     # same-box context for the roofline fraction: torch's copy_ of the same bytes (read + write of
     # the active rows), timed the same way right after the mixing launches
     ref_copy_ms = None
-    if world == 1:
+    if world == 1 and full:
         nbytes = group.n_local * P * 4
         src_t = torch.empty(nbytes // 4, dtype=torch.float32, device="cuda")
         dst_t = torch.empty_like(src_t)
@@ -1574,10 +1624,12 @@ def run(args, world, rank, line, wd, status=None):
     # launches back to back (HIP events bracketing it on the launch stream, 0 us between launches
     # by kernel trace); at N > 1 the timed rounds also hold the exchange, so the K separate
     # mixing-alone launches (per-launch events) stand in
-    mix_avg_ms = float(timed_events_ms) if world == 1 else float(mix_ms.mean())
+    # (a plain N > 1 run has no mixing-alone launches, so no roofline object: --full)
+    mix_avg_ms = float(timed_events_ms) if world == 1 else (float(mix_ms.mean()) if full else None)
     mix_bytes = float(np.mean(hbm_bytes))
-    achieved = mix_bytes / (mix_avg_ms * 1e-3)
-    traffic, traffic_src = pmc_traffic()
+    achieved = mix_bytes / (mix_avg_ms * 1e-3) if mix_avg_ms else None
+    traffic, traffic_src = pmc_traffic() if full else (None, None)
+    mix_stat = (lambda f: float(f(mix_ms))) if full else (lambda f: None)
     # the headline line (filled in further as the figures complete)
     out = line.out
     out.update({
@@ -1589,6 +1641,7 @@ def run(args, world, rank, line, wd, status=None):
         "warmup": W,
         "ms_per_step": 1e3 * elapsed / K,
         "higher_is_better": True,
+        "full": bool(full),
         "scaling": "strong",
         "vs_baseline": None,
         "dtype": "f32",
@@ -1609,9 +1662,11 @@ def run(args, world, rank, line, wd, status=None):
                      "events_mean": 1e3 * avg_ms, "events_last_block_mean": 1e3 * float(step_ms[-K:].mean()),
                      "events_first_block_mean": 1e3 * float(step_ms[:K].mean()),
                      "diag_rounds": int(diag_rounds), "timed_mean": 1e6 * elapsed / K,
-                     "note": f"per-round HIP events of {diag_rounds} untimed rounds (blocks of K, >= "
-                             f"{args.settle_ms} ms) run between the warmup and the timed region (rank 0)"},
-        "roofline": {"bound": "hbm", "kernel": f"{pkg.engine.mix_kernel_name(eng.n_slots)} (mx_gossip_mix)",
+                     "note": f"per-round HIP events of {diag_rounds} untimed rounds (blocks of K, about "
+                             f"{args.settle_ms} ms at the settled rate) run between the warmup and the timed "
+                             f"region (rank 0)"},
+        "roofline": None if achieved is None else
+                    {"bound": "hbm", "kernel": f"{pkg.engine.mix_kernel_name(eng.n_slots)} (mx_gossip_mix)",
                      "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK, "traffic": traffic,
                      "traffic_source": traffic_src, "bytes_per_launch": mix_bytes,
@@ -1619,9 +1674,9 @@ def run(args, world, rank, line, wd, status=None):
                      "avg_launch_source": ("HIP events over the K timed rounds (the mixing launches back to back)"
                                            if world == 1 else "K mixing-alone launches after the timed region, "
                                                               "per-launch HIP events"),
-                     "mixing_alone_events_ms": {"mean": float(mix_ms.mean()), "min": float(mix_ms.min()),
-                                                "median": float(np.median(mix_ms))},
-                     "min_launch_ms": float(mix_ms.min()), "median_launch_ms": float(np.median(mix_ms)),
+                     "mixing_alone_events_ms": {"mean": mix_stat(np.mean), "min": mix_stat(np.min),
+                                                "median": mix_stat(np.median)} if full else None,
+                     "min_launch_ms": mix_stat(np.min), "median_launch_ms": mix_stat(np.median),
                      "frac_timed_region": (mix_bytes / (elapsed / K)) / HBM_PEAK if world == 1 else None,
                      "same_box_torch_copy_ms": ref_copy_ms,
                      "vs_same_box_copy": (ref_copy_ms / mix_avg_ms) if ref_copy_ms else None,
@@ -1647,6 +1702,7 @@ def run(args, world, rank, line, wd, status=None):
                        "note": "busiest GPU pair: bytes that cross it per round (one direction, and "
                                "both directions summed) / whole-job round time (exchange + mix), "
                                "against the 153 GB/s per-link figure of SURVEY.md §8d"}
+    if world > 1 and full:
         # the expected round of every form, from its parts (achieved / predicted names the term that is off)
         mix_s = float(np.median(mix_ms)) * 1e-3
         mix_s = max_over_ranks(mix_s, world, dev)
@@ -1660,6 +1716,22 @@ def run(args, world, rank, line, wd, status=None):
         out["predicted"]["timed_form"] = chosen_form or "rccl"
         out["predicted"]["achieved_over_predicted"] = (pr["round_ms"] / (1e3 * round_s)) if pr else None
     wd.disarm()
+
+    def finish():
+        line.emit()
+        if world > 1:
+            wd.arm("teardown", args.figure_timeout)
+            dist.barrier()
+            if isinstance(comm, pkg.engine.RcclComm):
+                comm.close()
+            dist.destroy_process_group()
+            wd.disarm()
+
+    if not full:
+        # a plain run ends here: the headline alone (no self-check, no secondary figure: --full)
+        for g in {id(g): g for g in (timed, group)}.values():
+            g.close()
+        return finish()
     # self-check: every worker's sampled columns after every round the timed group ran vs the
     # oracle's rounds on the same columns from the synthetic initial values (checker, untimed)
     if rank == 0:
@@ -1761,14 +1833,7 @@ def run(args, world, rank, line, wd, status=None):
     out["figures_s"] = time.monotonic() - t_fig
     if world > 1:
         out["pull_transport"] = pull_counts(pkg, world)     # the whole run's binds, summed over ranks
-    line.emit()
-    if world > 1:
-        wd.arm("teardown", args.figure_timeout)
-        dist.barrier()
-        if isinstance(comm, pkg.engine.RcclComm):
-            comm.close()
-        dist.destroy_process_group()
-        wd.disarm()
+    finish()
 
 
 if __name__ == "__main__":

@@ -176,3 +176,35 @@ def test_settle_rounds_sizes_the_burst():
     assert bench.settle_rounds(bench.SETTLE_MIN_BYTES, 1e6) == bench.SETTLE_MAX_ROUNDS
     assert bench.settle_rounds(64 * 2 * 1_000_000_000 * 4, 50.0) == 1            # one ER(64) round > 50 ms
     assert bench.settle_rounds(2 * 8 * 36_546_980 * 4, 50.0) < n                 # bigger rows, fewer rounds
+
+
+def test_headline_settle_blocks_are_fixed_by_the_arguments():
+    """bench.headline_settle_blocks: whole blocks of K covering settle_rounds (streaming rows) or
+    --lb-rounds (launch-bound rows), one block with nothing to settle, never more rounds than the
+    schedule holds -- a function of the arguments alone, so two runs apply the same rounds."""
+    import bench
+    head = 2 * 8 * 25_600_000 * 4
+    n = bench.settle_rounds(head, 50.0)
+    for K in (1, 7, 20, 50, n, n + 1, 5000):
+        b = bench.headline_settle_blocks(head, 50.0, K, 400, max(K, 4000))
+        assert b >= 1 and (b - 1) * K < max(n, 1) and (b * K >= n or K > n)
+    assert bench.headline_settle_blocks(head, 50.0, 20, 400, 4000) == -(-n // 20)
+    assert bench.headline_settle_blocks(head, 0, 20, 400, 4000) == 1
+    assert bench.headline_settle_blocks(2 * 8 * 100_000 * 4, 50.0, 3, 20, 4000) == 7      # launch-bound: lb_rounds
+    assert bench.headline_settle_blocks(2 * 8 * 100_000 * 4, 0, 3, 20, 4000) == 1
+    assert bench.headline_settle_blocks(head, 1e6, 20, 400, 100) == 5                     # capped by the schedule
+
+
+def test_dump_columns_fixed_sample():
+    """bench.dump_columns (--dump-outputs): every column while the rows fit the byte budget, else a
+    seeded sample -- the same from call to call, sorted, distinct, within the row, both ends in it,
+    and small enough that n fp32 rows of it stay under the budget."""
+    import bench
+    small = bench.dump_columns(10_007, 8)
+    assert np.array_equal(small, np.arange(10_007))
+    P, n = 25_600_000, 8
+    a, b = bench.dump_columns(P, n), bench.dump_columns(P, n)
+    assert np.array_equal(a, b) and a.dtype == np.int64
+    assert a[0] == 0 and a[-1] == P - 1 and np.all(np.diff(a) > 0)
+    assert 4 * n * len(a) <= bench.DUMP_BYTES <= 64 << 20
+    assert len(bench.dump_columns(P, 64)) * 64 * 4 <= bench.DUMP_BYTES

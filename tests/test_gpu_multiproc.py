@@ -60,7 +60,7 @@ def test_bench_multiprocess_path(nproc):
     config 4), the WRN / ResNet configs 2-3 and the ER(64) budget sweep (config 5) -- each one's
     oracle self-check must pass (configs 3-5 self-checking at N > 1).  nproc 8 is the
     driver's 8-GPU layout (one worker per rank; ER(64): 8 workers per rank) on one GPU."""
-    r = _torchrun(nproc, ["bench.py", "--gpus", str(nproc), "--transport", "gloo", "--steps", "3", "--warmup", "1",
+    r = _torchrun(nproc, ["bench.py", "--full", "--gpus", str(nproc), "--transport", "gloo", "--steps", "3", "--warmup", "1",
                           "--params", "200000", "--choco-params", "300000", "--cpu-seconds", "0",
                           "--wrn-params", "70000", "--resnet-params", "30000", "--mlp-params", "40000", "--lb-rounds", "20", "--er-params", "20000",
                           "--er-rounds", "2", "--er-budgets", "0.3,1.0"], timeout=280)
@@ -121,7 +121,7 @@ def test_bench_watchdog_line_on_hang():
     -- the headline intact -- with an "error" field, and the job ends instead of hanging, with a
     NON-zero exit status (the driver's rc must tell an aborted run from a
     clean one)."""
-    r = _torchrun(2, ["bench.py", "--gpus", "2", "--transport", "gloo", "--steps", "3", "--warmup", "1",
+    r = _torchrun(2, ["bench.py", "--full", "--gpus", "2", "--transport", "gloo", "--steps", "3", "--warmup", "1",
                       "--params", "100000", "--cpu-seconds", "0", "--configs", "0", "--er", "0",
                       "--figure-timeout", "15", "--debug-skip", "allreduce:1"], timeout=240)
     assert r.returncode != 0, _why(r)
@@ -139,7 +139,7 @@ def test_bench_multiprocess_overlap_forms(nproc, overlap, pull):
     calibrated among all three; the timed form passes the self-check.  With --pull on the Choco
     figure runs too, forced onto the pull form (messages read from the owners' snapshots)."""
     choco = ["--choco", "1", "--choco-params", "100000"] if pull == "on" else ["--choco", "0"]
-    r = _torchrun(nproc, ["bench.py", "--gpus", str(nproc), "--transport", "gloo", "--steps", "3", "--warmup", "1",
+    r = _torchrun(nproc, ["bench.py", "--full", "--gpus", str(nproc), "--transport", "gloo", "--steps", "3", "--warmup", "1",
                           "--params", "100000", "--cpu-seconds", "0", "--overlap", overlap,
                           "--pull", pull, "--configs", "0", "--er", "0", "--allreduce", "0"] + choco)
     assert r.returncode == 0, _why(r)
@@ -174,7 +174,7 @@ def test_bench_falls_back_to_pull_without_rccl():
     failed on every rank): the gossip runs over the pull transport alone -- headline, MATCHA,
     Choco (both pull reads calibrated) and the configs each pass the oracle self-check, the line
     says why (rccl_unavailable) and the RCCL-only figures are skipped, not failed."""
-    r = _torchrun(2, ["bench.py", "--gpus", "2", "--transport", "gloo", "--debug-no-rccl", "--steps", "3",
+    r = _torchrun(2, ["bench.py", "--full", "--gpus", "2", "--transport", "gloo", "--debug-no-rccl", "--steps", "3",
                       "--warmup", "1", "--params", "100000", "--choco-params", "100000", "--cpu-seconds", "0",
                       "--wrn-params", "50000", "--resnet-params", "20000", "--mlp-params", "30000", "--lb-rounds", "20", "--er-params", "20000",
                       "--er-rounds", "1", "--er-budgets", "1.0"], timeout=280)
@@ -200,7 +200,7 @@ def test_bench_real_rccl_refusal_falls_back_to_pull():
     ("invalid usage": RCCL takes no two ranks on one device).  The bench's own collectives run on
     its gloo process group, so nothing else depends on RCCL: every rank continues over the pull
     transport, every figure's oracle self-check passes and the run exits 0."""
-    r = _torchrun(2, ["bench.py", "--gpus", "2", "--debug-share-gpu", "--steps", "3", "--warmup", "1",
+    r = _torchrun(2, ["bench.py", "--full", "--gpus", "2", "--debug-share-gpu", "--steps", "3", "--warmup", "1",
                       "--params", "100000", "--choco-params", "100000", "--cpu-seconds", "0", "--wrn-params", "50000",
                       "--resnet-params", "20000", "--mlp-params", "30000", "--lb-rounds", "20", "--er-params", "20000", "--er-rounds", "1",
                       "--er-budgets", "1.0", "--figure-timeout", "60"], timeout=280)
@@ -246,7 +246,7 @@ def test_bench_self_launch_gloo():
     """`python bench.py --gpus 2` WITHOUT torchrun: the parent starts the ranks
     as a child torch.distributed.run and relays rank 0's line -- n_gpus 2, the oracle self-check
     true, the launcher recorded (gloo transport: both ranks share this box's one GPU)."""
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--transport", "gloo", "--steps", "3",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--transport", "gloo", "--steps", "3",
                         "--warmup", "1", "--params", "100000", "--choco", "0", "--cpu-seconds", "0", "--configs",
                         "0", "--er", "0", "--allreduce", "1"], cwd=ROOT, capture_output=True, text=True,
                        timeout=240, env=dict(os.environ, OMP_NUM_THREADS="2"))
@@ -300,7 +300,7 @@ def test_bench_watchdog_line_on_stall():
     naming the figure (its own watchdog's, or -- when rank 1's watchdog fired first and the launcher
     stopped rank 0 -- the SIGTERM handler's), and the job exits NON-zero (bench.EXIT_ABORTED per
     rank)."""
-    r = _torchrun(2, ["bench.py", "--gpus", "2", "--transport", "gloo", "--steps", "3", "--warmup", "1",
+    r = _torchrun(2, ["bench.py", "--full", "--gpus", "2", "--transport", "gloo", "--steps", "3", "--warmup", "1",
                       "--params", "100000", "--choco-params", "100000", "--cpu-seconds", "0", "--configs", "0",
                       "--er", "0", "--figure-timeout", "15", "--debug-stall", "choco:1"], timeout=240)
     assert r.returncode != 0, _why(r)
@@ -352,7 +352,7 @@ def test_cross_gpu_transports_match_oracle():
 def test_bench_single_gpu_line():
     """bench.py at N = 1 (headline shape, few rounds): the line's contract fields, the self-check,
     the per-round event statistics, the config and host-model figures and the CPU baseline legs."""
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "4", "--warmup", "2",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "4", "--warmup", "2",
                         "--choco-params", "200000", "--cpu-seconds", "1", "--er-params", "3e6",
                         "--er-budgets", "0.2,1.0"], cwd=ROOT, capture_output=True,
                        text=True, timeout=280, env=dict(os.environ, OMP_NUM_THREADS="2"))

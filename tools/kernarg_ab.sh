@@ -1,6 +1,6 @@
 set -u
 mkdir -p gpurun_out/r6l
-B="python -u bench.py --steps 20 --warmup 5 --cpu-seconds 0 --staged 0 --configs 0 --choco 0 --allreduce 0 --er 0"
+B="python -u bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 --staged 0 --configs 0 --choco 0 --allreduce 0 --er 0"
 export TMPDIR=/tmp
 for rep in 1 2; do
   timeout -k 10 120 $B > gpurun_out/r6l/plain_$rep.json 2>/dev/null || exit 1

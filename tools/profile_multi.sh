@@ -22,12 +22,12 @@ GPUS=$(python -c "import torch; print(torch.cuda.device_count())")
 if [ "$GPUS" -lt "$N" ]; then echo "profile_multi: $N ranks need $N GPUs, $GPUS present"; exit 2; fi
 PORT=$((20000 + RANDOM % 20000))
 TR="python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT --no-python"
-BENCH="python -u bench.py --gpus $N --steps 20 --warmup 5 --cpu-seconds 0 --staged 0 --configs 0 --choco 0 --allreduce 0 --er 0"
+BENCH="python -u bench.py --full --gpus $N --steps 20 --warmup 5 --cpu-seconds 0 --staged 0 --configs 0 --choco 0 --allreduce 0 --er 0"
 run() { local lim=$1; shift; echo "== $*"; timeout -k 10 -s KILL $lim "$@"; local rc=$?; echo "rc=$rc"; return $rc; }
 rocprofv3 -L > $OUT/counters.txt 2>&1 || true
 run 600 $TR rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace/rank%env{RANK}%" -o "trace_%pid%" -- $BENCH \
     > $OUT/trace.log 2>&1 || exit $?
-PMC_BENCH="python -u bench.py --gpus $N --steps 5 --warmup 2 --cpu-seconds 0 --settle-ms 0 --staged 0 --configs 0 --choco 0 --allreduce 0 --er 0"
+PMC_BENCH="python -u bench.py --full --gpus $N --steps 5 --warmup 2 --cpu-seconds 0 --settle-ms 0 --staged 0 --configs 0 --choco 0 --allreduce 0 --er 0"
 for C in FETCH_SIZE WRITE_SIZE; do
   run 300 $TR rocprofv3 --pmc $C --output-format csv -d "$OUT/${C,,}/rank%env{RANK}%" -o "pmc_%pid%" -- $PMC_BENCH \
       > $OUT/${C,,}.log 2>&1 || exit $?
