@@ -32,6 +32,13 @@ SIGNATURES = {
     "mx_gossip_mix_at": (c_int, [c_p, c_p, c_p, c_p, c_int, c_i64, c_int, c_p, c_p, c_i64, c_int, c_int, c_f32,
                                  c_p]),
     "mx_iter_advance": (c_int, [c_p, c_i64, c_p]),
+    "mx_mix_bf16_tile": (c_int, [c_int]),
+    "mx_mix_bf16_layout": (c_int, [c_p, c_int, c_int, c_p]),
+    "mx_mix_bf16_set": (c_int, [ctypes.c_char_p, c_int]),
+    "mx_mix_bf16_get": (c_int, [ctypes.c_char_p]),
+    "mx_gossip_mix_bf16_packed": (c_int, [c_p, c_i64, c_p]),
+    "mx_gossip_mix_bf16_at": (c_int, [c_p, c_p, c_p, c_p, c_int, c_i64, c_int, c_p, c_p, c_i64, c_int, c_int, c_f32,
+                                      c_p]),
     "mx_gather": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p]),
     "mx_scatter": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p]),
     "mx_topk_work_bytes": (ctypes.c_size_t, [c_i64]),

@@ -31,7 +31,7 @@ def topk_count(P, ratio):
 
 class ChocoWorkerGroup:
     def __init__(self, topology, models=None, numel=None, *, ratio, consensus_lr, rank=0, nranks=1,
-                 comm=None, adopt=True, placement=None, pull_read="fetch"):
+                 comm=None, adopt=True, placement=None, pull_read="fetch", dtype=torch.float32):
         """placement: as VirtualWorkerGroup (None / "contiguous", "auto" or a worker order);
         `workers` lists the worker id of each local row.  pull_read (PullTransport only): "fetch"
         (default) copies the round's partner messages from their owners' snapshots into the receive
@@ -40,6 +40,9 @@ class ChocoWorkerGroup:
         load per message).  Same bits; which is faster across GPUs is measured by bench.py."""
         if pull_read not in ("fetch", "direct"):
             raise ValueError("pull_read must be 'fetch' or 'direct'")
+        if dtype != torch.float32:
+            # only VirtualWorkerGroup's mixing round has a bfloat16 form (csrc/mix_bf16.hip)
+            raise NotImplementedError(f"ChocoWorkerGroup: {dtype} rows -- the top-k and apply kernels are fp32-only")
         self.pull_read = pull_read
         require_device()
         from .placement import block_workers, place

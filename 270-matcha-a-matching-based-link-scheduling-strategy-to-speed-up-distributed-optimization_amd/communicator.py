@@ -88,7 +88,7 @@ class _Staging:
         reassigned p.data since, e.g. torch.nn.utils.vector_to_parameters or model.cpu())."""
         base, off = self.row.data_ptr(), 0
         for p in self.params:
-            if p.data.data_ptr() != base + 4 * off and p.numel():
+            if p.data.data_ptr() != base + self.row.element_size() * off and p.numel():
                 return False
             off += p.numel()
         return True
@@ -263,9 +263,13 @@ class decenCommunicator(Communicator):
             # same call, as every rank's model changes size together in data-parallel training)
             self.close()
             on_gpu = all(p.device.type == "cuda" for p in params)
+            # a bfloat16 model on the GPU is mixed as bfloat16 rows when this process holds every
+            # worker (size == 1); anywhere else the rows are fp32 (staging and the exchange are fp32-only)
+            bf16 = on_gpu and self.size == 1 and bool(params) and all(p.dtype == torch.bfloat16 for p in params)
             self._group = VirtualWorkerGroup(self.topology, [model] if on_gpu else None,
                                              numel=None if on_gpu else n, rank=self.rank,
-                                             nranks=self.size, comm=self._comm(), idle_rows=self.idle_rows)
+                                             nranks=self.size, comm=self._comm(), idle_rows=self.idle_rows,
+                                             dtype=torch.bfloat16 if bf16 else torch.float32)
             self._stage = _Staging(params, self._group.rows[0])
         self._model_params = params
 

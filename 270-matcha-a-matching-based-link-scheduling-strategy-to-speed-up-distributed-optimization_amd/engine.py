@@ -40,6 +40,18 @@ def mix_kernel_name(n_slots):
 
 _TUNE_GEN = [0]     # bumped on every knob change: layouts re-check their tile size only then
 _mix_packed = lib.mx_gossip_mix_packed
+_mix_bf16_packed = lib.mx_gossip_mix_bf16_packed
+
+# row element types the mixing kernels take: float32 everywhere; bfloat16 on one GPU with every
+# partner local (csrc/mix_bf16.hip: an fp32 FMA chain over exactly widened inputs, rounded to
+# nearest even once at the store)
+ROW_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def row_dtype(dtype):
+    if dtype not in ROW_DTYPES:
+        raise TypeError(f"worker rows are float32 or bfloat16, not {dtype}")
+    return dtype
 
 
 def set_mix_tuning(**knobs):
@@ -381,9 +393,14 @@ class MixCall(ctypes.Structure):
 
 
 class Layout:
-    """Pointer table of the mixing kernel: slot k's copy of segment s (include/matcha_gossip.h)."""
+    """Pointer table of the mixing kernel: slot k's copy of segment s (include/matcha_gossip.h).
+    Lengths are in elements of `dtype` (float32, or bfloat16: the mx_mix_bf16_* tiles and kernels)."""
 
-    def __init__(self, seg_lens, slot_ptrs, n_slots):
+    def __init__(self, seg_lens, slot_ptrs, n_slots, dtype=torch.float32):
+        self.dtype = row_dtype(dtype)
+        self.bf16 = dtype == torch.bfloat16
+        self.elem = 2 if self.bf16 else 4
+        self._tile_fn = lib.mx_mix_bf16_tile if self.bf16 else lib.mx_mix_tile
         nseg = len(seg_lens)
         seg_len = np.asarray(seg_lens, dtype=np.int64)
         table = np.zeros((nseg, n_slots), dtype=np.int64)
@@ -394,10 +411,14 @@ class Layout:
                 if ptrs[s] % 16:
                     vec[s] = 0
         tile_off = np.zeros(nseg + 1, dtype=np.int64)
-        check(lib.mx_mix_layout(seg_len.ctypes.data, nseg, n_slots, tile_off.ctypes.data), "mx_mix_layout")
+        if self.bf16:
+            check(lib.mx_mix_bf16_layout(seg_len.ctypes.data, nseg, n_slots, tile_off.ctypes.data),
+                  "mx_mix_bf16_layout")
+        else:
+            check(lib.mx_mix_layout(seg_len.ctypes.data, nseg, n_slots, tile_off.ctypes.data), "mx_mix_layout")
         self.nseg = nseg
         self.n_slots = n_slots
-        self.tile = int(lib.mx_mix_tile(n_slots))
+        self.tile = int(self._tile_fn(n_slots))
         self.total_tiles = int(tile_off[-1])
         self.seg_ptrs = torch.from_numpy(table).to("cuda")
         self.seg_len = torch.from_numpy(seg_len).to("cuda")
@@ -600,14 +621,14 @@ class GossipEngine:
     def mix(self, it, layout, stream=None):
         it = self.round_index(it)                # the kernel indexes the plan table by `it`
         if layout.tune_gen != _TUNE_GEN[0]:
-            if layout.tile != lib.mx_mix_tile(layout.n_slots):
+            if layout.tile != layout._tile_fn(layout.n_slots):
                 raise MXError("layout built for another mixing tile size (the unroll knob changed it)")
             layout.tune_gen = _TUNE_GEN[0]
         # one ctypes call per round with the group's arguments packed once (small rows are
         # launch-bound: tools/launch_overhead.py)
-        rc = _mix_packed(layout.call_for(self), it, stream_ptr(stream))
+        rc = (_mix_bf16_packed if layout.bf16 else _mix_packed)(layout.call_for(self), it, stream_ptr(stream))
         if rc:
-            check(rc, "mx_gossip_mix_packed")
+            check(rc, "mx_gossip_mix_bf16_packed" if layout.bf16 else "mx_gossip_mix_packed")
 
 
     def mix_at(self, iter_dev, layout, stream=None):
@@ -616,14 +637,15 @@ class GossipEngine:
         stream, so a captured launch pair serves every iteration (a counter past the schedule
         makes the launch a no-op)."""
         if layout.tune_gen != _TUNE_GEN[0]:
-            if layout.tile != lib.mx_mix_tile(layout.n_slots):
+            if layout.tile != layout._tile_fn(layout.n_slots):
                 raise MXError("layout built for another mixing tile size (the unroll knob changed it)")
             layout.tune_gen = _TUNE_GEN[0]
         if iter_dev.dtype != torch.int64 or iter_dev.device.type != "cuda" or iter_dev.numel() != 1:
             raise TypeError("iter_dev must be a one-element int64 CUDA tensor")
         s = stream_ptr(stream)
-        check(lib.mx_gossip_mix_at(*layout._args, self._plan_ptr, iter_dev.data_ptr(), self.T, self.n_local,
-                                   self.M, self.alpha32, s), "mx_gossip_mix_at")
+        mix_at = lib.mx_gossip_mix_bf16_at if layout.bf16 else lib.mx_gossip_mix_at
+        check(mix_at(*layout._args, self._plan_ptr, iter_dev.data_ptr(), self.T, self.n_local,
+                     self.M, self.alpha32, s), "mx_gossip_mix_bf16_at" if layout.bf16 else "mx_gossip_mix_at")
         check(lib.mx_iter_advance(iter_dev.data_ptr(), 1, s), "mx_iter_advance")
 
     def mix_rounds_at(self, iter_dev, ctrs, layout, stream=None):
@@ -631,7 +653,7 @@ class GossipEngine:
         *iter_dev + j, *iter_dev += K), then one mixing launch per round reading its own counter --
         the same rounds as K mix_at calls, without the K counter bumps."""
         if layout.tune_gen != _TUNE_GEN[0]:
-            if layout.tile != lib.mx_mix_tile(layout.n_slots):
+            if layout.tile != layout._tile_fn(layout.n_slots):
                 raise MXError("layout built for another mixing tile size (the unroll knob changed it)")
             layout.tune_gen = _TUNE_GEN[0]
         for t in (iter_dev, ctrs):
@@ -640,9 +662,11 @@ class GossipEngine:
         K = ctrs.numel()
         s = stream_ptr(stream)
         check(lib.mx_iter_expand(iter_dev.data_ptr(), ctrs.data_ptr(), K, s), "mx_iter_expand")
+        mix_at = lib.mx_gossip_mix_bf16_at if layout.bf16 else lib.mx_gossip_mix_at
         for j in range(K):
-            check(lib.mx_gossip_mix_at(*layout._args, self._plan_ptr, ctrs.data_ptr() + 8 * j, self.T,
-                                       self.n_local, self.M, self.alpha32, s), "mx_gossip_mix_at")
+            check(mix_at(*layout._args, self._plan_ptr, ctrs.data_ptr() + 8 * j, self.T,
+                         self.n_local, self.M, self.alpha32, s),
+                  "mx_gossip_mix_bf16_at" if layout.bf16 else "mx_gossip_mix_at")
 
 
 def _params(model):
@@ -663,11 +687,33 @@ class VirtualWorkerGroup:
                xGMI pair) or an explicit worker order.  `workers` lists the worker id of each
                local row (models are given in that order).
     idle_rows -- "skip" (default) or "canonical": see GossipEngine.
+    dtype   -- torch.float32 (default) or torch.bfloat16: the arena's (and every adopted
+               parameter's) element type.  A bfloat16 round runs the fp32 FMA chain over exactly
+               widened inputs and rounds to nearest even once at the store (csrc/mix_bf16.hip); it
+               moves half the bytes.  bfloat16 groups live on one GPU with every partner local:
+               nranks > 1, a transport (comm) and chunk_cols raise NotImplementedError -- the
+               exchange, publish and ChocoSGD kernels are fp32-only.
     """
 
     def __init__(self, topology, models=None, numel=None, *, rank=0, nranks=1, comm=None, adopt=True,
-                 chunk_cols=None, placement=None, idle_rows="skip"):
+                 chunk_cols=None, placement=None, idle_rows="skip", dtype=torch.float32):
         require_device()
+        self.dtype = row_dtype(dtype)
+        self.elem = 2 if dtype == torch.bfloat16 else 4
+        if dtype == torch.bfloat16:
+            if nranks > 1 or comm is not None:
+                raise NotImplementedError("bfloat16 worker rows are mixed on one GPU only (nranks = 1, no transport): "
+                                          "the RCCL exchange and the pull transport move fp32 rows")
+            if chunk_cols:
+                raise NotImplementedError("bfloat16 worker rows: chunk_cols pipelines the fp32 cross-GPU exchange, "
+                                          "which bfloat16 groups do not have")
+        if models is not None:
+            # before anything is built or launched
+            kind = "bfloat16" if dtype == torch.bfloat16 else "float32"
+            for m in models:
+                for p in _params(m):
+                    if p.dtype != dtype or p.device.type != "cuda":
+                        raise TypeError(f"worker parameters must be {kind} CUDA tensors")
         from .placement import block_workers, place
         n = int(topology.size)
         topology, self.placement = place(topology, nranks, placement)
@@ -695,7 +741,7 @@ class VirtualWorkerGroup:
                 raise ValueError("give models or numel")
             self.numel = int(numel)
         self.ld = (self.numel + ROW_ALIGN - 1) // ROW_ALIGN * ROW_ALIGN
-        self.arena = torch.zeros((self.n_local, self.ld), dtype=torch.float32, device="cuda")
+        self.arena = torch.zeros((self.n_local, self.ld), dtype=self.dtype, device="cuda")
         # column pipelining of the cross-GPU exchange (N > 1): chunk c+1 travels over RCCL on a side
         # stream while chunk c is mixed; the receive slab is two chunk-wide buffers
         self._pull = None
@@ -714,8 +760,6 @@ class VirtualWorkerGroup:
             for r, m in enumerate(models):
                 off = 0
                 for p in _params(m):
-                    if p.dtype != torch.float32 or p.device.type != "cuda":
-                        raise TypeError("worker parameters must be float32 CUDA tensors")
                     k = p.numel()
                     view = self.arena[r, off:off + k].view(p.shape)
                     view.copy_(p.data)
@@ -748,7 +792,7 @@ class VirtualWorkerGroup:
             slot_ptrs = [[p] for p in self._row_ptrs]
             if self.slab is not None:
                 slot_ptrs += [[self.slab[k].data_ptr()] for k in range(self.engine.max_remote)]
-            self.layout = Layout([self.numel], slot_ptrs, self.engine.n_slots)
+            self.layout = Layout([self.numel], slot_ptrs, self.engine.n_slots, dtype=self.dtype)
 
     @property
     def rows(self):
@@ -771,7 +815,7 @@ class VirtualWorkerGroup:
         if self.engine.comm is not None:
             self.engine.exchange(it, self._row_ptrs,
                                  self.slab.data_ptr() if self.slab is not None else None,
-                                 self.ld * 4, self.numel * 4, stream)
+                                 self.ld * self.elem, self.numel * self.elem, stream)
         self.engine.mix(it, self.layout, stream)
         return True
 

@@ -172,6 +172,13 @@ def sync_rows(rows, order=0):
     n, count = rows.shape
     if n == 1 or count == 0:
         return
+    if rows.dtype == torch.bfloat16:
+        # bfloat16 rows (VirtualWorkerGroup(dtype=torch.bfloat16)): the same fp32 sum over the exactly
+        # widened rows, rounded to bfloat16 once -- a start-up step, not a per-round one
+        wide = rows.float()
+        sync_rows(wide, order)
+        rows.copy_(wide)
+        return
     if rows.stride(1) != 1:
         raise ValueError("sync_rows: rows must be contiguous along the parameter axis")
     # one pass: every column of every row read, then the mean written to that column of every row
@@ -209,7 +216,10 @@ class VirtualTrainer:
             self.group = ChocoWorkerGroup(self.GP, self.models, ratio=args.ratio,
                                           consensus_lr=args.consensus_lr)
         else:
-            self.group = VirtualWorkerGroup(self.GP, self.models)
+            # bfloat16 models are mixed as bfloat16 rows (half the bytes per round), like decenCommunicator
+            dts = {p.dtype for m in self.models for p in m.parameters()}
+            self.group = VirtualWorkerGroup(self.GP, self.models,
+                                            dtype=torch.bfloat16 if dts == {torch.bfloat16} else torch.float32)
         sync_rows(self.group.rows)
         self.optimizers = [torch.optim.SGD(m.parameters(), lr=args.lr, momentum=args.momentum,
                                            weight_decay=5e-4, nesterov=args.nesterov, dampening=0)
@@ -217,6 +227,8 @@ class VirtualTrainer:
         self.criterion = nn.CrossEntropyLoss()
         self.data = [synthetic_batches(r, n_batches, args.bs, args.shape, args.num_classes, args.randomSeed,
                                        device) for r in range(size)]
+        if self.group.rows.dtype == torch.bfloat16:              # inputs in the models' element type
+            self.data = [[(x.to(torch.bfloat16), y) for x, y in batches] for batches in self.data]
         self.n_batches = n_batches
         self.recorders = [Recorder(args, r) for r in range(size)] if args.save else None
         self.epoch = 0

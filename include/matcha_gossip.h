@@ -209,6 +209,43 @@ int mx_iter_advance(int64_t* iter_dev, int64_t by, void* stream);
  * &ctrs[0] .. &ctrs[n-1].  Same rounds as n (mix_at + advance-by-1) pairs, half the launches. */
 int mx_iter_expand(int64_t* iter_dev, int64_t* ctrs, int n, void* stream);
 
+/* ---------------------------------------------------------------- the hot path, bfloat16 rows
+ * The same round (decenCommunicator.averaging + prepare_comm_buffer + reset_model,
+ * communicator.py:87-131) for worker rows held in bfloat16, one GPU, every partner local:
+ *   acc = 0.0f;  for each active partner j (ascending matching): acc = fmaf(alpha, f32(x_j), acc)
+ *   acc = fmaf(selfweight_r, f32(x_r), acc);  x_r = bf16_rne(acc)
+ * f32() is the exact widening (bits << 16); alpha and selfweight are the plan record's fp32 values;
+ * the fp32 chain is rounded to bfloat16 once, to nearest even, at the store (a NaN stays a NaN, payload
+ * unspecified).  This is NOT what the reference's recv_buffer.add_(alpha, recv_tmp)
+ * (communicator.py:92-122) would compute on bf16 tensors -- it would round after every partner;
+ * see DESIGN.md §4.  Plan tables (mx_plan_build, mx_plan_set_idle) are the fp32 path's, unchanged.
+ * Pointers are to 16-bit elements and every length is in elements:
+ *   seg_ptrs_dev  uint16* [nseg][n_slots]; n_slots == n_local (no receive slots), 1-64 slots,
+ *                 M <= 32 matchings -- anything else is MX_ERR_INVALID and nothing is launched
+ *   tile_off_dev  prefix of ceil(len / mx_mix_bf16_tile(n_slots)) per tensor (mx_mix_bf16_layout);
+ *                 tiles are 2048 / 2048 / 1024 / 512 columns for the 8 / 16 / 32 / 64-slot classes
+ *                 (twice the fp32 classes' columns in the same LDS bytes); 0 for n_slots > 64
+ *   seg_vec_dev   unused (16-byte accesses wherever a row pointer is 16-byte aligned and the 8
+ *                 elements are in range, 2-byte accesses elsewhere); may be NULL
+ * mx_gossip_mix_bf16_packed takes the fp32 call record unchanged (its float* table read as uint16*
+ * pointers); need_host is the same load hint: rows named there are loaded before the plan record
+ * arrives, and a wrong mask costs time, never bits.  mx_gossip_mix_bf16_at is the graph-replayable
+ * form (round = *iter_dev, a no-op outside [0, n_iters)), as mx_gossip_mix_at.
+ * mx_mix_bf16_set / _get: "nontemporal" (1 / 0 / 2 = auto as mx_mix_set's), "wgpc" (8 / 16 slots on
+ * the flat grid: workgroups per CU, 0 = as many as fit), "blocks_per_cu" (persistent grids),
+ * "flat_small" (8 / 16 slots: one workgroup per 1024-column work item up to this many x the
+ * persistent grid), "grid" (> 0: exact persistent grid size), "split" (8 / 16 slots: work items per 2048-column layout tile, 1 / 2 / 4;
+ * 0 = the default, 2 -- layouts are unaffected).  Speed only, never bits. */
+int mx_mix_bf16_tile(int n_slots);
+int mx_mix_bf16_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host);
+int mx_mix_bf16_set(const char* key, int value);
+int mx_mix_bf16_get(const char* key);
+int mx_gossip_mix_bf16_packed(const mx_mix_call* call, int64_t iter, void* stream);
+int mx_gossip_mix_bf16_at(uint16_t* const* seg_ptrs_dev, const int64_t* seg_len_dev,
+                          const int64_t* tile_off_dev, const uint8_t* seg_vec_dev, int nseg,
+                          int64_t total_tiles, int n_slots, const int32_t* plan_dev, const int64_t* iter_dev,
+                          int64_t n_iters, int n_local, int M, float alpha, void* stream);
+
 /* ---------------------------------------------------------------- flatten / unflatten
  * mx_gather replaces flatten_tensors (comm_helpers.py:12-30): flat[off[s] + i] = src[s][i].
  * mx_scatter is the copy_ loop of reset_model over unflatten_tensors views
