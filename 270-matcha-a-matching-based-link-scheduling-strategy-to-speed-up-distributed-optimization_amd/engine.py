@@ -60,6 +60,21 @@ def set_mix_tuning(**knobs):
         check(lib.mx_mix_set(k.encode(), int(v)), "mx_mix_set")
 
 
+SGD_TUNE_KEYS = ("nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid")
+_sgd_mix = lib.mx_sgd_mix
+
+
+def sgd_mix_tuning():
+    """Current knobs of the fused SGD + mixing kernel (include/matcha_gossip.h, mx_sgd_mix_set)."""
+    return {k: int(lib.mx_sgd_mix_get(k.encode())) for k in SGD_TUNE_KEYS}
+
+
+def set_sgd_mix_tuning(**knobs):
+    _TUNE_GEN[0] += 1
+    for k, v in knobs.items():
+        check(lib.mx_sgd_mix_set(k.encode(), int(v)), "mx_sgd_mix_set")
+
+
 def partition(n, nranks):
     """Contiguous worker blocks [(row_base, n_local)] per rank (sizes differ by at most 1)."""
     base, extra = divmod(n, nranks)
@@ -444,6 +459,58 @@ class Layout:
         return rec[1]
 
 
+class SgdMixCall(ctypes.Structure):
+    """mx_sgd_mix_call (include/matcha_gossip.h): the fused SGD + mixing launch's arguments, packed once."""
+    _fields_ = [("x_ptrs_dev", ctypes.c_void_p), ("g_ptrs_dev", ctypes.c_void_p), ("m_ptrs_dev", ctypes.c_void_p),
+                ("seg_len_dev", ctypes.c_void_p), ("tile_off_dev", ctypes.c_void_p), ("plan_dev", ctypes.c_void_p),
+                ("total_tiles", ctypes.c_int64), ("nseg", ctypes.c_int32), ("n_slots", ctypes.c_int32),
+                ("n_local", ctypes.c_int32), ("M", ctypes.c_int32), ("alpha", ctypes.c_float),
+                ("wd", ctypes.c_float), ("mom", ctypes.c_float), ("nesterov", ctypes.c_int32),
+                ("zero_grads", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+class SgdLayout:
+    """Pointer tables of the fused SGD + mixing kernel (csrc/sgd_mix.hip): row r's copy of segment s,
+    its gradient and -- unless m_ptrs is None (no momentum) -- its momentum buffer, fp32, lengths in
+    floats.  x_ptrs / g_ptrs / m_ptrs are lists over the rows of per-segment device addresses."""
+
+    def __init__(self, seg_lens, x_ptrs, g_ptrs, m_ptrs, n_local):
+        nseg = len(seg_lens)
+        seg_len = np.asarray(seg_lens, dtype=np.int64)
+        tile_off = np.zeros(nseg + 1, dtype=np.int64)
+        check(lib.mx_sgd_mix_layout(seg_len.ctypes.data, nseg, n_local, tile_off.ctypes.data), "mx_sgd_mix_layout")
+
+        def table(rows):
+            t = np.zeros((nseg, n_local), dtype=np.int64)
+            for r, ptrs in enumerate(rows):
+                t[:, r] = ptrs
+            return torch.from_numpy(t).to("cuda")
+
+        self.nseg, self.n_local = nseg, n_local
+        self.tile = int(lib.mx_sgd_mix_tile(n_local))
+        self.total_tiles = int(tile_off[-1])
+        self.x_ptrs, self.g_ptrs = table(x_ptrs), table(g_ptrs)
+        self.m_ptrs = table(m_ptrs) if m_ptrs is not None else None
+        self.seg_len = torch.from_numpy(seg_len).to("cuda")
+        self.tile_off = torch.from_numpy(tile_off).to("cuda")
+        self.tune_gen = _TUNE_GEN[0]
+
+    def check_tile(self):
+        """After a knob change: the tile this layout was built for is still the kernel's (as
+        GossipEngine.mix does for Layout)."""
+        if self.tune_gen != _TUNE_GEN[0]:
+            if self.tile != lib.mx_sgd_mix_tile(self.n_local):
+                raise MXError("layout built for another fused SGD + mixing tile size")
+            self.tune_gen = _TUNE_GEN[0]
+
+    def call(self, engine, wd, mom, nesterov, zero_grads):
+        return SgdMixCall(self.x_ptrs.data_ptr(), self.g_ptrs.data_ptr(),
+                          self.m_ptrs.data_ptr() if self.m_ptrs is not None else None, self.seg_len.data_ptr(),
+                          self.tile_off.data_ptr(), engine._plan_ptr, self.total_tiles, self.nseg, engine.n_slots,
+                          engine.n_local, engine.M, engine.alpha32, float(np.float32(wd)), float(np.float32(mom)),
+                          int(bool(nesterov)), int(bool(zero_grads)), 0)
+
+
 IDLE_MODES = {"skip": 0, "canonical": 1}
 
 
@@ -727,6 +794,9 @@ class VirtualWorkerGroup:
         self.topology = topology
         self.iter = 0
         self.iter_dev = torch.zeros(1, dtype=torch.int64, device="cuda")   # device_round's counter
+        self._chunk_cols = chunk_cols
+        self._adopted = models if (models is not None and adopt) else None
+        self._sgd = None                     # attach_sgd: the fused SGD + mixing launch's state
         self._round_ctrs = {}                # device_rounds(K): per-round counters, one tensor per K
         if models is not None:
             if len(models) != self.n_local:
@@ -922,18 +992,120 @@ class VirtualWorkerGroup:
             ctrs = self._round_ctrs[K] = torch.zeros(K, dtype=torch.int64, device="cuda")
         self.engine.mix_rounds_at(self.iter_dev, ctrs, self.layout, stream)
 
+    # ------------------------------------------------------------------ fused SGD + mixing
+    def attach_sgd(self, momentum=0.0, weight_decay=0.0, nesterov=False, zero_grads=True):
+        """Give the group torch.optim.SGD's state (dampening 0) so that one launch per iteration
+        applies every worker's update and the round's mix (csrc/sgd_mix.hip; the reference's
+        optimizer.step() + zero_grad() + communicate(), train_mpi.py:131-142).
+
+        Allocates `grad_arena` ([n_local, ld] fp32 zeros; `grads` is its [:, :numel] view) and, with
+        momentum, `mom_arena` / `momentum_rows`.  For adopted models every parameter's .grad becomes
+        the matching view of the gradient arena, so backward() accumulates in place.
+        zero_grads=True (default) has the launch zero the gradients it consumed, which makes
+        optimizer.zero_grad() unnecessary -- and zero_grad(set_to_none=True), torch's default,
+        would DETACH those views (later gradients would land in fresh tensors the kernel never
+        reads): do not call it on an attached group, or pass set_to_none=False.
+        fp32 groups on one GPU only: every partner's updated row must exist before any exchange, so
+        a cross-GPU group is a different design."""
+        if self._sgd is not None:
+            raise RuntimeError("attach_sgd: already attached")
+        if self.dtype != torch.float32:
+            raise NotImplementedError("attach_sgd: the fused SGD + mixing kernel takes fp32 rows, not bfloat16")
+        if self.engine.comm is not None or self.engine.max_remote:
+            raise NotImplementedError("attach_sgd: one GPU only (nranks = 1, no transport): the partners' updated "
+                                      "rows must exist before any exchange")
+        if self._chunk_cols:
+            raise NotImplementedError("attach_sgd: not with chunk_cols (the column-pipelined cross-GPU exchange)")
+        momentum, weight_decay = float(momentum), float(weight_decay)
+        if nesterov and momentum == 0.0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if lib.mx_sgd_mix_tile(self.n_local) <= 0 or self.engine.M > 32:
+            raise NotImplementedError(f"attach_sgd: {self.n_local} local rows / {self.engine.M} matchings exceed the "
+                                      "fused kernel's 64 rows / 32 matchings")
+        self.grad_arena = torch.zeros((self.n_local, self.ld), dtype=torch.float32, device="cuda")
+        self.grads = self.grad_arena[:, :self.numel]
+        self.mom_arena = self.momentum_rows = None
+        if momentum != 0.0:
+            self.mom_arena = torch.zeros((self.n_local, self.ld), dtype=torch.float32, device="cuda")
+            self.momentum_rows = self.mom_arena[:, :self.numel]
+        lay = SgdLayout([self.numel], [[p] for p in self._row_ptrs],
+                        [[self.grad_arena[r].data_ptr()] for r in range(self.n_local)],
+                        [[self.mom_arena[r].data_ptr()] for r in range(self.n_local)] if momentum != 0.0 else None,
+                        self.n_local)
+        call = lay.call(self.engine, weight_decay, momentum, nesterov, zero_grads)
+        if self._adopted is not None:
+            for r, m in enumerate(self._adopted):
+                off = 0
+                for p in _params(m):
+                    k = p.numel()
+                    p.grad = self.grad_arena[r, off:off + k].view(p.shape)
+                    off += k
+        self.lr_dev = torch.zeros(1, dtype=torch.float32, device="cuda")   # sgd_device_round's learning rate
+        self.sgd_hyper = {"momentum": momentum, "weight_decay": weight_decay, "nesterov": bool(nesterov),
+                          "zero_grads": bool(zero_grads)}
+        self._sgd = (lay, call, ctypes.addressof(call))
+
+    def _sgd_state(self):
+        if self._sgd is None:
+            raise MXError("no SGD state: call attach_sgd() first")
+        self._sgd[0].check_tile()
+        return self._sgd[2]
+
+    def sgd_step(self, it, lr, stream=None):
+        """Enqueue ONE launch: every local worker's SGD update at learning rate `lr`, then round
+        `it`'s mix of the updated rows.  Always launches -- an all-zero round is the SGD step
+        alone -- and returns whether the round mixed."""
+        call = self._sgd_state()
+        it = self.engine.round_index(it)
+        rc = _sgd_mix(call, it, lr, None, stream_ptr(stream))
+        if rc:
+            check(rc, "mx_sgd_mix")
+        return bool(self.engine.any_active[it])
+
+    def sgd_device_round(self, stream=None):
+        """Graph-replayable sgd_step: the round is read from `self.iter_dev` and the learning rate
+        from `self.lr_dev` (a 1-element fp32 CUDA tensor) when the kernel runs, then the counter is
+        advanced, so one captured launch pair serves every iteration and every learning rate.  A
+        counter outside the schedule makes the launch a no-op: no SGD step either."""
+        call = self._sgd_state()
+        s = stream_ptr(stream)
+        check(lib.mx_sgd_mix_at(call, self.iter_dev.data_ptr(), self.engine.T, 0.0, self.lr_dev.data_ptr(), s),
+              "mx_sgd_mix_at")
+        check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, s), "mx_iter_advance")
+
+    def sgd_communicate(self, lr):
+        """optimizer.step() + zero_grad() + communicate() of every worker at the group's own
+        iteration counter, as one launch; returns seconds like communicate()."""
+        it = self.iter
+        self.iter += 1
+        torch.cuda.synchronize()
+        tic = time.time()
+        self.sgd_step(it, lr)
+        self.wait_round()
+        return time.time() - tic
+
     def state_dict(self):
-        """Checkpoint: the workers' rows and the iteration counter (resume on the same schedule)."""
-        return {"kind": "decen", "iter": int(self.iter), "row_base": int(self.row_base),
-                "workers": list(self.workers), "rows": self.rows.detach().clone()}
+        """Checkpoint: the workers' rows and the iteration counter (resume on the same schedule);
+        with attach_sgd(momentum != 0) the momentum rows too."""
+        state = {"kind": "decen", "iter": int(self.iter), "row_base": int(self.row_base),
+                 "workers": list(self.workers), "rows": self.rows.detach().clone()}
+        if self._sgd is not None and self.momentum_rows is not None:
+            state["momentum_rows"] = self.momentum_rows.detach().clone()
+        return state
 
     def load_state_dict(self, state):
         if state.get("kind") != "decen" or int(state["row_base"]) != self.row_base or \
                 list(state.get("workers", self.workers)) != self.workers or \
                 tuple(state["rows"].shape) != tuple(self.rows.shape):
             raise ValueError("checkpoint does not match this worker group")
+        mom = state.get("momentum_rows")
+        have = self._sgd is not None and self.momentum_rows is not None
+        if mom is not None and (not have or tuple(mom.shape) != tuple(self.momentum_rows.shape)):
+            raise ValueError("checkpoint carries momentum rows: attach_sgd(momentum=...) before loading it")
         with torch.no_grad():
             self.rows.copy_(state["rows"])
+            if have:                             # a checkpoint without them: the buffers start as zeros
+                self.momentum_rows.zero_() if mom is None else self.momentum_rows.copy_(mom)
         self.iter = int(state["iter"])
 
     def communicate(self):

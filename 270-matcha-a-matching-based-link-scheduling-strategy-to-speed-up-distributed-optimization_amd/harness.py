@@ -196,8 +196,14 @@ class VirtualTrainer:
     element-wise op sequence of torch.optim.SGD) runs once over the stacked views -- a training
     step for all workers is a handful of batched launches plus the gossip kernel."""
 
-    def __init__(self, args, model_fn, n_batches, device="cuda", batched=False, graph=False):
-        """graph=True (with batched=True, decentralized gossip, one GPU): once the learning rate
+    def __init__(self, args, model_fn, n_batches, device="cuda", batched=False, graph=False, fused_sgd=False):
+        """fused_sgd=True (non-batched, uncompressed, fp32 models): the workers' optimizer.step() /
+        zero_grad() and the gossip round run as ONE launch (VirtualWorkerGroup.attach_sgd /
+        sgd_communicate, csrc/sgd_mix.hip): backward() accumulates into the group's gradient arena,
+        the optimizers stay constructed only because their param_groups carry the learning-rate
+        schedule, and checkpoints save the group's momentum rows.
+
+        graph=True (with batched=True, decentralized gossip, one GPU): once the learning rate
         is constant within an epoch, the whole training iteration -- vmap'd forward / backward,
         SGD update and the gossip round at a device-side iteration counter (device_round) -- is
         captured once per learning rate in a HIP graph and replayed, so an iteration costs one
@@ -207,6 +213,10 @@ class VirtualTrainer:
         size = args.size
         np.random.seed(args.randomSeed)                          # train_mpi.py:62
         torch.manual_seed(args.randomSeed)
+        self.fused_sgd = bool(fused_sgd)
+        if self.fused_sgd and (batched or args.compress):
+            raise ValueError("fused_sgd needs per-worker (non-batched), uncompressed training: the vmap path's "
+                             "gradients are fresh tensors every iteration and ChocoSGD mixes compressed messages")
         self.GP = make_topology(args, 0, size, args.epoch * n_batches)
         self.models = []
         for r in range(size):
@@ -220,6 +230,10 @@ class VirtualTrainer:
             dts = {p.dtype for m in self.models for p in m.parameters()}
             self.group = VirtualWorkerGroup(self.GP, self.models,
                                             dtype=torch.bfloat16 if dts == {torch.bfloat16} else torch.float32)
+        if self.fused_sgd:
+            if self.group.dtype != torch.float32:
+                raise ValueError("fused_sgd needs float32 models")
+            self.group.attach_sgd(args.momentum, 5e-4, args.nesterov)
         sync_rows(self.group.rows)
         self.optimizers = [torch.optim.SGD(m.parameters(), lr=args.lr, momentum=args.momentum,
                                            weight_decay=5e-4, nesterov=args.nesterov, dampening=0)
@@ -397,13 +411,17 @@ class VirtualTrainer:
                     losses[r].update(loss.item(), data.size(0))
                     top1[r].update(acc1[0].item(), data.size(0))
                     loss.backward()
-                    update_learning_rate(opt, epoch, args, itr=b, itr_per_epoch=self.n_batches)
-                    opt.step()
-                    opt.zero_grad()
+                    lr = update_learning_rate(opt, epoch, args, itr=b, itr_per_epoch=self.n_batches)
+                    if not self.fused_sgd:               # fused: the update runs inside the gossip launch
+                        opt.step()
+                        opt.zero_grad()
                     comp[r] += time.time() - t0
             if on_round is not None:
                 on_round("before", self)
-            comm_time += self.communicate()                  # train_mpi.py:142, all workers at once
+            if self.fused_sgd:                               # step + zero_grad + communicate: one launch
+                comm_time += self.group.sgd_communicate(lr)
+            else:
+                comm_time += self.communicate()              # train_mpi.py:142, all workers at once
             self._dev_iter_synced = False
             if on_round is not None:
                 on_round("after", self)

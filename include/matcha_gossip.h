@@ -246,6 +246,70 @@ int mx_gossip_mix_bf16_at(uint16_t* const* seg_ptrs_dev, const int64_t* seg_len_
                           int64_t total_tiles, int n_slots, const int32_t* plan_dev, const int64_t* iter_dev,
                           int64_t n_iters, int n_local, int M, float alpha, void* stream);
 
+/* ---------------------------------------------------------------- the hot path, SGD step fused in
+ * One training iteration's optimizer.step(), optimizer.zero_grad() and communicator.communicate(model)
+ * (train_mpi.py:131-142) for every local worker in ONE launch, fp32 rows, one GPU, every partner local.
+ * Per row r and column c, with x, g, m the parameter, gradient and momentum-buffer elements
+ * (torch.optim.SGD, dampening 0):
+ *   d  = (wd != 0) ? fmaf(wd, x, g) : g                       g.add(p, alpha=wd)
+ *   if mom != 0:  m = fadd(fmul(mom, m), d)                   buf.mul_(mom).add_(d_p): two roundings
+ *                 d = nesterov ? fmaf(mom, m, d) : m
+ *   x' = fmaf(-lr, d, x)                                      p.add_(d_p, alpha=-lr)
+ * and then the round of mx_gossip_mix (decenCommunicator.averaging + prepare_comm_buffer + reset_model,
+ * communicator.py:87-131) on the x' values: same plan record, alpha, selfweight, ascending-matching
+ * partner order, self term last.  Rows the record reads and writes (degree > 0, or every row of an
+ * active round in idle mode 1) get that FMA chain; every other row, and every row of a round whose
+ * flags are all zero, gets x' stored as it is -- an all-zero round is the SGD step alone, NOT a no-op.
+ * The momentum buffer starts as zeros and the momentum line always runs, with no first-step case:
+ * fadd(fmul(mom, 0), d) equals torch's first-step buf = clone(d_p) under IEEE == and differs only in
+ * the sign of a zero (d = -0.0 gives m = +0.0).  lr, wd and mom are the fp32 roundings of the Python
+ * floats.  Traffic: 20 bytes per element (24 with zero_grads; 12 / 16 without momentum).
+ * mx_sgd_mix_call, built once and kept alive by the caller (pointer tables and plan on the device):
+ *   x_ptrs_dev / g_ptrs_dev / m_ptrs_dev   float* [nseg][n_local]: row r's copy of tensor s, its gradient
+ *                 and its momentum buffer; m_ptrs_dev is NULL exactly when mom == 0.  x and m are
+ *                 updated in place; g is read only, or overwritten with zeros when zero_grads != 0.
+ *                 Nothing is written at or past seg_len of a row in any of the three.
+ *   seg_len_dev   int64 [nseg] floats per tensor; tile_off_dev int64 [nseg+1] prefix of
+ *                 ceil(len / mx_sgd_mix_tile(n_slots)) per tensor (mx_sgd_mix_layout); total_tiles =
+ *                 tile_off[nseg].  Tiles are 1024 / 1024 / 512 / 256 columns for the 8 / 16 / 32 / 64-row
+ *                 classes; 0 for n_slots > 64.
+ *   plan_dev      plan table of mx_plan_build / mx_plan_set_idle, unchanged
+ *   n_slots == n_local (no receive slots), 1-64 rows, M <= 32 matchings: anything else is
+ *   MX_ERR_INVALID and nothing is launched.  A record with the peer-reads bit (mx_plan_set_peer_reads)
+ *   is not this kernel's either: the bit lives in device memory, so it is the launch that refuses it --
+ *   it writes nothing.
+ * 16-byte accesses where the x, g and m pointers of a (segment, row) are all 16-byte aligned and the 4
+ * elements are in range, 4-byte accesses elsewhere.
+ * mx_sgd_mix(call, iter, lr, lr_dev, stream): round `iter` of the plan table; a non-NULL lr_dev (device
+ * float) overrides lr and is read when the kernel runs.
+ * mx_sgd_mix_at: the graph-replayable form (as mx_gossip_mix_at): the round is *iter_dev; a counter
+ * outside [0, n_iters) makes the whole launch a no-op -- x, g and m are not written, the SGD step
+ * included.  With lr_dev one captured launch serves every iteration and every learning rate.
+ * mx_sgd_mix_set / _get: "nontemporal" (1 / 0 / 2 = auto as mx_mix_set's, on the bytes the round moves),
+ * "wgpc" (8 / 16 rows on the flat grid: workgroups per CU, 0 = as many as fit), "blocks_per_cu"
+ * (persistent grids), "flat_small" (8 / 16 rows: one workgroup per 512-column work item up to this many
+ * x the persistent grid), "grid" (> 0: exact persistent grid size).  Speed only, never bits; none of
+ * them changes the tile. */
+typedef struct mx_sgd_mix_call {
+    float* const* x_ptrs_dev;
+    float* const* g_ptrs_dev;
+    float* const* m_ptrs_dev;
+    const int64_t* seg_len_dev;
+    const int64_t* tile_off_dev;
+    const int32_t* plan_dev;
+    int64_t total_tiles;
+    int32_t nseg, n_slots, n_local, M;
+    float alpha, wd, mom;
+    int32_t nesterov, zero_grads, pad_;
+} mx_sgd_mix_call;
+int mx_sgd_mix_tile(int n_slots);
+int mx_sgd_mix_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host);
+int mx_sgd_mix_set(const char* key, int value);
+int mx_sgd_mix_get(const char* key);
+int mx_sgd_mix(const mx_sgd_mix_call* call, int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_sgd_mix_at(const mx_sgd_mix_call* call, const int64_t* iter_dev, int64_t n_iters, float lr,
+                  const float* lr_dev, void* stream);
+
 /* ---------------------------------------------------------------- flatten / unflatten
  * mx_gather replaces flatten_tensors (comm_helpers.py:12-30): flat[off[s] + i] = src[s][i].
  * mx_scatter is the copy_ loop of reset_model over unflatten_tensors views

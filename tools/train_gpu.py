@@ -2,6 +2,7 @@
 
     python tools/train_gpu.py --workers 8 --epoch 2 --batches 50                 # 8 virtual workers, 1 GPU
     python tools/train_gpu.py --compress --budget 0.5                           # ChocoSGD
+    python tools/train_gpu.py --momentum 0.9 --fused-sgd                        # SGD step fused into the round
     torchrun --nproc-per-node N --master-addr 127.0.0.1 tools/train_gpu.py     # one worker per GPU
 
 Flags follow train_mpi.py:205-231 (same names and defaults where they apply); --workers,
@@ -44,6 +45,8 @@ def main():
     ap.add_argument("--batched", action="store_true", help="one vmap'd step for all virtual workers")
     ap.add_argument("--graph", action="store_true", help="with --batched: replay each iteration (step + "
                     "gossip round) as one captured HIP graph once the learning rate is constant")
+    ap.add_argument("--fused-sgd", action="store_true", help="one GPU, per-worker (non-batched) fp32 training: the "
+                    "workers' optimizer.step() / zero_grad() and the gossip round as ONE launch per iteration")
     ap.add_argument("--pull", action="store_true", help="one process per GPU: gossip rounds over the pull "
                     "transport (partner rows / Choco messages read from the peers' HBM) instead of RCCL")
     a = ap.parse_args()
@@ -60,7 +63,8 @@ def main():
         tr = H.RankTrainer(args, H.model_factory(args), a.batches, rank, world,
                            transport="pull" if a.pull else None)
     else:
-        tr = H.VirtualTrainer(args, H.model_factory(args), a.batches, batched=a.batched or a.graph, graph=a.graph)
+        tr = H.VirtualTrainer(args, H.model_factory(args), a.batches, batched=a.batched or a.graph, graph=a.graph,
+                              fused_sgd=a.fused_sgd)
         if a.resume:
             tr.load(a.resume)
     import time
