@@ -75,6 +75,20 @@ def set_sgd_mix_tuning(**knobs):
         check(lib.mx_sgd_mix_set(k.encode(), int(v)), "mx_sgd_mix_set")
 
 
+_sgd_mix_bf16 = lib.mx_sgd_mix_bf16
+
+
+def sgd_mix_bf16_tuning():
+    """Current knobs of the mixed-precision fused SGD + mixing kernel (mx_sgd_mix_bf16_set)."""
+    return {k: int(lib.mx_sgd_mix_bf16_get(k.encode())) for k in SGD_TUNE_KEYS}
+
+
+def set_sgd_mix_bf16_tuning(**knobs):
+    _TUNE_GEN[0] += 1
+    for k, v in knobs.items():
+        check(lib.mx_sgd_mix_bf16_set(k.encode(), int(v)), "mx_sgd_mix_bf16_set")
+
+
 def partition(n, nranks):
     """Contiguous worker blocks [(row_base, n_local)] per rank (sizes differ by at most 1)."""
     base, extra = divmod(n, nranks)
@@ -511,6 +525,59 @@ class SgdLayout:
                           int(bool(nesterov)), int(bool(zero_grads)), 0)
 
 
+class SgdBf16Call(ctypes.Structure):
+    """mx_sgd_mix_bf16_call (include/matcha_gossip.h): the mixed-precision fused launch's arguments."""
+    _fields_ = [("w_ptrs_dev", ctypes.c_void_p), ("g_ptrs_dev", ctypes.c_void_p), ("m_ptrs_dev", ctypes.c_void_p),
+                ("p_ptrs_dev", ctypes.c_void_p), ("seg_len_dev", ctypes.c_void_p), ("tile_off_dev", ctypes.c_void_p),
+                ("plan_dev", ctypes.c_void_p), ("total_tiles", ctypes.c_int64), ("nseg", ctypes.c_int32),
+                ("n_slots", ctypes.c_int32), ("n_local", ctypes.c_int32), ("M", ctypes.c_int32),
+                ("alpha", ctypes.c_float), ("wd", ctypes.c_float), ("mom", ctypes.c_float),
+                ("nesterov", ctypes.c_int32), ("zero_grads", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+class SgdBf16Layout:
+    """Pointer tables of the mixed-precision fused kernel (csrc/sgd_mix_bf16.hip): row r's fp32 master of
+    segment s, its bfloat16 gradient, its fp32 momentum buffer (m_ptrs None without momentum) and its
+    bfloat16 model row, lengths in elements.  Each argument is a list over the rows of per-segment
+    device addresses."""
+
+    def __init__(self, seg_lens, w_ptrs, g_ptrs, m_ptrs, p_ptrs, n_local):
+        nseg = len(seg_lens)
+        seg_len = np.asarray(seg_lens, dtype=np.int64)
+        tile_off = np.zeros(nseg + 1, dtype=np.int64)
+        check(lib.mx_sgd_mix_bf16_layout(seg_len.ctypes.data, nseg, n_local, tile_off.ctypes.data),
+              "mx_sgd_mix_bf16_layout")
+
+        def table(rows):
+            t = np.zeros((nseg, n_local), dtype=np.int64)
+            for r, ptrs in enumerate(rows):
+                t[:, r] = ptrs
+            return torch.from_numpy(t).to("cuda")
+
+        self.nseg, self.n_local = nseg, n_local
+        self.tile = int(lib.mx_sgd_mix_bf16_tile(n_local))
+        self.total_tiles = int(tile_off[-1])
+        self.w_ptrs, self.g_ptrs, self.p_ptrs = table(w_ptrs), table(g_ptrs), table(p_ptrs)
+        self.m_ptrs = table(m_ptrs) if m_ptrs is not None else None
+        self.seg_len = torch.from_numpy(seg_len).to("cuda")
+        self.tile_off = torch.from_numpy(tile_off).to("cuda")
+        self.tune_gen = _TUNE_GEN[0]
+
+    def check_tile(self):
+        if self.tune_gen != _TUNE_GEN[0]:
+            if self.tile != lib.mx_sgd_mix_bf16_tile(self.n_local):
+                raise MXError("layout built for another mixed-precision fused SGD + mixing tile size")
+            self.tune_gen = _TUNE_GEN[0]
+
+    def call(self, engine, wd, mom, nesterov, zero_grads):
+        return SgdBf16Call(self.w_ptrs.data_ptr(), self.g_ptrs.data_ptr(),
+                           self.m_ptrs.data_ptr() if self.m_ptrs is not None else None, self.p_ptrs.data_ptr(),
+                           self.seg_len.data_ptr(), self.tile_off.data_ptr(), engine._plan_ptr, self.total_tiles,
+                           self.nseg, engine.n_slots, engine.n_local, engine.M, engine.alpha32,
+                           float(np.float32(wd)), float(np.float32(mom)), int(bool(nesterov)),
+                           int(bool(zero_grads)), 0)
+
+
 IDLE_MODES = {"skip": 0, "canonical": 1}
 
 
@@ -797,6 +864,7 @@ class VirtualWorkerGroup:
         self._chunk_cols = chunk_cols
         self._adopted = models if (models is not None and adopt) else None
         self._sgd = None                     # attach_sgd: the fused SGD + mixing launch's state
+        self.master_arena = self.master_rows = None   # attach_sgd(master_weights=True): fp32 masters of bf16 rows
         self._round_ctrs = {}                # device_rounds(K): per-round counters, one tensor per K
         if models is not None:
             if len(models) != self.n_local:
@@ -993,7 +1061,7 @@ class VirtualWorkerGroup:
         self.engine.mix_rounds_at(self.iter_dev, ctrs, self.layout, stream)
 
     # ------------------------------------------------------------------ fused SGD + mixing
-    def attach_sgd(self, momentum=0.0, weight_decay=0.0, nesterov=False, zero_grads=True):
+    def attach_sgd(self, momentum=0.0, weight_decay=0.0, nesterov=False, zero_grads=True, master_weights=False):
         """Give the group torch.optim.SGD's state (dampening 0) so that one launch per iteration
         applies every worker's update and the round's mix (csrc/sgd_mix.hip; the reference's
         optimizer.step() + zero_grad() + communicate(), train_mpi.py:131-142).
@@ -1005,12 +1073,26 @@ class VirtualWorkerGroup:
         optimizer.zero_grad() unnecessary -- and zero_grad(set_to_none=True), torch's default,
         would DETACH those views (later gradients would land in fresh tensors the kernel never
         reads): do not call it on an attached group, or pass set_to_none=False.
-        fp32 groups on one GPU only: every partner's updated row must exist before any exchange, so
-        a cross-GPU group is a different design."""
+        One GPU only: every partner's updated row must exist before any exchange, so a cross-GPU
+        group is a different design.
+
+        master_weights=True is the bfloat16 group's form (csrc/sgd_mix_bf16.hip; a ValueError on an
+        fp32 group, and a bfloat16 group refuses to attach without it): `master_arena` /
+        `master_rows` hold an fp32 master of every row, starting as the exact widening of `rows`;
+        the gradient arena is bfloat16 (each adopted parameter's .grad a bf16 view of it), the
+        momentum arena fp32.  The launch updates and mixes the MASTERS and rewrites `rows` as
+        bf16(master), rounded once to nearest even, so updates below half a bf16 ulp accumulate
+        instead of rounding away.  `rows` is write-only to the launch: anything written to `rows`
+        directly (sync_rows, a checkpoint without masters) is overwritten by bf16(master) at the
+        next step unless master_from_rows() is called after it."""
         if self._sgd is not None:
             raise RuntimeError("attach_sgd: already attached")
-        if self.dtype != torch.float32:
-            raise NotImplementedError("attach_sgd: the fused SGD + mixing kernel takes fp32 rows, not bfloat16")
+        if master_weights and self.dtype != torch.bfloat16:
+            raise ValueError("attach_sgd: master_weights=True is for bfloat16 groups; fp32 rows are their own masters")
+        if self.dtype != torch.float32 and not master_weights:
+            raise NotImplementedError("attach_sgd: a bfloat16 group needs fp32 master weights for its SGD step: "
+                                      "pass master_weights=True (the fp32 fused kernel does not take bfloat16 rows)")
+        mixed = bool(master_weights)
         if self.engine.comm is not None or self.engine.max_remote:
             raise NotImplementedError("attach_sgd: one GPU only (nranks = 1, no transport): the partners' updated "
                                       "rows must exist before any exchange")
@@ -1019,19 +1101,30 @@ class VirtualWorkerGroup:
         momentum, weight_decay = float(momentum), float(weight_decay)
         if nesterov and momentum == 0.0:
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        if lib.mx_sgd_mix_tile(self.n_local) <= 0 or self.engine.M > 32:
+        tile = lib.mx_sgd_mix_bf16_tile(self.n_local) if mixed else lib.mx_sgd_mix_tile(self.n_local)
+        if tile <= 0 or self.engine.M > 32:
             raise NotImplementedError(f"attach_sgd: {self.n_local} local rows / {self.engine.M} matchings exceed the "
                                       "fused kernel's 64 rows / 32 matchings")
-        self.grad_arena = torch.zeros((self.n_local, self.ld), dtype=torch.float32, device="cuda")
+        self.grad_arena = torch.zeros((self.n_local, self.ld), dtype=self.dtype, device="cuda")
         self.grads = self.grad_arena[:, :self.numel]
         self.mom_arena = self.momentum_rows = None
         if momentum != 0.0:
             self.mom_arena = torch.zeros((self.n_local, self.ld), dtype=torch.float32, device="cuda")
             self.momentum_rows = self.mom_arena[:, :self.numel]
-        lay = SgdLayout([self.numel], [[p] for p in self._row_ptrs],
-                        [[self.grad_arena[r].data_ptr()] for r in range(self.n_local)],
-                        [[self.mom_arena[r].data_ptr()] for r in range(self.n_local)] if momentum != 0.0 else None,
-                        self.n_local)
+        self.master_arena = self.master_rows = None
+
+        def row_ptrs(arena):
+            return [[arena[r].data_ptr()] for r in range(self.n_local)]
+
+        if mixed:
+            self.master_arena = self.arena.to(torch.float32)          # the exact widening, tails (zeros) included
+            self.master_rows = self.master_arena[:, :self.numel]
+            lay = SgdBf16Layout([self.numel], row_ptrs(self.master_arena), row_ptrs(self.grad_arena),
+                                row_ptrs(self.mom_arena) if momentum != 0.0 else None,
+                                [[p] for p in self._row_ptrs], self.n_local)
+        else:
+            lay = SgdLayout([self.numel], [[p] for p in self._row_ptrs], row_ptrs(self.grad_arena),
+                            row_ptrs(self.mom_arena) if momentum != 0.0 else None, self.n_local)
         call = lay.call(self.engine, weight_decay, momentum, nesterov, zero_grads)
         if self._adopted is not None:
             for r, m in enumerate(self._adopted):
@@ -1044,6 +1137,18 @@ class VirtualWorkerGroup:
         self.sgd_hyper = {"momentum": momentum, "weight_decay": weight_decay, "nesterov": bool(nesterov),
                           "zero_grads": bool(zero_grads)}
         self._sgd = (lay, call, ctypes.addressof(call))
+        self._sgd_fn = (_sgd_mix_bf16, lib.mx_sgd_mix_bf16_at, "mx_sgd_mix_bf16") if mixed else \
+                       (_sgd_mix, lib.mx_sgd_mix_at, "mx_sgd_mix")
+
+    def master_from_rows(self):
+        """Redo the masters as the exact widening of `rows` (attach_sgd(master_weights=True) groups).
+        Call it after anything that writes `rows` directly -- sync_rows, loading a checkpoint that
+        has no masters: the launch never reads `rows`, so such a write is otherwise overwritten by
+        bf16(master) at the next step."""
+        if self.master_rows is None:
+            raise MXError("master_from_rows: no master weights (attach_sgd(master_weights=True) on a bfloat16 group)")
+        with torch.no_grad():
+            self.master_rows.copy_(self.rows)
 
     def _sgd_state(self):
         if self._sgd is None:
@@ -1057,9 +1162,9 @@ class VirtualWorkerGroup:
         alone -- and returns whether the round mixed."""
         call = self._sgd_state()
         it = self.engine.round_index(it)
-        rc = _sgd_mix(call, it, lr, None, stream_ptr(stream))
+        rc = self._sgd_fn[0](call, it, lr, None, stream_ptr(stream))
         if rc:
-            check(rc, "mx_sgd_mix")
+            check(rc, self._sgd_fn[2])
         return bool(self.engine.any_active[it])
 
     def sgd_device_round(self, stream=None):
@@ -1069,8 +1174,8 @@ class VirtualWorkerGroup:
         counter outside the schedule makes the launch a no-op: no SGD step either."""
         call = self._sgd_state()
         s = stream_ptr(stream)
-        check(lib.mx_sgd_mix_at(call, self.iter_dev.data_ptr(), self.engine.T, 0.0, self.lr_dev.data_ptr(), s),
-              "mx_sgd_mix_at")
+        check(self._sgd_fn[1](call, self.iter_dev.data_ptr(), self.engine.T, 0.0, self.lr_dev.data_ptr(), s),
+              self._sgd_fn[2] + "_at")
         check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, s), "mx_iter_advance")
 
     def sgd_communicate(self, lr):
@@ -1086,11 +1191,14 @@ class VirtualWorkerGroup:
 
     def state_dict(self):
         """Checkpoint: the workers' rows and the iteration counter (resume on the same schedule);
-        with attach_sgd(momentum != 0) the momentum rows too."""
+        with attach_sgd(momentum != 0) the momentum rows too, and with master_weights=True the fp32
+        master rows."""
         state = {"kind": "decen", "iter": int(self.iter), "row_base": int(self.row_base),
                  "workers": list(self.workers), "rows": self.rows.detach().clone()}
         if self._sgd is not None and self.momentum_rows is not None:
             state["momentum_rows"] = self.momentum_rows.detach().clone()
+        if self.master_rows is not None:
+            state["master_rows"] = self.master_rows.detach().clone()
         return state
 
     def load_state_dict(self, state):
@@ -1102,10 +1210,15 @@ class VirtualWorkerGroup:
         have = self._sgd is not None and self.momentum_rows is not None
         if mom is not None and (not have or tuple(mom.shape) != tuple(self.momentum_rows.shape)):
             raise ValueError("checkpoint carries momentum rows: attach_sgd(momentum=...) before loading it")
+        master = state.get("master_rows")
+        if master is not None and (self.master_rows is None or tuple(master.shape) != tuple(self.master_rows.shape)):
+            raise ValueError("checkpoint carries master rows: attach_sgd(master_weights=True) before loading it")
         with torch.no_grad():
             self.rows.copy_(state["rows"])
             if have:                             # a checkpoint without them: the buffers start as zeros
                 self.momentum_rows.zero_() if mom is None else self.momentum_rows.copy_(mom)
+            if self.master_rows is not None:     # a checkpoint without them: the widened rows
+                self.master_rows.copy_(self.rows if master is None else master)
         self.iter = int(state["iter"])
 
     def communicate(self):

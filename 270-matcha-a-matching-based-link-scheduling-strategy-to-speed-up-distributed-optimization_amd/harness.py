@@ -197,11 +197,14 @@ class VirtualTrainer:
     step for all workers is a handful of batched launches plus the gossip kernel."""
 
     def __init__(self, args, model_fn, n_batches, device="cuda", batched=False, graph=False, fused_sgd=False):
-        """fused_sgd=True (non-batched, uncompressed, fp32 models): the workers' optimizer.step() /
+        """fused_sgd=True (non-batched, uncompressed): the workers' optimizer.step() /
         zero_grad() and the gossip round run as ONE launch (VirtualWorkerGroup.attach_sgd /
         sgd_communicate, csrc/sgd_mix.hip): backward() accumulates into the group's gradient arena,
         the optimizers stay constructed only because their param_groups carry the learning-rate
-        schedule, and checkpoints save the group's momentum rows.
+        schedule, and checkpoints save the group's momentum rows.  All-bfloat16 models train in
+        mixed precision (attach_sgd(master_weights=True), csrc/sgd_mix_bf16.hip): fp32 master rows
+        are updated and mixed, the bfloat16 models are their rounded image, and checkpoints save
+        the masters too.
 
         graph=True (with batched=True, decentralized gossip, one GPU): once the learning rate
         is constant within an epoch, the whole training iteration -- vmap'd forward / backward,
@@ -230,11 +233,13 @@ class VirtualTrainer:
             dts = {p.dtype for m in self.models for p in m.parameters()}
             self.group = VirtualWorkerGroup(self.GP, self.models,
                                             dtype=torch.bfloat16 if dts == {torch.bfloat16} else torch.float32)
+        mixed = self.fused_sgd and self.group.dtype == torch.bfloat16
         if self.fused_sgd:
-            if self.group.dtype != torch.float32:
-                raise ValueError("fused_sgd needs float32 models")
-            self.group.attach_sgd(args.momentum, 5e-4, args.nesterov)
+            # all-bfloat16 models: fp32 master weights, updated and mixed by the launch (csrc/sgd_mix_bf16.hip)
+            self.group.attach_sgd(args.momentum, 5e-4, args.nesterov, master_weights=mixed)
         sync_rows(self.group.rows)
+        if mixed:
+            self.group.master_from_rows()                        # the masters of the synchronized rows
         self.optimizers = [torch.optim.SGD(m.parameters(), lr=args.lr, momentum=args.momentum,
                                            weight_decay=5e-4, nesterov=args.nesterov, dampening=0)
                            for m in self.models]

@@ -310,6 +310,59 @@ int mx_sgd_mix(const mx_sgd_mix_call* call, int64_t iter, float lr, const float*
 int mx_sgd_mix_at(const mx_sgd_mix_call* call, const int64_t* iter_dev, int64_t n_iters, float lr,
                   const float* lr_dev, void* stream);
 
+/* ---------------------------------------------------------------- the hot path, mixed-precision SGD fused in
+ * mx_sgd_mix for models held in bfloat16: the optimizer works on fp32 MASTER rows, the master rows are
+ * what the round mixes, and the bfloat16 model row is the rounded image of its master, rewritten by every
+ * launch (csrc/sgd_mix_bf16.hip).  Per (segment, row) four arrays, every length in elements:
+ *   w  float*    fp32 master, read and written in place
+ *   g  uint16_t* bfloat16 gradient, read; overwritten with zeros when zero_grads != 0
+ *   m  float*    fp32 momentum buffer, read and written; no table (NULL) exactly when mom == 0
+ *   p  uint16_t* bfloat16 model row, WRITE ONLY: the kernel never reads it
+ * Arithmetic contract, per row and column (torch.optim.SGD, dampening 0, on the masters):
+ *   g32 = f32(g)                                  exact widening, bits << 16
+ *   d   = (wd != 0) ? fmaf(wd, w, g32) : g32
+ *   m   = fadd(fmul(mom, m), d);  d = nesterov ? fmaf(mom, m, d) : m      [mom != 0]; m is rounded twice
+ *   w'  = fmaf(-lr, d, w)
+ *   w   = mx_sgd_mix's round on the w' values (same plan record, alpha, selfweight, ascending
+ *         matchings, self term last; a row the record leaves alone, and every row of an all-zero
+ *         round, keeps w' as it is)
+ *   p   = bf16_rne(w)                             one rounding, to nearest even, of the value stored to w;
+ *                                                 NaN stays NaN, payload unspecified
+ * p is written for every row in every launch that runs, rows the round leaves alone included (their w
+ * changed by the SGD step).  Nothing is written at or past seg_len of a row in any of the four arrays.
+ * Traffic: 20 bytes per element (22 with zero_grads; 10 / 12 without momentum) against 64 unfused.
+ * Alignment rule: a lane holds 4 elements; where w and m of a (segment, row) are 16-byte aligned, g and
+ * p are 8-byte aligned and the 4 elements are in range, the accesses are 16 bytes on w / m and 8 bytes
+ * on g / p; elsewhere they are per element (4 / 2 bytes), zero-filled past the end.
+ * mx_sgd_mix_bf16_call is mx_sgd_mix_call with the four tables above; the other fields, the tile
+ * (mx_sgd_mix_bf16_tile: 1024 / 1024 / 512 / 256 columns, 0 above 64 rows), the layout prefix, the
+ * host-side refusals (MX_ERR_INVALID, nothing launched: n_slots != n_local, more than 64 rows, M outside
+ * [1, 32], a momentum table that does not match mom, nesterov without momentum, a null table -- p
+ * included) and the launch-side no-ops (a peer-reads plan record; for _at a counter outside
+ * [0, n_iters): none of the four arrays is written, the SGD step included) are mx_sgd_mix's.
+ * mx_sgd_mix_bf16_set / _get: "nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid", as
+ * mx_sgd_mix_set's and independent of them.  Speed only, never bits; none of them changes the tile. */
+typedef struct mx_sgd_mix_bf16_call {
+    float* const* w_ptrs_dev;
+    uint16_t* const* g_ptrs_dev;
+    float* const* m_ptrs_dev;
+    uint16_t* const* p_ptrs_dev;
+    const int64_t* seg_len_dev;
+    const int64_t* tile_off_dev;
+    const int32_t* plan_dev;
+    int64_t total_tiles;
+    int32_t nseg, n_slots, n_local, M;
+    float alpha, wd, mom;
+    int32_t nesterov, zero_grads, pad_;
+} mx_sgd_mix_bf16_call;
+int mx_sgd_mix_bf16_tile(int n_slots);
+int mx_sgd_mix_bf16_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host);
+int mx_sgd_mix_bf16_set(const char* key, int value);
+int mx_sgd_mix_bf16_get(const char* key);
+int mx_sgd_mix_bf16(const mx_sgd_mix_bf16_call* call, int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_sgd_mix_bf16_at(const mx_sgd_mix_bf16_call* call, const int64_t* iter_dev, int64_t n_iters, float lr,
+                       const float* lr_dev, void* stream);
+
 /* ---------------------------------------------------------------- flatten / unflatten
  * mx_gather replaces flatten_tensors (comm_helpers.py:12-30): flat[off[s] + i] = src[s][i].
  * mx_scatter is the copy_ loop of reset_model over unflatten_tensors views

@@ -3,6 +3,7 @@
     python tools/train_gpu.py --workers 8 --epoch 2 --batches 50                 # 8 virtual workers, 1 GPU
     python tools/train_gpu.py --compress --budget 0.5                           # ChocoSGD
     python tools/train_gpu.py --momentum 0.9 --fused-sgd                        # SGD step fused into the round
+    python tools/train_gpu.py --momentum 0.9 --fused-sgd --bf16                 # the same, bf16 models + fp32 masters
     torchrun --nproc-per-node N --master-addr 127.0.0.1 tools/train_gpu.py     # one worker per GPU
 
 Flags follow train_mpi.py:205-231 (same names and defaults where they apply); --workers,
@@ -45,8 +46,11 @@ def main():
     ap.add_argument("--batched", action="store_true", help="one vmap'd step for all virtual workers")
     ap.add_argument("--graph", action="store_true", help="with --batched: replay each iteration (step + "
                     "gossip round) as one captured HIP graph once the learning rate is constant")
-    ap.add_argument("--fused-sgd", action="store_true", help="one GPU, per-worker (non-batched) fp32 training: the "
+    ap.add_argument("--fused-sgd", action="store_true", help="one GPU, per-worker (non-batched) training: the "
                     "workers' optimizer.step() / zero_grad() and the gossip round as ONE launch per iteration")
+    ap.add_argument("--bf16", action="store_true", help="one GPU: the models are cast to bfloat16 (bfloat16 gossip "
+                    "rows); with --fused-sgd the step runs in mixed precision on fp32 master weights, which the "
+                    "round mixes, and the bfloat16 models are their rounded image")
     ap.add_argument("--pull", action="store_true", help="one process per GPU: gossip rounds over the pull "
                     "transport (partner rows / Choco messages read from the peers' HBM) instead of RCCL")
     a = ap.parse_args()
@@ -58,12 +62,20 @@ def main():
                          compress=a.compress, consensus_lr=a.consensus_lr, randomSeed=a.randomSeed,
                          size=a.workers if world == 1 else world)
     import torch
+    model_fn = H.model_factory(args)
+    if a.bf16:
+        if world > 1:
+            ap.error("--bf16: bfloat16 worker rows are mixed on one GPU only")
+        fp32_fn = model_fn
+
+        def model_fn():
+            return fp32_fn().to(torch.bfloat16)
     if world > 1:
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
-        tr = H.RankTrainer(args, H.model_factory(args), a.batches, rank, world,
+        tr = H.RankTrainer(args, model_fn, a.batches, rank, world,
                            transport="pull" if a.pull else None)
     else:
-        tr = H.VirtualTrainer(args, H.model_factory(args), a.batches, batched=a.batched or a.graph, graph=a.graph,
+        tr = H.VirtualTrainer(args, model_fn, a.batches, batched=a.batched or a.graph, graph=a.graph,
                               fused_sgd=a.fused_sgd)
         if a.resume:
             tr.load(a.resume)
