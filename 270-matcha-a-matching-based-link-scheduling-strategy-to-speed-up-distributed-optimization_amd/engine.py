@@ -13,6 +13,7 @@ Per round (reference: decenCommunicator.communicate, communicator.py:133-158):
 Everything is enqueued on one HIP stream; nothing is copied to or from the host per round.
 """
 import ctypes
+import math
 import sys
 import time
 import weakref
@@ -87,6 +88,48 @@ def set_sgd_mix_bf16_tuning(**knobs):
     _TUNE_GEN[0] += 1
     for k, v in knobs.items():
         check(lib.mx_sgd_mix_bf16_set(k.encode(), int(v)), "mx_sgd_mix_bf16_set")
+
+
+_adamw_mix = lib.mx_adamw_mix
+
+
+def adamw_mix_tuning():
+    """Current knobs of the fused AdamW + mixing kernel (mx_adamw_mix_set)."""
+    return {k: int(lib.mx_adamw_mix_get(k.encode())) for k in SGD_TUNE_KEYS}
+
+
+def set_adamw_mix_tuning(**knobs):
+    _TUNE_GEN[0] += 1
+    for k, v in knobs.items():
+        check(lib.mx_adamw_mix_set(k.encode(), int(v)), "mx_adamw_mix_set")
+
+
+ADAM_BIAS_MAX = 1 << 21     # entries (16 MB): reached at beta2 ~ 0.99999
+
+
+def adam_bias_table(beta1, beta2):
+    """Adam's bias corrections as the fused kernel reads them (include/matcha_gossip.h, mx_adamw_mix):
+    float32 [n_bias, 2], row t-1 = (f32(1 - beta1**t), f32(sqrt(1 - beta2**t))) in Python floats, as
+    torch.optim.Adam computes them, ending at the first row where both are exactly 1.0f -- every later
+    step uses that row, exactly.  ValueError for betas outside [0, 1) or that do not get there within
+    2^21 rows."""
+    beta1, beta2 = float(beta1), float(beta2)
+    if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+        raise ValueError(f"adam_bias_table: betas ({beta1}, {beta2}) outside [0, 1)")
+    one = np.float32(1.0)
+
+    def row(t):
+        return np.float32(1.0 - beta1 ** t), np.float32(math.sqrt(1.0 - beta2 ** t))
+
+    # both columns are non-decreasing in t, so the last admissible row decides before anything is built
+    if row(ADAM_BIAS_MAX) != (one, one):
+        raise ValueError(f"adam_bias_table: betas ({beta1}, {beta2}) do not saturate within {ADAM_BIAS_MAX} steps")
+    rows = []
+    for t in range(1, ADAM_BIAS_MAX + 1):
+        rows.append(row(t))
+        if rows[-1] == (one, one):
+            break
+    return np.array(rows, dtype=np.float32).reshape(-1, 2)
 
 
 def partition(n, nranks):
@@ -525,6 +568,67 @@ class SgdLayout:
                           int(bool(nesterov)), int(bool(zero_grads)), 0)
 
 
+class AdamwMixCall(ctypes.Structure):
+    """mx_adamw_mix_call (include/matcha_gossip.h): the fused AdamW + mixing launch's arguments, packed once."""
+    _fields_ = [("x_ptrs_dev", ctypes.c_void_p), ("g_ptrs_dev", ctypes.c_void_p), ("m_ptrs_dev", ctypes.c_void_p),
+                ("v_ptrs_dev", ctypes.c_void_p), ("seg_len_dev", ctypes.c_void_p), ("tile_off_dev", ctypes.c_void_p),
+                ("plan_dev", ctypes.c_void_p), ("bias_dev", ctypes.c_void_p), ("total_tiles", ctypes.c_int64),
+                ("n_bias", ctypes.c_int64), ("nseg", ctypes.c_int32), ("n_slots", ctypes.c_int32),
+                ("n_local", ctypes.c_int32), ("M", ctypes.c_int32), ("alpha", ctypes.c_float),
+                ("wd", ctypes.c_float), ("omb1", ctypes.c_float), ("beta2", ctypes.c_float),
+                ("omb2", ctypes.c_float), ("eps", ctypes.c_float), ("decoupled", ctypes.c_int32),
+                ("zero_grads", ctypes.c_int32)]
+
+
+class AdamwLayout:
+    """Pointer tables of the fused AdamW + mixing kernel (csrc/adamw_mix.hip): row r's copy of segment s,
+    its gradient, exp_avg and exp_avg_sq, fp32, lengths in floats, and the bias-correction table
+    (adam_bias_table) on the device.  x_ptrs / g_ptrs / m_ptrs / v_ptrs are lists over the rows of
+    per-segment device addresses."""
+
+    def __init__(self, seg_lens, x_ptrs, g_ptrs, m_ptrs, v_ptrs, n_local, bias):
+        nseg = len(seg_lens)
+        seg_len = np.asarray(seg_lens, dtype=np.int64)
+        tile_off = np.zeros(nseg + 1, dtype=np.int64)
+        check(lib.mx_adamw_mix_layout(seg_len.ctypes.data, nseg, n_local, tile_off.ctypes.data),
+              "mx_adamw_mix_layout")
+
+        def table(rows):
+            t = np.zeros((nseg, n_local), dtype=np.int64)
+            for r, ptrs in enumerate(rows):
+                t[:, r] = ptrs
+            return torch.from_numpy(t).to("cuda")
+
+        self.nseg, self.n_local = nseg, n_local
+        self.tile = int(lib.mx_adamw_mix_tile(n_local))
+        self.total_tiles = int(tile_off[-1])
+        self.x_ptrs, self.g_ptrs, self.m_ptrs, self.v_ptrs = table(x_ptrs), table(g_ptrs), table(m_ptrs), table(v_ptrs)
+        self.seg_len = torch.from_numpy(seg_len).to("cuda")
+        self.tile_off = torch.from_numpy(tile_off).to("cuda")
+        bias = np.ascontiguousarray(bias, dtype=np.float32)
+        if bias.ndim != 2 or bias.shape[1] != 2 or bias.shape[0] < 1:
+            raise ValueError("bias table: float32 [n_bias, 2]")
+        self.n_bias = int(bias.shape[0])
+        self.bias = torch.from_numpy(bias).to("cuda")
+        self.tune_gen = _TUNE_GEN[0]
+
+    def check_tile(self):
+        if self.tune_gen != _TUNE_GEN[0]:
+            if self.tile != lib.mx_adamw_mix_tile(self.n_local):
+                raise MXError("layout built for another fused AdamW + mixing tile size")
+            self.tune_gen = _TUNE_GEN[0]
+
+    def call(self, engine, betas, eps, wd, decoupled, zero_grads):
+        """betas are the Python floats: omb1 / omb2 are rounded from the fp64 values 1 - beta."""
+        b1, b2 = float(betas[0]), float(betas[1])
+        return AdamwMixCall(self.x_ptrs.data_ptr(), self.g_ptrs.data_ptr(), self.m_ptrs.data_ptr(),
+                            self.v_ptrs.data_ptr(), self.seg_len.data_ptr(), self.tile_off.data_ptr(),
+                            engine._plan_ptr, self.bias.data_ptr(), self.total_tiles, self.n_bias, self.nseg,
+                            engine.n_slots, engine.n_local, engine.M, engine.alpha32, float(np.float32(wd)),
+                            float(np.float32(1.0 - b1)), float(np.float32(b2)), float(np.float32(1.0 - b2)),
+                            float(np.float32(eps)), int(bool(decoupled)), int(bool(zero_grads)))
+
+
 class SgdBf16Call(ctypes.Structure):
     """mx_sgd_mix_bf16_call (include/matcha_gossip.h): the mixed-precision fused launch's arguments."""
     _fields_ = [("w_ptrs_dev", ctypes.c_void_p), ("g_ptrs_dev", ctypes.c_void_p), ("m_ptrs_dev", ctypes.c_void_p),
@@ -865,6 +969,7 @@ class VirtualWorkerGroup:
         self._adopted = models if (models is not None and adopt) else None
         self._sgd = None                     # attach_sgd: the fused SGD + mixing launch's state
         self.master_arena = self.master_rows = None   # attach_sgd(master_weights=True): fp32 masters of bf16 rows
+        self._adamw = None                   # attach_adamw: the fused AdamW + mixing launch's state
         self._round_ctrs = {}                # device_rounds(K): per-round counters, one tensor per K
         if models is not None:
             if len(models) != self.n_local:
@@ -1087,6 +1192,8 @@ class VirtualWorkerGroup:
         next step unless master_from_rows() is called after it."""
         if self._sgd is not None:
             raise RuntimeError("attach_sgd: already attached")
+        if self._adamw is not None:
+            raise RuntimeError("attach_sgd: the group already carries AdamW state (attach_adamw)")
         if master_weights and self.dtype != torch.bfloat16:
             raise ValueError("attach_sgd: master_weights=True is for bfloat16 groups; fp32 rows are their own masters")
         if self.dtype != torch.float32 and not master_weights:
@@ -1189,16 +1296,123 @@ class VirtualWorkerGroup:
         self.wait_round()
         return time.time() - tic
 
+    # ------------------------------------------------------------------ fused AdamW + mixing
+    def attach_adamw(self, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled=True, zero_grads=True):
+        """Give the group torch.optim.AdamW's state (decoupled=False: torch.optim.Adam's, the decay as
+        an L2 term in the gradient; no amsgrad, no maximize) so that one launch per iteration applies
+        every worker's update and the round's mix (csrc/adamw_mix.hip).
+
+        Allocates `grad_arena` / `grads` as attach_sgd does (adopted parameters' .grad become views
+        of it; see attach_sgd on zero_grad), `exp_avg_arena` / `exp_avg_rows` and `exp_avg_sq_arena`
+        / `exp_avg_sq_rows` (fp32 zeros), and the bias-correction table (adam_bias_table) on the
+        device.  `opt_step` counts the optimizer steps taken (adamw_step runs step opt_step + 1);
+        `opt_step_dev` (int64 CUDA) is the NEXT step of adamw_device_round, and `lr_dev` its
+        learning rate.  fp32 groups on one GPU only."""
+        if self._adamw is not None:
+            raise RuntimeError("attach_adamw: already attached")
+        if self._sgd is not None:
+            raise RuntimeError("attach_adamw: the group already carries SGD state (attach_sgd)")
+        if self.dtype != torch.float32:
+            raise NotImplementedError("attach_adamw: bfloat16 groups need fp32 master weights under AdamW, which "
+                                      "the fused kernel does not have yet; fp32 groups only")
+        if self.engine.comm is not None or self.engine.max_remote:
+            raise NotImplementedError("attach_adamw: one GPU only (nranks = 1, no transport): the partners' updated "
+                                      "rows must exist before any exchange")
+        if self._chunk_cols:
+            raise NotImplementedError("attach_adamw: not with chunk_cols (the column-pipelined cross-GPU exchange)")
+        if lib.mx_adamw_mix_tile(self.n_local) <= 0 or self.engine.M > 32:
+            raise NotImplementedError(f"attach_adamw: {self.n_local} local rows / {self.engine.M} matchings exceed "
+                                      "the fused kernel's 64 rows / 32 matchings")
+        betas = (float(betas[0]), float(betas[1]))
+        eps, weight_decay = float(eps), float(weight_decay)
+        if eps < 0.0 or weight_decay < 0.0:
+            raise ValueError("attach_adamw: eps and weight_decay must not be negative")
+        bias = adam_bias_table(*betas)                               # ValueError for betas it cannot serve
+
+        def arena():
+            return torch.zeros((self.n_local, self.ld), dtype=torch.float32, device="cuda")
+
+        def row_ptrs(a):
+            return [[a[r].data_ptr()] for r in range(self.n_local)]
+
+        self.grad_arena, self.exp_avg_arena, self.exp_avg_sq_arena = arena(), arena(), arena()
+        self.grads = self.grad_arena[:, :self.numel]
+        self.exp_avg_rows = self.exp_avg_arena[:, :self.numel]
+        self.exp_avg_sq_rows = self.exp_avg_sq_arena[:, :self.numel]
+        lay = AdamwLayout([self.numel], [[p] for p in self._row_ptrs], row_ptrs(self.grad_arena),
+                          row_ptrs(self.exp_avg_arena), row_ptrs(self.exp_avg_sq_arena), self.n_local, bias)
+        call = lay.call(self.engine, betas, eps, weight_decay, decoupled, zero_grads)
+        if self._adopted is not None:
+            for r, m in enumerate(self._adopted):
+                off = 0
+                for p in _params(m):
+                    k = p.numel()
+                    p.grad = self.grad_arena[r, off:off + k].view(p.shape)
+                    off += k
+        self.lr_dev = torch.zeros(1, dtype=torch.float32, device="cuda")   # adamw_device_round's learning rate
+        self.opt_step = 0
+        self.opt_step_dev = torch.ones(1, dtype=torch.int64, device="cuda")
+        self.adamw_hyper = {"betas": betas, "eps": eps, "weight_decay": weight_decay, "decoupled": bool(decoupled),
+                            "zero_grads": bool(zero_grads)}
+        self._adamw = (lay, call, ctypes.addressof(call))
+
+    def _adamw_state(self):
+        if self._adamw is None:
+            raise MXError("no AdamW state: call attach_adamw() first")
+        self._adamw[0].check_tile()
+        return self._adamw[2]
+
+    def adamw_step(self, it, lr, stream=None):
+        """Enqueue ONE launch: every local worker's AdamW update number opt_step + 1 at learning rate
+        `lr`, then round `it`'s mix of the updated rows; opt_step += 1.  Always launches -- an
+        all-zero round is the optimizer step alone -- and returns whether the round mixed."""
+        call = self._adamw_state()
+        it = self.engine.round_index(it)
+        rc = _adamw_mix(call, it, self.opt_step + 1, lr, None, stream_ptr(stream))
+        if rc:
+            check(rc, "mx_adamw_mix")
+        self.opt_step += 1
+        return bool(self.engine.any_active[it])
+
+    def adamw_device_round(self, stream=None):
+        """Graph-replayable adamw_step: the round is read from `self.iter_dev`, the optimizer step from
+        `self.opt_step_dev` and the learning rate from `self.lr_dev` when the kernel runs, then both
+        counters are advanced (unconditionally, as sgd_device_round advances iter_dev), so one
+        captured launch triple serves every iteration.  A round counter outside the schedule or a
+        step below 1 makes the launch a no-op.  `self.opt_step` (adamw_step's host counter) is not
+        touched."""
+        call = self._adamw_state()
+        s = stream_ptr(stream)
+        check(lib.mx_adamw_mix_at(call, self.iter_dev.data_ptr(), self.engine.T, self.opt_step_dev.data_ptr(), 0.0,
+                                  self.lr_dev.data_ptr(), s), "mx_adamw_mix_at")
+        check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, s), "mx_iter_advance")
+        check(lib.mx_iter_advance(self.opt_step_dev.data_ptr(), 1, s), "mx_iter_advance")
+
+    def adamw_communicate(self, lr):
+        """optimizer.step() + zero_grad() + communicate() of every worker at the group's own
+        iteration counter, as one launch; returns seconds like communicate()."""
+        it = self.iter
+        self.iter += 1
+        torch.cuda.synchronize()
+        tic = time.time()
+        self.adamw_step(it, lr)
+        self.wait_round()
+        return time.time() - tic
+
     def state_dict(self):
         """Checkpoint: the workers' rows and the iteration counter (resume on the same schedule);
-        with attach_sgd(momentum != 0) the momentum rows too, and with master_weights=True the fp32
-        master rows."""
+        with attach_sgd(momentum != 0) the momentum rows too, with master_weights=True the fp32
+        master rows, and with attach_adamw the exp_avg / exp_avg_sq rows and the step count."""
         state = {"kind": "decen", "iter": int(self.iter), "row_base": int(self.row_base),
                  "workers": list(self.workers), "rows": self.rows.detach().clone()}
         if self._sgd is not None and self.momentum_rows is not None:
             state["momentum_rows"] = self.momentum_rows.detach().clone()
         if self.master_rows is not None:
             state["master_rows"] = self.master_rows.detach().clone()
+        if self._adamw is not None:
+            state["exp_avg_rows"] = self.exp_avg_rows.detach().clone()
+            state["exp_avg_sq_rows"] = self.exp_avg_sq_rows.detach().clone()
+            state["opt_step"] = int(self.opt_step)
         return state
 
     def load_state_dict(self, state):
@@ -1213,8 +1427,17 @@ class VirtualWorkerGroup:
         master = state.get("master_rows")
         if master is not None and (self.master_rows is None or tuple(master.shape) != tuple(self.master_rows.shape)):
             raise ValueError("checkpoint carries master rows: attach_sgd(master_weights=True) before loading it")
+        adam = [state.get(k) for k in ("exp_avg_rows", "exp_avg_sq_rows")]
+        if any(a is not None for a in adam) or state.get("opt_step") is not None:
+            if self._adamw is None or any(a is None or tuple(a.shape) != tuple(self.rows.shape) for a in adam):
+                raise ValueError("checkpoint carries Adam state (exp_avg rows): attach_adamw() before loading it")
         with torch.no_grad():
             self.rows.copy_(state["rows"])
+            if self._adamw is not None:          # a checkpoint without them: zero buffers, step 0
+                for rows, a in zip((self.exp_avg_rows, self.exp_avg_sq_rows), adam):
+                    rows.zero_() if a is None else rows.copy_(a)
+                self.opt_step = int(state.get("opt_step") or 0)
+                self.opt_step_dev.fill_(self.opt_step + 1)
             if have:                             # a checkpoint without them: the buffers start as zeros
                 self.momentum_rows.zero_() if mom is None else self.momentum_rows.copy_(mom)
             if self.master_rows is not None:     # a checkpoint without them: the widened rows

@@ -196,7 +196,8 @@ class VirtualTrainer:
     element-wise op sequence of torch.optim.SGD) runs once over the stacked views -- a training
     step for all workers is a handful of batched launches plus the gossip kernel."""
 
-    def __init__(self, args, model_fn, n_batches, device="cuda", batched=False, graph=False, fused_sgd=False):
+    def __init__(self, args, model_fn, n_batches, device="cuda", batched=False, graph=False, fused_sgd=False,
+                 fused_adamw=False, adamw_hyper=None):
         """fused_sgd=True (non-batched, uncompressed): the workers' optimizer.step() /
         zero_grad() and the gossip round run as ONE launch (VirtualWorkerGroup.attach_sgd /
         sgd_communicate, csrc/sgd_mix.hip): backward() accumulates into the group's gradient arena,
@@ -205,6 +206,12 @@ class VirtualTrainer:
         mixed precision (attach_sgd(master_weights=True), csrc/sgd_mix_bf16.hip): fp32 master rows
         are updated and mixed, the bfloat16 models are their rounded image, and checkpoints save
         the masters too.
+
+        fused_adamw=True (same conditions, fp32 models, not together with fused_sgd): the same with
+        AdamW's update in the launch (VirtualWorkerGroup.attach_adamw / adamw_communicate,
+        csrc/adamw_mix.hip): betas (0.9, 0.999), eps 1e-8 and the harness's weight decay 5e-4 as the
+        decoupled decay, or what adamw_hyper (attach_adamw's keyword arguments) overrides; checkpoints
+        save exp_avg / exp_avg_sq rows and the step count.
 
         graph=True (with batched=True, decentralized gossip, one GPU): once the learning rate
         is constant within an epoch, the whole training iteration -- vmap'd forward / backward,
@@ -219,6 +226,12 @@ class VirtualTrainer:
         self.fused_sgd = bool(fused_sgd)
         if self.fused_sgd and (batched or args.compress):
             raise ValueError("fused_sgd needs per-worker (non-batched), uncompressed training: the vmap path's "
+                             "gradients are fresh tensors every iteration and ChocoSGD mixes compressed messages")
+        self.fused_adamw = bool(fused_adamw)
+        if self.fused_adamw and self.fused_sgd:
+            raise ValueError("fused_adamw and fused_sgd are mutually exclusive: the group carries one optimizer")
+        if self.fused_adamw and (batched or args.compress):
+            raise ValueError("fused_adamw needs per-worker (non-batched), uncompressed training: the vmap path's "
                              "gradients are fresh tensors every iteration and ChocoSGD mixes compressed messages")
         self.GP = make_topology(args, 0, size, args.epoch * n_batches)
         self.models = []
@@ -237,6 +250,12 @@ class VirtualTrainer:
         if self.fused_sgd:
             # all-bfloat16 models: fp32 master weights, updated and mixed by the launch (csrc/sgd_mix_bf16.hip)
             self.group.attach_sgd(args.momentum, 5e-4, args.nesterov, master_weights=mixed)
+        if self.fused_adamw:
+            if self.group.dtype != torch.float32:
+                raise ValueError("fused_adamw needs fp32 models: mixed-precision AdamW is not fused yet")
+            hyper = {"betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 5e-4, "decoupled": True}
+            hyper.update(adamw_hyper or {})
+            self.group.attach_adamw(**hyper)
         sync_rows(self.group.rows)
         if mixed:
             self.group.master_from_rows()                        # the masters of the synchronized rows
@@ -417,7 +436,7 @@ class VirtualTrainer:
                     top1[r].update(acc1[0].item(), data.size(0))
                     loss.backward()
                     lr = update_learning_rate(opt, epoch, args, itr=b, itr_per_epoch=self.n_batches)
-                    if not self.fused_sgd:               # fused: the update runs inside the gossip launch
+                    if not (self.fused_sgd or self.fused_adamw):   # fused: the update runs inside the gossip launch
                         opt.step()
                         opt.zero_grad()
                     comp[r] += time.time() - t0
@@ -425,6 +444,8 @@ class VirtualTrainer:
                 on_round("before", self)
             if self.fused_sgd:                               # step + zero_grad + communicate: one launch
                 comm_time += self.group.sgd_communicate(lr)
+            elif self.fused_adamw:
+                comm_time += self.group.adamw_communicate(lr)
             else:
                 comm_time += self.communicate()              # train_mpi.py:142, all workers at once
             self._dev_iter_synced = False

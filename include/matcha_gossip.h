@@ -363,6 +363,72 @@ int mx_sgd_mix_bf16(const mx_sgd_mix_bf16_call* call, int64_t iter, float lr, co
 int mx_sgd_mix_bf16_at(const mx_sgd_mix_bf16_call* call, const int64_t* iter_dev, int64_t n_iters, float lr,
                        const float* lr_dev, void* stream);
 
+/* ---------------------------------------------------------------- the hot path, AdamW / Adam step fused in
+ * mx_sgd_mix with torch.optim.AdamW's (decoupled != 0) or torch.optim.Adam's (decoupled == 0) update in
+ * place of SGD's (csrc/adamw_mix.hip): fp32 rows, one GPU, every partner local, one launch per training
+ * iteration.  No amsgrad, no maximize.  Per row and column, with x, g, m, v the parameter, gradient,
+ * exp_avg and exp_avg_sq elements, every operation ONE IEEE fp32 rounding (explicit fmas, correctly
+ * rounded square root and division, denormals kept):
+ *   decay = fmaf(-lr, wd, 1.0f)                              once per launch
+ *   x1 = (wd != 0 &&  decoupled) ? fmul(x, decay) : x        AdamW: p.mul_(1 - lr*wd)
+ *   g1 = (wd != 0 && !decoupled) ? fmaf(wd, x, g) : g        Adam:  g.add(p, alpha=wd)
+ *   m' = fmaf(omb1, fsub(g1, m), m)                          exp_avg.lerp_(g, 1 - beta1)
+ *   v' = fmaf(omb2, fmul(g1, g1), fmul(beta2, v))            exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
+ *   den = fadd(fdiv(fsqrt(v'), bc2s), eps)
+ *   ss  = fdiv(lr, bc1)                                      once per launch
+ *   x'  = fmaf(-ss, fdiv(m', den), x1)
+ * and then mx_sgd_mix's round on the x' values (same plan record, alpha, selfweight, ascending
+ * matchings, self term last; a row the record leaves alone, and every row of an all-zero round, keeps
+ * x' as it is -- an all-zero round is the optimizer step alone, NOT a no-op).  wd, eps and beta2 are the
+ * fp32 roundings of the Python floats, omb1 / omb2 the fp32 roundings of the fp64 values 1 - beta1 and
+ * 1 - beta2; m and v start as zeros.
+ * Bias correction: (bc1, bc2s) of optimizer step t >= 1 are bias_dev[min(t, n_bias) - 1], bias_dev being
+ * float [n_bias][2] with entry t-1 = (f32(1 - beta1**t), f32(sqrt(1 - beta2**t))) computed by the host in
+ * double precision, as torch does, and ending at the first entry where both are exactly 1.0f (every
+ * later step uses it, exactly).  Nothing computes pow on the device, so a launch is bit-reproducible
+ * and graph-replayable.
+ * Traffic: 28 bytes per element (32 with zero_grads) against 88 for the torch op sequence + the round.
+ * mx_adamw_mix_call is mx_sgd_mix_call with four tables -- x / g / m / v_ptrs_dev, float* [nseg][n_local];
+ * x, m and v are updated in place, g is read only or overwritten with zeros when zero_grads != 0, and
+ * nothing is written at or past seg_len of a row in any of the four -- plus the bias table.  The tile
+ * (mx_adamw_mix_tile: 1024 / 1024 / 512 / 256 columns for the 8 / 16 / 32 / 64-row classes, 0 above 64
+ * rows), the layout prefix and the host-side refusals (MX_ERR_INVALID, nothing launched:
+ * n_slots != n_local, more than 64 rows, M outside [1, 32], a null table, n_bias < 1) are mx_sgd_mix's.
+ * 16-byte accesses where the x, g, m and v pointers of a (segment, row) are all 16-byte aligned and the 4
+ * elements are in range, 4-byte accesses elsewhere.
+ * mx_adamw_mix(call, iter, step, lr, lr_dev, stream): round `iter` at optimizer step `step`; step < 1 is
+ * MX_ERR_INVALID and nothing is launched.  A non-NULL lr_dev (device float) overrides lr and is read
+ * when the kernel runs.
+ * mx_adamw_mix_at: the graph-replayable form: round *iter_dev, step *step_dev (both device int64,
+ * advanced by the caller, e.g. mx_iter_advance).  An iteration counter outside [0, n_iters) or a step
+ * below 1 makes the launch a complete no-op: none of x, g, m, v is written.  So does a plan record with
+ * the peer-reads bit, in either form.
+ * mx_adamw_mix_set / _get: "nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid", as
+ * mx_sgd_mix_set's and independent of them.  Speed only, never bits; none of them changes the tile. */
+typedef struct mx_adamw_mix_call {
+    float* const* x_ptrs_dev;
+    float* const* g_ptrs_dev;
+    float* const* m_ptrs_dev;
+    float* const* v_ptrs_dev;
+    const int64_t* seg_len_dev;
+    const int64_t* tile_off_dev;
+    const int32_t* plan_dev;
+    const float* bias_dev;
+    int64_t total_tiles;
+    int64_t n_bias;
+    int32_t nseg, n_slots, n_local, M;
+    float alpha, wd, omb1, beta2, omb2, eps;
+    int32_t decoupled, zero_grads;
+} mx_adamw_mix_call;
+int mx_adamw_mix_tile(int n_slots);
+int mx_adamw_mix_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host);
+int mx_adamw_mix_set(const char* key, int value);
+int mx_adamw_mix_get(const char* key);
+int mx_adamw_mix(const mx_adamw_mix_call* call, int64_t iter, int64_t step, float lr, const float* lr_dev,
+                 void* stream);
+int mx_adamw_mix_at(const mx_adamw_mix_call* call, const int64_t* iter_dev, int64_t n_iters,
+                    const int64_t* step_dev, float lr, const float* lr_dev, void* stream);
+
 /* ---------------------------------------------------------------- flatten / unflatten
  * mx_gather replaces flatten_tensors (comm_helpers.py:12-30): flat[off[s] + i] = src[s][i].
  * mx_scatter is the copy_ loop of reset_model over unflatten_tensors views
