@@ -57,6 +57,12 @@ SIGNATURES = {
     "mx_adamw_mix_get": (c_int, [ctypes.c_char_p]),
     "mx_adamw_mix": (c_int, [c_p, c_i64, c_i64, c_f32, c_p, c_p]),
     "mx_adamw_mix_at": (c_int, [c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
+    "mx_adamw_mix_bf16_tile": (c_int, [c_int]),
+    "mx_adamw_mix_bf16_layout": (c_int, [c_p, c_int, c_int, c_p]),
+    "mx_adamw_mix_bf16_set": (c_int, [ctypes.c_char_p, c_int]),
+    "mx_adamw_mix_bf16_get": (c_int, [ctypes.c_char_p]),
+    "mx_adamw_mix_bf16": (c_int, [c_p, c_i64, c_i64, c_f32, c_p, c_p]),
+    "mx_adamw_mix_bf16_at": (c_int, [c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
     "mx_gather": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p]),
     "mx_scatter": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p]),
     "mx_topk_work_bytes": (ctypes.c_size_t, [c_i64]),

@@ -104,6 +104,20 @@ def set_adamw_mix_tuning(**knobs):
         check(lib.mx_adamw_mix_set(k.encode(), int(v)), "mx_adamw_mix_set")
 
 
+_adamw_mix_bf16 = lib.mx_adamw_mix_bf16
+
+
+def adamw_mix_bf16_tuning():
+    """Current knobs of the mixed-precision fused AdamW + mixing kernel (mx_adamw_mix_bf16_set)."""
+    return {k: int(lib.mx_adamw_mix_bf16_get(k.encode())) for k in SGD_TUNE_KEYS}
+
+
+def set_adamw_mix_bf16_tuning(**knobs):
+    _TUNE_GEN[0] += 1
+    for k, v in knobs.items():
+        check(lib.mx_adamw_mix_bf16_set(k.encode(), int(v)), "mx_adamw_mix_bf16_set")
+
+
 ADAM_BIAS_MAX = 1 << 21     # entries (16 MB): reached at beta2 ~ 0.99999
 
 
@@ -682,6 +696,69 @@ class SgdBf16Layout:
                            int(bool(zero_grads)), 0)
 
 
+class AdamwBf16Call(ctypes.Structure):
+    """mx_adamw_mix_bf16_call (include/matcha_gossip.h): the mixed-precision fused AdamW launch's arguments."""
+    _fields_ = [("w_ptrs_dev", ctypes.c_void_p), ("g_ptrs_dev", ctypes.c_void_p), ("m_ptrs_dev", ctypes.c_void_p),
+                ("v_ptrs_dev", ctypes.c_void_p), ("p_ptrs_dev", ctypes.c_void_p), ("seg_len_dev", ctypes.c_void_p),
+                ("tile_off_dev", ctypes.c_void_p), ("plan_dev", ctypes.c_void_p), ("bias_dev", ctypes.c_void_p),
+                ("total_tiles", ctypes.c_int64), ("n_bias", ctypes.c_int64), ("nseg", ctypes.c_int32),
+                ("n_slots", ctypes.c_int32), ("n_local", ctypes.c_int32), ("M", ctypes.c_int32),
+                ("alpha", ctypes.c_float), ("wd", ctypes.c_float), ("omb1", ctypes.c_float),
+                ("beta2", ctypes.c_float), ("omb2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("decoupled", ctypes.c_int32), ("zero_grads", ctypes.c_int32)]
+
+
+class AdamwBf16Layout:
+    """Pointer tables of the mixed-precision fused AdamW kernel (csrc/adamw_mix_bf16.hip): row r's fp32
+    master of segment s, its bfloat16 gradient, its fp32 exp_avg and exp_avg_sq and its bfloat16 model
+    row, lengths in elements, and the bias-correction table (adam_bias_table) on the device.  Each
+    pointer argument is a list over the rows of per-segment device addresses."""
+
+    def __init__(self, seg_lens, w_ptrs, g_ptrs, m_ptrs, v_ptrs, p_ptrs, n_local, bias):
+        nseg = len(seg_lens)
+        seg_len = np.asarray(seg_lens, dtype=np.int64)
+        tile_off = np.zeros(nseg + 1, dtype=np.int64)
+        check(lib.mx_adamw_mix_bf16_layout(seg_len.ctypes.data, nseg, n_local, tile_off.ctypes.data),
+              "mx_adamw_mix_bf16_layout")
+
+        def table(rows):
+            t = np.zeros((nseg, n_local), dtype=np.int64)
+            for r, ptrs in enumerate(rows):
+                t[:, r] = ptrs
+            return torch.from_numpy(t).to("cuda")
+
+        self.nseg, self.n_local = nseg, n_local
+        self.tile = int(lib.mx_adamw_mix_bf16_tile(n_local))
+        self.total_tiles = int(tile_off[-1])
+        self.w_ptrs, self.g_ptrs, self.p_ptrs = table(w_ptrs), table(g_ptrs), table(p_ptrs)
+        self.m_ptrs, self.v_ptrs = table(m_ptrs), table(v_ptrs)
+        self.seg_len = torch.from_numpy(seg_len).to("cuda")
+        self.tile_off = torch.from_numpy(tile_off).to("cuda")
+        bias = np.ascontiguousarray(bias, dtype=np.float32)
+        if bias.ndim != 2 or bias.shape[1] != 2 or bias.shape[0] < 1:
+            raise ValueError("bias table: float32 [n_bias, 2]")
+        self.n_bias = int(bias.shape[0])
+        self.bias = torch.from_numpy(bias).to("cuda")
+        self.tune_gen = _TUNE_GEN[0]
+
+    def check_tile(self):
+        if self.tune_gen != _TUNE_GEN[0]:
+            if self.tile != lib.mx_adamw_mix_bf16_tile(self.n_local):
+                raise MXError("layout built for another mixed-precision fused AdamW + mixing tile size")
+            self.tune_gen = _TUNE_GEN[0]
+
+    def call(self, engine, betas, eps, wd, decoupled, zero_grads):
+        """betas are the Python floats: omb1 / omb2 are rounded from the fp64 values 1 - beta."""
+        b1, b2 = float(betas[0]), float(betas[1])
+        return AdamwBf16Call(self.w_ptrs.data_ptr(), self.g_ptrs.data_ptr(), self.m_ptrs.data_ptr(),
+                             self.v_ptrs.data_ptr(), self.p_ptrs.data_ptr(), self.seg_len.data_ptr(),
+                             self.tile_off.data_ptr(), engine._plan_ptr, self.bias.data_ptr(), self.total_tiles,
+                             self.n_bias, self.nseg, engine.n_slots, engine.n_local, engine.M, engine.alpha32,
+                             float(np.float32(wd)), float(np.float32(1.0 - b1)), float(np.float32(b2)),
+                             float(np.float32(1.0 - b2)), float(np.float32(eps)), int(bool(decoupled)),
+                             int(bool(zero_grads)))
+
+
 IDLE_MODES = {"skip": 0, "canonical": 1}
 
 
@@ -1248,12 +1325,13 @@ class VirtualWorkerGroup:
                        (_sgd_mix, lib.mx_sgd_mix_at, "mx_sgd_mix")
 
     def master_from_rows(self):
-        """Redo the masters as the exact widening of `rows` (attach_sgd(master_weights=True) groups).
+        """Redo the masters as the exact widening of `rows` (attach_sgd / attach_adamw(master_weights=True) groups).
         Call it after anything that writes `rows` directly -- sync_rows, loading a checkpoint that
         has no masters: the launch never reads `rows`, so such a write is otherwise overwritten by
         bf16(master) at the next step."""
         if self.master_rows is None:
-            raise MXError("master_from_rows: no master weights (attach_sgd(master_weights=True) on a bfloat16 group)")
+            raise MXError("master_from_rows: no master weights (attach_sgd(master_weights=True) or "
+                          "attach_adamw(master_weights=True) on a bfloat16 group)")
         with torch.no_grad():
             self.master_rows.copy_(self.rows)
 
@@ -1297,7 +1375,8 @@ class VirtualWorkerGroup:
         return time.time() - tic
 
     # ------------------------------------------------------------------ fused AdamW + mixing
-    def attach_adamw(self, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled=True, zero_grads=True):
+    def attach_adamw(self, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled=True, zero_grads=True,
+                     master_weights=False):
         """Give the group torch.optim.AdamW's state (decoupled=False: torch.optim.Adam's, the decay as
         an L2 term in the gradient; no amsgrad, no maximize) so that one launch per iteration applies
         every worker's update and the round's mix (csrc/adamw_mix.hip).
@@ -1307,20 +1386,32 @@ class VirtualWorkerGroup:
         / `exp_avg_sq_rows` (fp32 zeros), and the bias-correction table (adam_bias_table) on the
         device.  `opt_step` counts the optimizer steps taken (adamw_step runs step opt_step + 1);
         `opt_step_dev` (int64 CUDA) is the NEXT step of adamw_device_round, and `lr_dev` its
-        learning rate.  fp32 groups on one GPU only."""
+        learning rate.  One GPU only.
+
+        master_weights=True is the bfloat16 group's form (csrc/adamw_mix_bf16.hip; a ValueError on an
+        fp32 group, and a bfloat16 group refuses to attach without it), as attach_sgd's: `master_arena`
+        / `master_rows` hold an fp32 master of every row, starting as the exact widening of `rows`;
+        the gradient arena is bfloat16 (each adopted parameter's .grad a bf16 view of it), exp_avg
+        and exp_avg_sq stay fp32.  The launch updates and mixes the MASTERS and rewrites `rows` as
+        bf16(master), rounded once to nearest even.  `rows` is write-only to the launch: call
+        master_from_rows() after anything that writes `rows` directly."""
         if self._adamw is not None:
             raise RuntimeError("attach_adamw: already attached")
         if self._sgd is not None:
             raise RuntimeError("attach_adamw: the group already carries SGD state (attach_sgd)")
-        if self.dtype != torch.float32:
-            raise NotImplementedError("attach_adamw: bfloat16 groups need fp32 master weights under AdamW, which "
-                                      "the fused kernel does not have yet; fp32 groups only")
+        if master_weights and self.dtype != torch.bfloat16:
+            raise ValueError("attach_adamw: master_weights=True is for bfloat16 groups; fp32 rows are their own masters")
+        if self.dtype != torch.float32 and not master_weights:
+            raise NotImplementedError("attach_adamw: bfloat16 groups need fp32 master weights under AdamW: pass "
+                                      "master_weights=True (the fp32 fused kernel does not take bfloat16 rows)")
+        mixed = bool(master_weights)
         if self.engine.comm is not None or self.engine.max_remote:
             raise NotImplementedError("attach_adamw: one GPU only (nranks = 1, no transport): the partners' updated "
                                       "rows must exist before any exchange")
         if self._chunk_cols:
             raise NotImplementedError("attach_adamw: not with chunk_cols (the column-pipelined cross-GPU exchange)")
-        if lib.mx_adamw_mix_tile(self.n_local) <= 0 or self.engine.M > 32:
+        tile = lib.mx_adamw_mix_bf16_tile(self.n_local) if mixed else lib.mx_adamw_mix_tile(self.n_local)
+        if tile <= 0 or self.engine.M > 32:
             raise NotImplementedError(f"attach_adamw: {self.n_local} local rows / {self.engine.M} matchings exceed "
                                       "the fused kernel's 64 rows / 32 matchings")
         betas = (float(betas[0]), float(betas[1]))
@@ -1335,12 +1426,21 @@ class VirtualWorkerGroup:
         def row_ptrs(a):
             return [[a[r].data_ptr()] for r in range(self.n_local)]
 
-        self.grad_arena, self.exp_avg_arena, self.exp_avg_sq_arena = arena(), arena(), arena()
+        self.exp_avg_arena, self.exp_avg_sq_arena = arena(), arena()
+        self.grad_arena = torch.zeros((self.n_local, self.ld), dtype=self.dtype, device="cuda")
         self.grads = self.grad_arena[:, :self.numel]
         self.exp_avg_rows = self.exp_avg_arena[:, :self.numel]
         self.exp_avg_sq_rows = self.exp_avg_sq_arena[:, :self.numel]
-        lay = AdamwLayout([self.numel], [[p] for p in self._row_ptrs], row_ptrs(self.grad_arena),
-                          row_ptrs(self.exp_avg_arena), row_ptrs(self.exp_avg_sq_arena), self.n_local, bias)
+        self.master_arena = self.master_rows = None
+        if mixed:
+            self.master_arena = self.arena.to(torch.float32)          # the exact widening, tails (zeros) included
+            self.master_rows = self.master_arena[:, :self.numel]
+            lay = AdamwBf16Layout([self.numel], row_ptrs(self.master_arena), row_ptrs(self.grad_arena),
+                                  row_ptrs(self.exp_avg_arena), row_ptrs(self.exp_avg_sq_arena),
+                                  [[p] for p in self._row_ptrs], self.n_local, bias)
+        else:
+            lay = AdamwLayout([self.numel], [[p] for p in self._row_ptrs], row_ptrs(self.grad_arena),
+                              row_ptrs(self.exp_avg_arena), row_ptrs(self.exp_avg_sq_arena), self.n_local, bias)
         call = lay.call(self.engine, betas, eps, weight_decay, decoupled, zero_grads)
         if self._adopted is not None:
             for r, m in enumerate(self._adopted):
@@ -1355,6 +1455,8 @@ class VirtualWorkerGroup:
         self.adamw_hyper = {"betas": betas, "eps": eps, "weight_decay": weight_decay, "decoupled": bool(decoupled),
                             "zero_grads": bool(zero_grads)}
         self._adamw = (lay, call, ctypes.addressof(call))
+        self._adamw_fn = (_adamw_mix_bf16, lib.mx_adamw_mix_bf16_at, "mx_adamw_mix_bf16") if mixed else \
+                         (_adamw_mix, lib.mx_adamw_mix_at, "mx_adamw_mix")
 
     def _adamw_state(self):
         if self._adamw is None:
@@ -1368,9 +1470,9 @@ class VirtualWorkerGroup:
         all-zero round is the optimizer step alone -- and returns whether the round mixed."""
         call = self._adamw_state()
         it = self.engine.round_index(it)
-        rc = _adamw_mix(call, it, self.opt_step + 1, lr, None, stream_ptr(stream))
+        rc = self._adamw_fn[0](call, it, self.opt_step + 1, lr, None, stream_ptr(stream))
         if rc:
-            check(rc, "mx_adamw_mix")
+            check(rc, self._adamw_fn[2])
         self.opt_step += 1
         return bool(self.engine.any_active[it])
 
@@ -1383,8 +1485,8 @@ class VirtualWorkerGroup:
         touched."""
         call = self._adamw_state()
         s = stream_ptr(stream)
-        check(lib.mx_adamw_mix_at(call, self.iter_dev.data_ptr(), self.engine.T, self.opt_step_dev.data_ptr(), 0.0,
-                                  self.lr_dev.data_ptr(), s), "mx_adamw_mix_at")
+        check(self._adamw_fn[1](call, self.iter_dev.data_ptr(), self.engine.T, self.opt_step_dev.data_ptr(), 0.0,
+                                self.lr_dev.data_ptr(), s), self._adamw_fn[2] + "_at")
         check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, s), "mx_iter_advance")
         check(lib.mx_iter_advance(self.opt_step_dev.data_ptr(), 1, s), "mx_iter_advance")
 
@@ -1426,7 +1528,8 @@ class VirtualWorkerGroup:
             raise ValueError("checkpoint carries momentum rows: attach_sgd(momentum=...) before loading it")
         master = state.get("master_rows")
         if master is not None and (self.master_rows is None or tuple(master.shape) != tuple(self.master_rows.shape)):
-            raise ValueError("checkpoint carries master rows: attach_sgd(master_weights=True) before loading it")
+            raise ValueError("checkpoint carries master rows: attach_sgd(master_weights=True) before loading it "
+                             "(or attach_adamw(master_weights=True))")
         adam = [state.get(k) for k in ("exp_avg_rows", "exp_avg_sq_rows")]
         if any(a is not None for a in adam) or state.get("opt_step") is not None:
             if self._adamw is None or any(a is None or tuple(a.shape) != tuple(self.rows.shape) for a in adam):

@@ -207,9 +207,10 @@ class VirtualTrainer:
         are updated and mixed, the bfloat16 models are their rounded image, and checkpoints save
         the masters too.
 
-        fused_adamw=True (same conditions, fp32 models, not together with fused_sgd): the same with
-        AdamW's update in the launch (VirtualWorkerGroup.attach_adamw / adamw_communicate,
-        csrc/adamw_mix.hip): betas (0.9, 0.999), eps 1e-8 and the harness's weight decay 5e-4 as the
+        fused_adamw=True (same conditions, not together with fused_sgd): the same with AdamW's update
+        in the launch (VirtualWorkerGroup.attach_adamw / adamw_communicate, csrc/adamw_mix.hip;
+        all-bfloat16 models in mixed precision, attach_adamw(master_weights=True),
+        csrc/adamw_mix_bf16.hip): betas (0.9, 0.999), eps 1e-8 and the harness's weight decay 5e-4 as the
         decoupled decay, or what adamw_hyper (attach_adamw's keyword arguments) overrides; checkpoints
         save exp_avg / exp_avg_sq rows and the step count.
 
@@ -246,16 +247,15 @@ class VirtualTrainer:
             dts = {p.dtype for m in self.models for p in m.parameters()}
             self.group = VirtualWorkerGroup(self.GP, self.models,
                                             dtype=torch.bfloat16 if dts == {torch.bfloat16} else torch.float32)
-        mixed = self.fused_sgd and self.group.dtype == torch.bfloat16
+        mixed = (self.fused_sgd or self.fused_adamw) and self.group.dtype == torch.bfloat16
         if self.fused_sgd:
             # all-bfloat16 models: fp32 master weights, updated and mixed by the launch (csrc/sgd_mix_bf16.hip)
             self.group.attach_sgd(args.momentum, 5e-4, args.nesterov, master_weights=mixed)
         if self.fused_adamw:
-            if self.group.dtype != torch.float32:
-                raise ValueError("fused_adamw needs fp32 models: mixed-precision AdamW is not fused yet")
+            # all-bfloat16 models: fp32 master weights, as above (csrc/adamw_mix_bf16.hip)
             hyper = {"betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 5e-4, "decoupled": True}
             hyper.update(adamw_hyper or {})
-            self.group.attach_adamw(**hyper)
+            self.group.attach_adamw(**hyper, master_weights=mixed)
         sync_rows(self.group.rows)
         if mixed:
             self.group.master_from_rows()                        # the masters of the synchronized rows

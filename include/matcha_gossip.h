@@ -429,6 +429,73 @@ int mx_adamw_mix(const mx_adamw_mix_call* call, int64_t iter, int64_t step, floa
 int mx_adamw_mix_at(const mx_adamw_mix_call* call, const int64_t* iter_dev, int64_t n_iters,
                     const int64_t* step_dev, float lr, const float* lr_dev, void* stream);
 
+/* ---------------------------------------------------------------- the hot path, mixed-precision AdamW / Adam fused in
+ * mx_adamw_mix for models held in bfloat16 (csrc/adamw_mix_bf16.hip): the optimizer works on fp32 MASTER
+ * rows with fp32 exp_avg / exp_avg_sq, the master rows are what the round mixes, and the bfloat16 model
+ * row is the rounded image of its master, rewritten by every launch.  Per (segment, row) five arrays,
+ * every length in elements:
+ *   w  float*    fp32 master, read and written in place
+ *   g  uint16_t* bfloat16 gradient, read; overwritten with zeros when zero_grads != 0
+ *   m  float*    fp32 exp_avg, read and written
+ *   v  float*    fp32 exp_avg_sq, read and written
+ *   p  uint16_t* bfloat16 model row, WRITE ONLY: the kernel never reads it
+ * Arithmetic contract, per row and column, every line ONE IEEE fp32 rounding (explicit fmas, correctly
+ * rounded square root and division, denormals kept):
+ *   g32 = f32(g)                                             exact widening, bits << 16
+ *   decay = fmaf(-lr, wd, 1.0f)                              once per launch
+ *   w1 = (wd != 0 &&  decoupled) ? fmul(w, decay) : w
+ *   g1 = (wd != 0 && !decoupled) ? fmaf(wd, w, g32) : g32
+ *   m' = fmaf(omb1, fsub(g1, m), m)
+ *   v' = fmaf(omb2, fmul(g1, g1), fmul(beta2, v))
+ *   den = fadd(fdiv(fsqrt(v'), bc2s), eps)
+ *   ss  = fdiv(lr, bc1)                                      once per launch
+ *   w'  = fmaf(-ss, fdiv(m', den), w1)
+ *   w   = mx_sgd_mix's round on the w' values (same plan record, alpha, selfweight, ascending
+ *         matchings, self term last; a row the record leaves alone, and every row of an all-zero
+ *         round, keeps w' as it is)
+ *   p   = bf16_rne(w)                                        one rounding, to nearest even, of the value
+ *                                                            stored to w; NaN stays NaN, payload unspecified
+ * (bc1, bc2s) are mx_adamw_mix's: bias_dev[min(t, n_bias) - 1]; nothing computes pow on the device.
+ * p is written for every row in every launch that runs, rows the round leaves alone included (their w
+ * changed by the optimizer step).  Nothing is written at or past seg_len of a row in any of the five.
+ * Traffic: 28 bytes per element (30 with zero_grads) against 100 for g.float(), the torch op sequence,
+ * the fp32 round and the cast back.
+ * Alignment rule: a lane holds 4 elements; where w, m and v of a (segment, row) are 16-byte aligned, g
+ * and p are 8-byte aligned and the 4 elements are in range, the accesses are 16 bytes on w / m / v and
+ * 8 bytes on g / p; elsewhere they are per element (4 / 2 bytes), zero-filled past the end.
+ * mx_adamw_mix_bf16_call is mx_adamw_mix_call with the five tables above; the other fields, the tile
+ * (mx_adamw_mix_bf16_tile: 1024 / 1024 / 512 / 256 columns, 0 above 64 rows), the layout prefix, the
+ * host-side refusals (MX_ERR_INVALID, nothing launched: n_slots != n_local, more than 64 rows, M outside
+ * [1, 32], n_bias < 1, step < 1, a null table -- p included) and the launch-side no-ops (a peer-reads
+ * plan record; for _at an iteration counter outside [0, n_iters) or a step counter below 1: none of the
+ * five arrays is written) are mx_adamw_mix's.
+ * mx_adamw_mix_bf16_set / _get: "nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid", as
+ * mx_adamw_mix_set's and independent of them.  Speed only, never bits; none of them changes the tile. */
+typedef struct mx_adamw_mix_bf16_call {
+    float* const* w_ptrs_dev;
+    uint16_t* const* g_ptrs_dev;
+    float* const* m_ptrs_dev;
+    float* const* v_ptrs_dev;
+    uint16_t* const* p_ptrs_dev;
+    const int64_t* seg_len_dev;
+    const int64_t* tile_off_dev;
+    const int32_t* plan_dev;
+    const float* bias_dev;
+    int64_t total_tiles;
+    int64_t n_bias;
+    int32_t nseg, n_slots, n_local, M;
+    float alpha, wd, omb1, beta2, omb2, eps;
+    int32_t decoupled, zero_grads;
+} mx_adamw_mix_bf16_call;
+int mx_adamw_mix_bf16_tile(int n_slots);
+int mx_adamw_mix_bf16_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host);
+int mx_adamw_mix_bf16_set(const char* key, int value);
+int mx_adamw_mix_bf16_get(const char* key);
+int mx_adamw_mix_bf16(const mx_adamw_mix_bf16_call* call, int64_t iter, int64_t step, float lr, const float* lr_dev,
+                      void* stream);
+int mx_adamw_mix_bf16_at(const mx_adamw_mix_bf16_call* call, const int64_t* iter_dev, int64_t n_iters,
+                         const int64_t* step_dev, float lr, const float* lr_dev, void* stream);
+
 /* ---------------------------------------------------------------- flatten / unflatten
  * mx_gather replaces flatten_tensors (comm_helpers.py:12-30): flat[off[s] + i] = src[s][i].
  * mx_scatter is the copy_ loop of reset_model over unflatten_tensors views

@@ -5,6 +5,7 @@
     python tools/train_gpu.py --momentum 0.9 --fused-sgd                        # SGD step fused into the round
     python tools/train_gpu.py --momentum 0.9 --fused-sgd --bf16                 # the same, bf16 models + fp32 masters
     python tools/train_gpu.py --lr 1e-3 --no-warmup --fused-adamw --wd 1e-2       # AdamW step fused into the round
+    python tools/train_gpu.py --lr 1e-3 --no-warmup --fused-adamw --wd 1e-2 --bf16 # the same, bf16 models + fp32 masters
     torchrun --nproc-per-node N --master-addr 127.0.0.1 tools/train_gpu.py     # one worker per GPU
 
 Flags follow train_mpi.py:205-231 (same names and defaults where they apply); --workers,
@@ -50,13 +51,13 @@ def main():
     ap.add_argument("--fused-sgd", action="store_true", help="one GPU, per-worker (non-batched) training: the "
                     "workers' optimizer.step() / zero_grad() and the gossip round as ONE launch per iteration")
     ap.add_argument("--fused-adamw", action="store_true", help="as --fused-sgd with AdamW's update in the launch "
-                    "(fp32 models; --beta1 --beta2 --eps --wd; --lr is AdamW's, e.g. 1e-3)")
+                    "(--beta1 --beta2 --eps --wd; --lr is AdamW's, e.g. 1e-3)")
     ap.add_argument("--beta1", default=0.9, type=float)
     ap.add_argument("--beta2", default=0.999, type=float)
     ap.add_argument("--eps", default=1e-8, type=float)
     ap.add_argument("--wd", default=5e-4, type=float, help="--fused-adamw: the decoupled weight decay")
     ap.add_argument("--bf16", action="store_true", help="one GPU: the models are cast to bfloat16 (bfloat16 gossip "
-                    "rows); with --fused-sgd the step runs in mixed precision on fp32 master weights, which the "
+                    "rows); with --fused-sgd / --fused-adamw the step runs in mixed precision on fp32 master weights, which the "
                     "round mixes, and the bfloat16 models are their rounded image")
     ap.add_argument("--pull", action="store_true", help="one process per GPU: gossip rounds over the pull "
                     "transport (partner rows / Choco messages read from the peers' HBM) instead of RCCL")
