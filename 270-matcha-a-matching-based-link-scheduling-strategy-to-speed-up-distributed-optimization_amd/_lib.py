@@ -63,6 +63,19 @@ SIGNATURES = {
     "mx_adamw_mix_bf16_get": (c_int, [ctypes.c_char_p]),
     "mx_adamw_mix_bf16": (c_int, [c_p, c_i64, c_i64, c_f32, c_p, c_p]),
     "mx_adamw_mix_bf16_at": (c_int, [c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
+    "mx_grad_norm_cols": (c_int, []),
+    "mx_grad_norm_layout": (c_i64, [c_p, c_int, c_int, c_p]),
+    "mx_grad_norm_set": (c_int, [ctypes.c_char_p, c_int]),
+    "mx_grad_norm_get": (c_int, [ctypes.c_char_p]),
+    "mx_grad_norm": (c_int, [c_p, c_p]),
+    "mx_sgd_mix_scaled": (c_int, [c_p, c_p, c_i64, c_f32, c_p, c_p]),
+    "mx_sgd_mix_scaled_at": (c_int, [c_p, c_p, c_p, c_i64, c_f32, c_p, c_p]),
+    "mx_sgd_mix_bf16_scaled": (c_int, [c_p, c_p, c_i64, c_f32, c_p, c_p]),
+    "mx_sgd_mix_bf16_scaled_at": (c_int, [c_p, c_p, c_p, c_i64, c_f32, c_p, c_p]),
+    "mx_adamw_mix_scaled": (c_int, [c_p, c_p, c_i64, c_i64, c_f32, c_p, c_p]),
+    "mx_adamw_mix_scaled_at": (c_int, [c_p, c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
+    "mx_adamw_mix_bf16_scaled": (c_int, [c_p, c_p, c_i64, c_i64, c_f32, c_p, c_p]),
+    "mx_adamw_mix_bf16_scaled_at": (c_int, [c_p, c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
     "mx_gather": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p]),
     "mx_scatter": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p]),
     "mx_topk_work_bytes": (ctypes.c_size_t, [c_i64]),

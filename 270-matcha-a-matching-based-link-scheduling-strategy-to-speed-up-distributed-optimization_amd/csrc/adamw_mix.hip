@@ -97,9 +97,18 @@ __device__ __forceinline__ void fma4(F4& a, float w, const F4& x) {
     for (int t = 0; t < 4; ++t) a[t] = __builtin_fmaf(w, x[t], a[t]);
 }
 
+// the clip factor of the row (mx_*_scaled): g' = fmul(gscale[r], g), before anything else in the update
+__device__ __forceinline__ F4 scale4(const F4& g, float s) {
+    F4 v;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) v[t] = s * g[t];
+    return v;
+}
+
 struct Hyper {
     float lr, wd, omb1, beta2, omb2, eps;
     const float* lr_dev;       // non-NULL: the learning rate, read when the kernel runs
+    const float* gscale;       // non-NULL: float [n_local], row r's gradient is multiplied by gscale[r] (wave-uniform: a scalar load)
     const float* bias;         // float [n_bias][2]: (bc1, bc2s) of step t at entry min(t, n_bias) - 1
     int64_t n_bias;
     int64_t step;              // the optimizer step t >= 1; with step_dev, *step_dev when the kernel runs
@@ -274,7 +283,8 @@ __global__ __launch_bounds__(kTPB) void adamw_mix_rows(float* const* __restrict_
             if (k < n_local) {
                 const int64_t c = gq.col0 + (int64_t)(at % C4 + lane) * 4;
                 const bool vec = vec_of(gq, k);
-                lds[at + lane] = adam4(X[t], G[t], Mv[t], Vv[t], st, h);
+                const F4 g = h.gscale ? scale4(G[t], h.gscale[k]) : G[t];
+                lds[at + lane] = adam4(X[t], g, Mv[t], Vv[t], st, h);
                 store_chunk<NT>(m_ptrs[gq.base + k], c, gq.lim, vec, Mv[t]);
                 store_chunk<NT>(v_ptrs[gq.base + k], c, gq.lim, vec, Vv[t]);
                 if (h.zero_grads) store_chunk<NT>(g_ptrs[gq.base + k], c, gq.lim, vec, F4{0.0f, 0.0f, 0.0f, 0.0f});
@@ -411,7 +421,7 @@ int launch(const Args& a) {
     return MX_OK;
 }
 
-int adamw_mix(const mx_adamw_mix_call* c, int64_t iter, const int64_t* iter_dev, int64_t step,
+int adamw_mix(const mx_adamw_mix_call* c, const float* gscale, int64_t iter, const int64_t* iter_dev, int64_t step,
               const int64_t* step_dev, float lr, const float* lr_dev, void* stream, const char* who) {
     MX_CHECK(c, "%s: null call record", who);
     MX_CHECK(c->x_ptrs_dev && c->g_ptrs_dev && c->m_ptrs_dev && c->v_ptrs_dev && c->seg_len_dev && c->tile_off_dev &&
@@ -432,7 +442,7 @@ int adamw_mix(const mx_adamw_mix_call* c, int64_t iter, const int64_t* iter_dev,
     const bool nt = g_tune.nontemporal == 2 ? (ws <= ((int64_t)32 << 20) || ws > ((int64_t)320 << 20))
                                             : g_tune.nontemporal != 0;
     const Args a{c, iter, iter_dev,
-                 Hyper{lr, c->wd, c->omb1, c->beta2, c->omb2, c->eps, lr_dev, c->bias_dev, c->n_bias, step, step_dev,
+                 Hyper{lr, c->wd, c->omb1, c->beta2, c->omb2, c->eps, lr_dev, gscale, c->bias_dev, c->n_bias, step, step_dev,
                        c->decoupled != 0, c->zero_grads != 0},
                  mx::as_stream(stream)};
 #define MX_ADAMW(N, TW) (nt ? launch<N, TW, true>(a) : launch<N, TW, false>(a))
@@ -495,11 +505,23 @@ extern "C" int mx_adamw_mix_get(const char* key) {
 
 extern "C" int mx_adamw_mix(const mx_adamw_mix_call* c, int64_t iter, int64_t step, float lr, const float* lr_dev,
                             void* stream) {
-    return adamw_mix(c, iter, nullptr, step, nullptr, lr, lr_dev, stream, "mx_adamw_mix");
+    return adamw_mix(c, nullptr, iter, nullptr, step, nullptr, lr, lr_dev, stream, "mx_adamw_mix");
+}
+
+extern "C" int mx_adamw_mix_scaled(const mx_adamw_mix_call* c, const float* gscale_dev, int64_t iter, int64_t step,
+                                   float lr, const float* lr_dev, void* stream) {
+    return adamw_mix(c, gscale_dev, iter, nullptr, step, nullptr, lr, lr_dev, stream, "mx_adamw_mix_scaled");
 }
 
 extern "C" int mx_adamw_mix_at(const mx_adamw_mix_call* c, const int64_t* iter_dev, int64_t n_iters,
                                const int64_t* step_dev, float lr, const float* lr_dev, void* stream) {
     MX_CHECK(iter_dev && step_dev, "mx_adamw_mix_at: null iteration or step counter");
-    return adamw_mix(c, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream, "mx_adamw_mix_at");
+    return adamw_mix(c, nullptr, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream, "mx_adamw_mix_at");
+}
+
+extern "C" int mx_adamw_mix_scaled_at(const mx_adamw_mix_call* c, const float* gscale_dev, const int64_t* iter_dev,
+                                      int64_t n_iters, const int64_t* step_dev, float lr, const float* lr_dev,
+                                      void* stream) {
+    MX_CHECK(iter_dev && step_dev, "mx_adamw_mix_scaled_at: null iteration or step counter");
+    return adamw_mix(c, gscale_dev, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream, "mx_adamw_mix_scaled_at");
 }

@@ -176,9 +176,18 @@ __device__ __forceinline__ void fma4(F4& a, float w, const F4& x) {
     for (int t = 0; t < 4; ++t) a[t] = __builtin_fmaf(w, x[t], a[t]);
 }
 
+// the clip factor of the row (mx_*_scaled): g' = fmul(gscale[r], f32(g)), before anything else in the update
+__device__ __forceinline__ F4 scale4(const F4& g, float s) {
+    F4 v;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) v[t] = s * g[t];
+    return v;
+}
+
 struct Hyper {
     float lr, wd, omb1, beta2, omb2, eps;
     const float* lr_dev;       // non-NULL: the learning rate, read when the kernel runs
+    const float* gscale;       // non-NULL: float [n_local], row r's gradient is multiplied by gscale[r] (wave-uniform: a scalar load)
     const float* bias;         // float [n_bias][2]: (bc1, bc2s) of step t at entry min(t, n_bias) - 1
     int64_t n_bias;
     int64_t step;              // the optimizer step t >= 1; with step_dev, *step_dev when the kernel runs
@@ -355,7 +364,8 @@ __global__ __launch_bounds__(kTPB) void adamw_mix_bf16_rows(float* const* __rest
             if (k < n_local) {
                 const int64_t c = gq.col0 + (int64_t)(at % C4 + lane) * 4;
                 const bool vec = vec_of(gq, k);
-                lds[at + lane] = adam4(X[t], widen4(G[t]), Mv[t], Vv[t], st, h);
+                const F4 g = h.gscale ? scale4(widen4(G[t]), h.gscale[k]) : widen4(G[t]);
+                lds[at + lane] = adam4(X[t], g, Mv[t], Vv[t], st, h);
                 store_f32<NT>(m_ptrs[gq.base + k], c, gq.lim, vec, Mv[t]);
                 store_f32<NT>(v_ptrs[gq.base + k], c, gq.lim, vec, Vv[t]);
                 if (h.zero_grads) store_b16<NT>(g_ptrs[gq.base + k], c, gq.lim, vec, U2{0u, 0u});
@@ -497,8 +507,9 @@ int launch(const Args& a) {
     return MX_OK;
 }
 
-int adamw_mix_bf16(const mx_adamw_mix_bf16_call* c, int64_t iter, const int64_t* iter_dev, int64_t step,
-                   const int64_t* step_dev, float lr, const float* lr_dev, void* stream, const char* who) {
+int adamw_mix_bf16(const mx_adamw_mix_bf16_call* c, const float* gscale, int64_t iter, const int64_t* iter_dev,
+                   int64_t step, const int64_t* step_dev, float lr, const float* lr_dev, void* stream,
+                   const char* who) {
     MX_CHECK(c, "%s: null call record", who);
     MX_CHECK(c->w_ptrs_dev && c->g_ptrs_dev && c->m_ptrs_dev && c->v_ptrs_dev && c->p_ptrs_dev && c->seg_len_dev &&
                  c->tile_off_dev && c->plan_dev && c->bias_dev,
@@ -518,7 +529,7 @@ int adamw_mix_bf16(const mx_adamw_mix_bf16_call* c, int64_t iter, const int64_t*
     const bool nt = g_tune.nontemporal == 2 ? (ws <= ((int64_t)32 << 20) || ws > ((int64_t)320 << 20))
                                             : g_tune.nontemporal != 0;
     const Args a{c, iter, iter_dev,
-                 Hyper{lr, c->wd, c->omb1, c->beta2, c->omb2, c->eps, lr_dev, c->bias_dev, c->n_bias, step, step_dev,
+                 Hyper{lr, c->wd, c->omb1, c->beta2, c->omb2, c->eps, lr_dev, gscale, c->bias_dev, c->n_bias, step, step_dev,
                        c->decoupled != 0, c->zero_grads != 0},
                  mx::as_stream(stream)};
 #define MX_ADAMW(N, TW) (nt ? launch<N, TW, true>(a) : launch<N, TW, false>(a))
@@ -581,11 +592,24 @@ extern "C" int mx_adamw_mix_bf16_get(const char* key) {
 
 extern "C" int mx_adamw_mix_bf16(const mx_adamw_mix_bf16_call* c, int64_t iter, int64_t step, float lr,
                                  const float* lr_dev, void* stream) {
-    return adamw_mix_bf16(c, iter, nullptr, step, nullptr, lr, lr_dev, stream, "mx_adamw_mix_bf16");
+    return adamw_mix_bf16(c, nullptr, iter, nullptr, step, nullptr, lr, lr_dev, stream, "mx_adamw_mix_bf16");
+}
+
+extern "C" int mx_adamw_mix_bf16_scaled(const mx_adamw_mix_bf16_call* c, const float* gscale_dev, int64_t iter,
+                                        int64_t step, float lr, const float* lr_dev, void* stream) {
+    return adamw_mix_bf16(c, gscale_dev, iter, nullptr, step, nullptr, lr, lr_dev, stream, "mx_adamw_mix_bf16_scaled");
 }
 
 extern "C" int mx_adamw_mix_bf16_at(const mx_adamw_mix_bf16_call* c, const int64_t* iter_dev, int64_t n_iters,
                                     const int64_t* step_dev, float lr, const float* lr_dev, void* stream) {
     MX_CHECK(iter_dev && step_dev, "mx_adamw_mix_bf16_at: null iteration or step counter");
-    return adamw_mix_bf16(c, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream, "mx_adamw_mix_bf16_at");
+    return adamw_mix_bf16(c, nullptr, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream, "mx_adamw_mix_bf16_at");
+}
+
+extern "C" int mx_adamw_mix_bf16_scaled_at(const mx_adamw_mix_bf16_call* c, const float* gscale_dev,
+                                           const int64_t* iter_dev, int64_t n_iters, const int64_t* step_dev,
+                                           float lr, const float* lr_dev, void* stream) {
+    MX_CHECK(iter_dev && step_dev, "mx_adamw_mix_bf16_scaled_at: null iteration or step counter");
+    return adamw_mix_bf16(c, gscale_dev, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream,
+                          "mx_adamw_mix_bf16_scaled_at");
 }

@@ -161,9 +161,18 @@ __device__ __forceinline__ void fma4(F4& a, float w, const F4& x) {
     for (int t = 0; t < 4; ++t) a[t] = __builtin_fmaf(w, x[t], a[t]);
 }
 
+// the clip factor of the row (mx_*_scaled): g' = fmul(gscale[r], f32(g)), before anything else in the update
+__device__ __forceinline__ F4 scale4(const F4& g, float s) {
+    F4 v;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) v[t] = s * g[t];
+    return v;
+}
+
 struct Hyper {
     float lr, wd, mom;
     const float* lr_dev;   // non-NULL: the learning rate, read when the kernel runs
+    const float* gscale;   // non-NULL: float [n_local], row r's gradient is multiplied by gscale[r] (wave-uniform: a scalar load)
     int nesterov, zero_grads;
 };
 
@@ -316,7 +325,8 @@ __global__ __launch_bounds__(kTPB) void sgd_mix_bf16_rows(float* const* __restri
             if (k < n_local) {
                 const int64_t c = gq.col0 + (int64_t)(at % C4 + lane) * 4;
                 const bool vec = vec_of(gq, k);
-                lds[at + lane] = sgd4<MOM>(X[t], widen4(G[t]), Mv[t], nlr, h);
+                const F4 g = h.gscale ? scale4(widen4(G[t]), h.gscale[k]) : widen4(G[t]);
+                lds[at + lane] = sgd4<MOM>(X[t], g, Mv[t], nlr, h);
                 if constexpr (MOM) store_f32<NT>(m_ptrs[gq.base + k], c, gq.lim, vec, Mv[t]);
                 if (h.zero_grads) store_b16<NT>(g_ptrs[gq.base + k], c, gq.lim, vec, U2{0u, 0u});
             }
@@ -457,8 +467,8 @@ int launch(const Args& a) {
     return MX_OK;
 }
 
-int sgd_mix_bf16(const mx_sgd_mix_bf16_call* c, int64_t iter, const int64_t* iter_dev, float lr, const float* lr_dev,
-                 void* stream, const char* who) {
+int sgd_mix_bf16(const mx_sgd_mix_bf16_call* c, const float* gscale, int64_t iter, const int64_t* iter_dev, float lr,
+                 const float* lr_dev, void* stream, const char* who) {
     MX_CHECK(c, "%s: null call record", who);
     MX_CHECK(c->w_ptrs_dev && c->g_ptrs_dev && c->p_ptrs_dev && c->seg_len_dev && c->tile_off_dev && c->plan_dev,
              "%s: null pointer", who);
@@ -478,7 +488,7 @@ int sgd_mix_bf16(const mx_sgd_mix_bf16_call* c, int64_t iter, const int64_t* ite
     const int64_t ws = c->total_tiles * (int64_t)cl.tile * c->n_local * (12 + (mom ? 8 : 0) + (c->zero_grads ? 2 : 0));
     const bool nt = g_tune.nontemporal == 2 ? (ws <= ((int64_t)32 << 20) || ws > ((int64_t)320 << 20))
                                             : g_tune.nontemporal != 0;
-    const Args a{c, iter, iter_dev, Hyper{lr, c->wd, c->mom, lr_dev, c->nesterov != 0, c->zero_grads != 0},
+    const Args a{c, iter, iter_dev, Hyper{lr, c->wd, c->mom, lr_dev, gscale, c->nesterov != 0, c->zero_grads != 0},
                  mx::as_stream(stream)};
 #define MX_SGD(N, TW)                                                                              \
     (nt ? (mom ? launch<N, TW, true, true>(a) : launch<N, TW, true, false>(a))                     \
@@ -542,11 +552,23 @@ extern "C" int mx_sgd_mix_bf16_get(const char* key) {
 
 extern "C" int mx_sgd_mix_bf16(const mx_sgd_mix_bf16_call* c, int64_t iter, float lr, const float* lr_dev,
                                void* stream) {
-    return sgd_mix_bf16(c, iter, nullptr, lr, lr_dev, stream, "mx_sgd_mix_bf16");
+    return sgd_mix_bf16(c, nullptr, iter, nullptr, lr, lr_dev, stream, "mx_sgd_mix_bf16");
+}
+
+extern "C" int mx_sgd_mix_bf16_scaled(const mx_sgd_mix_bf16_call* c, const float* gscale_dev, int64_t iter, float lr,
+                                      const float* lr_dev, void* stream) {
+    return sgd_mix_bf16(c, gscale_dev, iter, nullptr, lr, lr_dev, stream, "mx_sgd_mix_bf16_scaled");
 }
 
 extern "C" int mx_sgd_mix_bf16_at(const mx_sgd_mix_bf16_call* c, const int64_t* iter_dev, int64_t n_iters, float lr,
                                   const float* lr_dev, void* stream) {
     MX_CHECK(iter_dev, "mx_sgd_mix_bf16_at: null iteration counter");
-    return sgd_mix_bf16(c, n_iters, iter_dev, lr, lr_dev, stream, "mx_sgd_mix_bf16_at");
+    return sgd_mix_bf16(c, nullptr, n_iters, iter_dev, lr, lr_dev, stream, "mx_sgd_mix_bf16_at");
+}
+
+extern "C" int mx_sgd_mix_bf16_scaled_at(const mx_sgd_mix_bf16_call* c, const float* gscale_dev,
+                                         const int64_t* iter_dev, int64_t n_iters, float lr, const float* lr_dev,
+                                         void* stream) {
+    MX_CHECK(iter_dev, "mx_sgd_mix_bf16_scaled_at: null iteration counter");
+    return sgd_mix_bf16(c, gscale_dev, n_iters, iter_dev, lr, lr_dev, stream, "mx_sgd_mix_bf16_scaled_at");
 }

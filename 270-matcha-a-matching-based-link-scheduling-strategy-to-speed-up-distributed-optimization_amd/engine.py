@@ -118,6 +118,34 @@ def set_adamw_mix_bf16_tuning(**knobs):
         check(lib.mx_adamw_mix_bf16_set(k.encode(), int(v)), "mx_adamw_mix_bf16_set")
 
 
+GRAD_NORM_TUNE_KEYS = ("blocks_per_cu", "grid")
+
+
+def grad_norm_tuning():
+    """Current knobs of the gradient-norm kernel (mx_grad_norm_set)."""
+    return {k: int(lib.mx_grad_norm_get(k.encode())) for k in GRAD_NORM_TUNE_KEYS}
+
+
+def set_grad_norm_tuning(**knobs):
+    for k, v in knobs.items():
+        check(lib.mx_grad_norm_set(k.encode(), int(v)), "mx_grad_norm_set")
+
+
+def clip_value(clip_grad_norm, who):
+    """The clip_grad_norm keyword of attach_sgd / attach_adamw: None (off) or a positive finite float."""
+    if clip_grad_norm is None:
+        return None
+    try:
+        v = float(clip_grad_norm)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: clip_grad_norm must be None or a positive finite number") from None
+    with np.errstate(over="ignore", under="ignore"):
+        v32 = float(np.float32(v)) if math.isfinite(v) else v      # the kernel takes the fp32 rounding
+    if not (math.isfinite(v32) and v32 > 0.0):
+        raise ValueError(f"{who}: clip_grad_norm must be None or a positive finite number, not {clip_grad_norm!r}")
+    return v
+
+
 ADAM_BIAS_MAX = 1 << 21     # entries (16 MB): reached at beta2 ~ 0.99999
 
 
@@ -759,6 +787,44 @@ class AdamwBf16Layout:
                              int(bool(zero_grads)))
 
 
+class GradNormCall(ctypes.Structure):
+    """mx_grad_norm_call (include/matcha_gossip.h): the gradient-norm launches' arguments, packed once."""
+    _fields_ = [("g_ptrs_dev", ctypes.c_void_p), ("seg_len_dev", ctypes.c_void_p), ("work_dev", ctypes.c_void_p),
+                ("norm_dev", ctypes.c_void_p), ("scale_dev", ctypes.c_void_p), ("chunks", ctypes.c_int64),
+                ("nseg", ctypes.c_int32), ("n_local", ctypes.c_int32), ("elem_size", ctypes.c_int32),
+                ("max_norm", ctypes.c_float)]
+
+
+class GradNorm:
+    """Per-worker gradient 2-norms and clip factors on the device (csrc/grad_norm.hip; torch's
+    clip_grad_norm_ per row): `norms` and `scales` (fp32 CUDA [n_local]) and the fp64 workspace, over
+    the gradient table of a fused layout (SgdLayout / AdamwLayout / their bf16 forms: `layout.g_ptrs`,
+    `layout.seg_len`).  elem_size 4 = fp32 gradients, 2 = bfloat16."""
+
+    def __init__(self, seg_lens, layout, elem_size, max_norm):
+        seg_len = np.asarray(seg_lens, dtype=np.int64)
+        chunks = ctypes.c_int64(0)
+        nbytes = int(lib.mx_grad_norm_layout(seg_len.ctypes.data, len(seg_len), layout.n_local, ctypes.byref(chunks)))
+        if nbytes < 0:
+            check(nbytes, "mx_grad_norm_layout")
+        self.layout = layout                                   # keeps the tables alive
+        self.max_norm = float(np.float32(max_norm))
+        self.work = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device="cuda")
+        self.norms = torch.zeros(layout.n_local, dtype=torch.float32, device="cuda")
+        self.scales = torch.ones(layout.n_local, dtype=torch.float32, device="cuda")
+        self.call = GradNormCall(layout.g_ptrs.data_ptr(), layout.seg_len.data_ptr(), self.work.data_ptr(),
+                                 self.norms.data_ptr(), self.scales.data_ptr(), chunks.value, len(seg_len),
+                                 layout.n_local, int(elem_size), self.max_norm)
+        self._addr = ctypes.addressof(self.call)
+        self.scale_ptr = self.scales.data_ptr()
+
+    def enqueue(self, s):
+        """The two norm launches on raw stream `s`: no host synchronisation, graph-capturable."""
+        rc = lib.mx_grad_norm(self._addr, s)
+        if rc:
+            check(rc, "mx_grad_norm")
+
+
 IDLE_MODES = {"skip": 0, "canonical": 1}
 
 
@@ -1047,6 +1113,9 @@ class VirtualWorkerGroup:
         self._sgd = None                     # attach_sgd: the fused SGD + mixing launch's state
         self.master_arena = self.master_rows = None   # attach_sgd(master_weights=True): fp32 masters of bf16 rows
         self._adamw = None                   # attach_adamw: the fused AdamW + mixing launch's state
+        self._clip = None                    # attach_*(clip_grad_norm=...): the norm launch's state (GradNorm)
+        self.clip_grad_norm = None
+        self.grad_norms = self.grad_scales = None
         self._round_ctrs = {}                # device_rounds(K): per-round counters, one tensor per K
         if models is not None:
             if len(models) != self.n_local:
@@ -1243,7 +1312,25 @@ class VirtualWorkerGroup:
         self.engine.mix_rounds_at(self.iter_dev, ctrs, self.layout, stream)
 
     # ------------------------------------------------------------------ fused SGD + mixing
-    def attach_sgd(self, momentum=0.0, weight_decay=0.0, nesterov=False, zero_grads=True, master_weights=False):
+    def _attach_clip(self, lay, clip):
+        """attach_*(clip_grad_norm=clip): the norm launch's state over the fused layout's gradient table"""
+        self.clip_grad_norm = clip
+        if clip is None:
+            return
+        self._clip = GradNorm([self.numel], lay, self.grad_arena.element_size(), clip)
+        self.grad_norms, self.grad_scales = self._clip.norms, self._clip.scales
+
+    def grad_norm(self, stream=None):
+        """Enqueue the norm launches alone (csrc/grad_norm.hip) and return `grad_norms`: every worker's
+        gradient 2-norm, fp32 CUDA [n_local], valid once the stream reaches it; `grad_scales` holds the
+        clip factors.  Needs attach_sgd / attach_adamw with clip_grad_norm set."""
+        if self._clip is None:
+            raise MXError("grad_norm: no clipping state: attach_sgd / attach_adamw with clip_grad_norm=...")
+        self._clip.enqueue(stream_ptr(stream))
+        return self.grad_norms
+
+    def attach_sgd(self, momentum=0.0, weight_decay=0.0, nesterov=False, zero_grads=True, master_weights=False,
+                   clip_grad_norm=None):
         """Give the group torch.optim.SGD's state (dampening 0) so that one launch per iteration
         applies every worker's update and the round's mix (csrc/sgd_mix.hip; the reference's
         optimizer.step() + zero_grad() + communicate(), train_mpi.py:131-142).
@@ -1266,7 +1353,18 @@ class VirtualWorkerGroup:
         bf16(master), rounded once to nearest even, so updates below half a bf16 ulp accumulate
         instead of rounding away.  `rows` is write-only to the launch: anything written to `rows`
         directly (sync_rows, a checkpoint without masters) is overwritten by bf16(master) at the
-        next step unless master_from_rows() is called after it."""
+        next step unless master_from_rows() is called after it.
+
+        clip_grad_norm=X (a positive finite float; anything else but None is a ValueError) is
+        torch.nn.utils.clip_grad_norm_(model.parameters(), X) -- 2-norm, error_if_nonfinite=False --
+        per worker, without its passes over the gradients: every step first enqueues the norm
+        launches (csrc/grad_norm.hip: one read of the gradient arena), then the fused launch with
+        each row's factor multiplied into its gradient on the way into the update.  `grad_norms`
+        (fp32 CUDA [n_local]) holds the norms BEFORE clipping -- what torch's function returns -- and
+        `grad_scales` the factors, after every step and after grad_norm().  Unlike torch, the gradients
+        in memory are never rewritten scaled: they are zeroed under zero_grads and otherwise left as
+        backward wrote them.  Clipping has no state: checkpoints are unchanged and load either way."""
+        clip = clip_value(clip_grad_norm, "attach_sgd")
         if self._sgd is not None:
             raise RuntimeError("attach_sgd: already attached")
         if self._adamw is not None:
@@ -1323,6 +1421,9 @@ class VirtualWorkerGroup:
         self._sgd = (lay, call, ctypes.addressof(call))
         self._sgd_fn = (_sgd_mix_bf16, lib.mx_sgd_mix_bf16_at, "mx_sgd_mix_bf16") if mixed else \
                        (_sgd_mix, lib.mx_sgd_mix_at, "mx_sgd_mix")
+        self._sgd_fn_scaled = (lib.mx_sgd_mix_bf16_scaled, lib.mx_sgd_mix_bf16_scaled_at) if mixed else \
+                              (lib.mx_sgd_mix_scaled, lib.mx_sgd_mix_scaled_at)
+        self._attach_clip(lay, clip)
 
     def master_from_rows(self):
         """Redo the masters as the exact widening of `rows` (attach_sgd / attach_adamw(master_weights=True) groups).
@@ -1347,7 +1448,12 @@ class VirtualWorkerGroup:
         alone -- and returns whether the round mixed."""
         call = self._sgd_state()
         it = self.engine.round_index(it)
-        rc = self._sgd_fn[0](call, it, lr, None, stream_ptr(stream))
+        if self._clip is not None:               # the norm launches, then the launch that applies the factors
+            s = stream_ptr(stream)
+            self._clip.enqueue(s)
+            rc = self._sgd_fn_scaled[0](call, self._clip.scale_ptr, it, lr, None, s)
+        else:
+            rc = self._sgd_fn[0](call, it, lr, None, stream_ptr(stream))
         if rc:
             check(rc, self._sgd_fn[2])
         return bool(self.engine.any_active[it])
@@ -1359,8 +1465,13 @@ class VirtualWorkerGroup:
         counter outside the schedule makes the launch a no-op: no SGD step either."""
         call = self._sgd_state()
         s = stream_ptr(stream)
-        check(self._sgd_fn[1](call, self.iter_dev.data_ptr(), self.engine.T, 0.0, self.lr_dev.data_ptr(), s),
-              self._sgd_fn[2] + "_at")
+        if self._clip is not None:
+            self._clip.enqueue(s)
+            check(self._sgd_fn_scaled[1](call, self._clip.scale_ptr, self.iter_dev.data_ptr(), self.engine.T, 0.0,
+                                         self.lr_dev.data_ptr(), s), self._sgd_fn[2] + "_scaled_at")
+        else:
+            check(self._sgd_fn[1](call, self.iter_dev.data_ptr(), self.engine.T, 0.0, self.lr_dev.data_ptr(), s),
+                  self._sgd_fn[2] + "_at")
         check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, s), "mx_iter_advance")
 
     def sgd_communicate(self, lr):
@@ -1376,7 +1487,7 @@ class VirtualWorkerGroup:
 
     # ------------------------------------------------------------------ fused AdamW + mixing
     def attach_adamw(self, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled=True, zero_grads=True,
-                     master_weights=False):
+                     master_weights=False, clip_grad_norm=None):
         """Give the group torch.optim.AdamW's state (decoupled=False: torch.optim.Adam's, the decay as
         an L2 term in the gradient; no amsgrad, no maximize) so that one launch per iteration applies
         every worker's update and the round's mix (csrc/adamw_mix.hip).
@@ -1394,7 +1505,13 @@ class VirtualWorkerGroup:
         the gradient arena is bfloat16 (each adopted parameter's .grad a bf16 view of it), exp_avg
         and exp_avg_sq stay fp32.  The launch updates and mixes the MASTERS and rewrites `rows` as
         bf16(master), rounded once to nearest even.  `rows` is write-only to the launch: call
-        master_from_rows() after anything that writes `rows` directly."""
+        master_from_rows() after anything that writes `rows` directly.
+
+        clip_grad_norm=X is attach_sgd's: torch.nn.utils.clip_grad_norm_(model.parameters(), X) per
+        worker as one extra read of the gradient arena; exp_avg and exp_avg_sq see the clipped
+        gradient, `grad_norms` / `grad_scales` hold the pre-clip norms and the factors, and the
+        gradients in memory are never rewritten scaled."""
+        clip = clip_value(clip_grad_norm, "attach_adamw")
         if self._adamw is not None:
             raise RuntimeError("attach_adamw: already attached")
         if self._sgd is not None:
@@ -1457,6 +1574,9 @@ class VirtualWorkerGroup:
         self._adamw = (lay, call, ctypes.addressof(call))
         self._adamw_fn = (_adamw_mix_bf16, lib.mx_adamw_mix_bf16_at, "mx_adamw_mix_bf16") if mixed else \
                          (_adamw_mix, lib.mx_adamw_mix_at, "mx_adamw_mix")
+        self._adamw_fn_scaled = (lib.mx_adamw_mix_bf16_scaled, lib.mx_adamw_mix_bf16_scaled_at) if mixed else \
+                                (lib.mx_adamw_mix_scaled, lib.mx_adamw_mix_scaled_at)
+        self._attach_clip(lay, clip)
 
     def _adamw_state(self):
         if self._adamw is None:
@@ -1470,7 +1590,12 @@ class VirtualWorkerGroup:
         all-zero round is the optimizer step alone -- and returns whether the round mixed."""
         call = self._adamw_state()
         it = self.engine.round_index(it)
-        rc = self._adamw_fn[0](call, it, self.opt_step + 1, lr, None, stream_ptr(stream))
+        if self._clip is not None:               # the norm launches, then the launch that applies the factors
+            s = stream_ptr(stream)
+            self._clip.enqueue(s)
+            rc = self._adamw_fn_scaled[0](call, self._clip.scale_ptr, it, self.opt_step + 1, lr, None, s)
+        else:
+            rc = self._adamw_fn[0](call, it, self.opt_step + 1, lr, None, stream_ptr(stream))
         if rc:
             check(rc, self._adamw_fn[2])
         self.opt_step += 1
@@ -1485,8 +1610,14 @@ class VirtualWorkerGroup:
         touched."""
         call = self._adamw_state()
         s = stream_ptr(stream)
-        check(self._adamw_fn[1](call, self.iter_dev.data_ptr(), self.engine.T, self.opt_step_dev.data_ptr(), 0.0,
-                                self.lr_dev.data_ptr(), s), self._adamw_fn[2] + "_at")
+        if self._clip is not None:
+            self._clip.enqueue(s)
+            check(self._adamw_fn_scaled[1](call, self._clip.scale_ptr, self.iter_dev.data_ptr(), self.engine.T,
+                                           self.opt_step_dev.data_ptr(), 0.0, self.lr_dev.data_ptr(), s),
+                  self._adamw_fn[2] + "_scaled_at")
+        else:
+            check(self._adamw_fn[1](call, self.iter_dev.data_ptr(), self.engine.T, self.opt_step_dev.data_ptr(), 0.0,
+                                    self.lr_dev.data_ptr(), s), self._adamw_fn[2] + "_at")
         check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, s), "mx_iter_advance")
         check(lib.mx_iter_advance(self.opt_step_dev.data_ptr(), 1, s), "mx_iter_advance")
 

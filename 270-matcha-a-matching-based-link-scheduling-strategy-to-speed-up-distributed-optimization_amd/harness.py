@@ -197,7 +197,7 @@ class VirtualTrainer:
     step for all workers is a handful of batched launches plus the gossip kernel."""
 
     def __init__(self, args, model_fn, n_batches, device="cuda", batched=False, graph=False, fused_sgd=False,
-                 fused_adamw=False, adamw_hyper=None):
+                 fused_adamw=False, adamw_hyper=None, clip_grad_norm=None):
         """fused_sgd=True (non-batched, uncompressed): the workers' optimizer.step() /
         zero_grad() and the gossip round run as ONE launch (VirtualWorkerGroup.attach_sgd /
         sgd_communicate, csrc/sgd_mix.hip): backward() accumulates into the group's gradient arena,
@@ -213,6 +213,12 @@ class VirtualTrainer:
         csrc/adamw_mix_bf16.hip): betas (0.9, 0.999), eps 1e-8 and the harness's weight decay 5e-4 as the
         decoupled decay, or what adamw_hyper (attach_adamw's keyword arguments) overrides; checkpoints
         save exp_avg / exp_avg_sq rows and the step count.
+
+        clip_grad_norm=X (with fused_sgd or fused_adamw): torch.nn.utils.clip_grad_norm_(model.parameters(),
+        X) per worker inside the fused step (attach_sgd / attach_adamw's keyword: one extra read of the
+        gradient arena, csrc/grad_norm.hip).  `grad_norm_log` collects every round's pre-clip norms
+        (a float32 CPU tensor [size] per round) and the epoch stats carry each worker's last one.  The
+        other paths keep torch's optimizers and do not clip: asking for it there is a ValueError.
 
         graph=True (with batched=True, decentralized gossip, one GPU): once the learning rate
         is constant within an epoch, the whole training iteration -- vmap'd forward / backward,
@@ -234,6 +240,11 @@ class VirtualTrainer:
         if self.fused_adamw and (batched or args.compress):
             raise ValueError("fused_adamw needs per-worker (non-batched), uncompressed training: the vmap path's "
                              "gradients are fresh tensors every iteration and ChocoSGD mixes compressed messages")
+        self.clip_grad_norm = clip_grad_norm
+        if clip_grad_norm is not None and not (self.fused_sgd or self.fused_adamw):
+            raise ValueError("clip_grad_norm is honoured by the fused optimizer steps only (fused_sgd=True or "
+                             "fused_adamw=True): the other paths step torch's optimizers and do not clip")
+        self.grad_norm_log = []
         self.GP = make_topology(args, 0, size, args.epoch * n_batches)
         self.models = []
         for r in range(size):
@@ -250,12 +261,13 @@ class VirtualTrainer:
         mixed = (self.fused_sgd or self.fused_adamw) and self.group.dtype == torch.bfloat16
         if self.fused_sgd:
             # all-bfloat16 models: fp32 master weights, updated and mixed by the launch (csrc/sgd_mix_bf16.hip)
-            self.group.attach_sgd(args.momentum, 5e-4, args.nesterov, master_weights=mixed)
+            self.group.attach_sgd(args.momentum, 5e-4, args.nesterov, master_weights=mixed,
+                                  clip_grad_norm=clip_grad_norm)
         if self.fused_adamw:
             # all-bfloat16 models: fp32 master weights, as above (csrc/adamw_mix_bf16.hip)
             hyper = {"betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 5e-4, "decoupled": True}
             hyper.update(adamw_hyper or {})
-            self.group.attach_adamw(**hyper, master_weights=mixed)
+            self.group.attach_adamw(**hyper, master_weights=mixed, clip_grad_norm=clip_grad_norm)
         sync_rows(self.group.rows)
         if mixed:
             self.group.master_from_rows()                        # the masters of the synchronized rows
@@ -449,6 +461,8 @@ class VirtualTrainer:
             else:
                 comm_time += self.communicate()              # train_mpi.py:142, all workers at once
             self._dev_iter_synced = False
+            if self.clip_grad_norm is not None:              # the round is complete (wait_round): a plain read
+                self.grad_norm_log.append(self.group.grad_norms.cpu())
             if on_round is not None:
                 on_round("after", self)
         record_time = time.time() - tic
@@ -457,6 +471,8 @@ class VirtualTrainer:
             test_acc = top1[r].avg             # no test split in the synthetic stream
             stats.append({"worker": r, "loss": losses[r].avg, "train_acc": top1[r].avg,
                           "comp_time": comp[r], "comm_time": comm_time})
+            if self.clip_grad_norm is not None and self.grad_norm_log:
+                stats[-1]["grad_norm"] = float(self.grad_norm_log[-1][r])
             if self.recorders is not None:
                 self.recorders[r].add_new(record_time, comp[r], comm_time, comp[r] + comm_time, top1[r].avg,
                                           losses[r].avg, test_acc)

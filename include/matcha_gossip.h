@@ -496,6 +496,86 @@ int mx_adamw_mix_bf16(const mx_adamw_mix_bf16_call* call, int64_t iter, int64_t 
 int mx_adamw_mix_bf16_at(const mx_adamw_mix_bf16_call* call, const int64_t* iter_dev, int64_t n_iters,
                          const int64_t* step_dev, float lr, const float* lr_dev, void* stream);
 
+/* ---------------------------------------------------------------- global-norm gradient clipping
+ * torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) -- 2-norm, error_if_nonfinite=False -- PER
+ * WORKER, for the four fused launches above (csrc/grad_norm.hip).  Every row of the gradient tables is one
+ * model's gradient and gets its own norm and its own factor:
+ *   S_r      = sum over every segment of row r of f64(g)^2     every square formed and summed in fp64; bfloat16
+ *                                                              is widened exactly (bits << 16)
+ *   norm[r]  = f32(sqrt(S_r))                                  fp64 square root, ONE rounding to fp32: the
+ *                                                              value clip_grad_norm_ returns, before clipping
+ *   c        = fmul(fdiv(1.0f, fadd(norm[r], 1e-6f)), max_norm)   one fp32 rounding each: torch evaluates its
+ *                                                              max_norm / (total_norm + 1e-6) on a tensor as
+ *                                                              reciprocal() * max_norm (Tensor.__rtruediv__)
+ *   scale[r] = c > 1.0f ? 1.0f : c                             torch's clamp(max=1.0); a NaN stays a NaN
+ * The summation order is fixed (csrc/grad_norm.hip): norm[r] depends only on row r's values and lengths,
+ * and the bits are the same on every launch and under every knob; no floating-point atomics.  For
+ * P <= 2^26 elements per row any fp64 order is within P * 2^-53 of the exact sum, so norm[r] is within
+ * 1 fp32 ulp of the correctly rounded norm.  A NaN element gives a NaN norm and factor, an Inf element
+ * norm Inf and factor 0, a row of zeros norm 0 and factor 1.
+ * mx_grad_norm_call, built once and kept alive by the caller:
+ *   g_ptrs_dev   [nseg][n_local] device table of row pointers and seg_len_dev int64 [nseg] elements per
+ *                tensor: the g_ptrs_dev / seg_len_dev of the fused call records, read only.  Nothing at or
+ *                past seg_len of a row is read into the sum.
+ *   elem_size    4 (fp32) or 2 (bfloat16 bit patterns)
+ *   work_dev     fp64 workspace of mx_grad_norm_layout(seg_len_host, nseg, n_local, &chunks) BYTES (the
+ *                return value; negative on bad arguments); `chunks` is what that call stored: one slot
+ *                per mx_grad_norm_cols() = 4096 columns of a (segment, row).  Every slot is rewritten by
+ *                every call: no zeroing.
+ *   norm_dev / scale_dev   float [n_local] outputs, on the device
+ * mx_grad_norm(call, stream) enqueues two launches -- per-work-item partials into their own workspace
+ * slots, then one workgroup per row adding them in a fixed order -- with no host synchronisation and no
+ * host read, so it can be captured in a graph.  16-byte loads where a row pointer is 16-byte aligned
+ * and the elements are in range, per-element loads elsewhere; plain (temporal) loads, because the fused
+ * launch reads the same gradient right afterwards.
+ * MX_ERR_INVALID, nothing launched: a null call record, table, output or workspace; elem_size other than
+ * 2 or 4; n_local outside [1, 64]; max_norm not a positive finite number.
+ * mx_grad_norm_set / _get: "blocks_per_cu" (persistent workgroups per CU of the partial pass, default
+ * 8), "grid" (> 0: exact grid size).  Which workgroup computes a work item, never how: speed only. */
+typedef struct mx_grad_norm_call {
+    const void* const* g_ptrs_dev;
+    const int64_t* seg_len_dev;
+    double* work_dev;
+    float* norm_dev;
+    float* scale_dev;
+    int64_t chunks;
+    int32_t nseg, n_local, elem_size;
+    float max_norm;
+} mx_grad_norm_call;
+int mx_grad_norm_cols(void);
+int64_t mx_grad_norm_layout(const int64_t* seg_len_host, int nseg, int n_local, int64_t* chunks_out);
+int mx_grad_norm_set(const char* key, int value);
+int mx_grad_norm_get(const char* key);
+int mx_grad_norm(const mx_grad_norm_call* call, void* stream);
+
+/* The fused launches with a per-row gradient factor: the call record of the unscaled entry point,
+ * unchanged, plus gscale_dev (float [n_local] on the device, read when the kernel runs -- scale_dev of an
+ * mx_grad_norm enqueued before it on the same stream).  Before anything else in the update
+ *   g' = fmul(gscale[r], g)            fp32;  fmul(gscale[r], f32(g)) for bfloat16 gradients
+ * and the L2 term, m, v and the momentum buffer all see g', as they do in torch after clip_grad_norm_.
+ * g IN MEMORY is never rewritten scaled -- it is zeroed under zero_grads, otherwise left as backward wrote
+ * it -- which differs from torch's in-place clipping: whoever reads the gradients after the step sees them
+ * unclipped.  gscale_dev == NULL multiplies nothing: every bit is the unscaled entry point's (which pass
+ * NULL themselves).  Row handling, launch-side no-ops (nothing of x / w, g, m, v, p is written) and
+ * host-side refusals are the unscaled entry points'. */
+int mx_sgd_mix_scaled(const mx_sgd_mix_call* call, const float* gscale_dev, int64_t iter, float lr,
+                      const float* lr_dev, void* stream);
+int mx_sgd_mix_scaled_at(const mx_sgd_mix_call* call, const float* gscale_dev, const int64_t* iter_dev,
+                         int64_t n_iters, float lr, const float* lr_dev, void* stream);
+int mx_sgd_mix_bf16_scaled(const mx_sgd_mix_bf16_call* call, const float* gscale_dev, int64_t iter, float lr,
+                           const float* lr_dev, void* stream);
+int mx_sgd_mix_bf16_scaled_at(const mx_sgd_mix_bf16_call* call, const float* gscale_dev, const int64_t* iter_dev,
+                              int64_t n_iters, float lr, const float* lr_dev, void* stream);
+int mx_adamw_mix_scaled(const mx_adamw_mix_call* call, const float* gscale_dev, int64_t iter, int64_t step,
+                        float lr, const float* lr_dev, void* stream);
+int mx_adamw_mix_scaled_at(const mx_adamw_mix_call* call, const float* gscale_dev, const int64_t* iter_dev,
+                           int64_t n_iters, const int64_t* step_dev, float lr, const float* lr_dev, void* stream);
+int mx_adamw_mix_bf16_scaled(const mx_adamw_mix_bf16_call* call, const float* gscale_dev, int64_t iter,
+                             int64_t step, float lr, const float* lr_dev, void* stream);
+int mx_adamw_mix_bf16_scaled_at(const mx_adamw_mix_bf16_call* call, const float* gscale_dev,
+                                const int64_t* iter_dev, int64_t n_iters, const int64_t* step_dev, float lr,
+                                const float* lr_dev, void* stream);
+
 /* ---------------------------------------------------------------- flatten / unflatten
  * mx_gather replaces flatten_tensors (comm_helpers.py:12-30): flat[off[s] + i] = src[s][i].
  * mx_scatter is the copy_ loop of reset_model over unflatten_tensors views

@@ -61,9 +61,18 @@ def main():
                     "round mixes, and the bfloat16 models are their rounded image")
     ap.add_argument("--pull", action="store_true", help="one process per GPU: gossip rounds over the pull "
                     "transport (partner rows / Choco messages read from the peers' HBM) instead of RCCL")
+    ap.add_argument("--clip-grad-norm", default=None, type=float, metavar="X", help="--fused-sgd / --fused-adamw: "
+                    "torch.nn.utils.clip_grad_norm_(model.parameters(), X) per worker inside the fused step (one "
+                    "extra read of the gradients); an error on the paths that keep torch's optimizers")
     a = ap.parse_args()
+    if a.clip_grad_norm is not None and not (a.fused_sgd or a.fused_adamw):
+        ap.error("--clip-grad-norm is honoured by the fused optimizer steps only: add --fused-sgd or --fused-adamw "
+                 "(the other paths step torch's optimizers and do not clip)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    if a.clip_grad_norm is not None and world > 1:
+        ap.error("--clip-grad-norm: one process per GPU trains with torch's optimizers (no fused step yet) and "
+                 "does not clip")
     args = H.HarnessArgs(name=a.name, description=a.description, model=a.model, lr=a.lr, momentum=a.momentum,
                          epoch=a.epoch, bs=a.bs, warmup=a.warmup, nesterov=a.nesterov, matcha=a.matcha,
                          budget=a.budget, graphid=a.graphid, savePath=a.savePath, save=a.save,
@@ -85,7 +94,8 @@ def main():
     else:
         tr = H.VirtualTrainer(args, model_fn, a.batches, batched=a.batched or a.graph, graph=a.graph,
                               fused_sgd=a.fused_sgd, fused_adamw=a.fused_adamw,
-                              adamw_hyper={"betas": (a.beta1, a.beta2), "eps": a.eps, "weight_decay": a.wd})
+                              adamw_hyper={"betas": (a.beta1, a.beta2), "eps": a.eps, "weight_decay": a.wd},
+                              clip_grad_norm=a.clip_grad_norm)
         if a.resume:
             tr.load(a.resume)
     import time
@@ -95,8 +105,10 @@ def main():
         stats = tr.train_epoch()
         torch.cuda.synchronize()
         if rank == 0:
+            norms = "" if "grad_norm" not in stats[0] else \
+                ", grad_norm: " + " ".join(f"{s['grad_norm']:.3g}" for s in stats)
             print(H.epoch_summary(stats, tr.epoch - 1) + f", wall: {time.time() - t:.3f} s "
-                  f"({a.batches / (time.time() - t):.1f} iterations/s)", flush=True)
+                  f"({a.batches / (time.time() - t):.1f} iterations/s)" + norms, flush=True)
     tr.finish()
     if a.checkpoint and world == 1:
         tr.save(a.checkpoint)
