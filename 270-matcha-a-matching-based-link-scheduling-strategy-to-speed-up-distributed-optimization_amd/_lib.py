@@ -76,6 +76,15 @@ SIGNATURES = {
     "mx_adamw_mix_scaled_at": (c_int, [c_p, c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
     "mx_adamw_mix_bf16_scaled": (c_int, [c_p, c_p, c_i64, c_i64, c_f32, c_p, c_p]),
     "mx_adamw_mix_bf16_scaled_at": (c_int, [c_p, c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
+    "mx_param_runs_check": (c_int, [c_p, c_int, c_p, c_p, c_p, c_p]),
+    "mx_sgd_mix_grouped": (c_int, [c_p, c_p, c_p, c_i64, c_f32, c_p, c_p]),
+    "mx_sgd_mix_grouped_at": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_f32, c_p, c_p]),
+    "mx_sgd_mix_bf16_grouped": (c_int, [c_p, c_p, c_p, c_i64, c_f32, c_p, c_p]),
+    "mx_sgd_mix_bf16_grouped_at": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_f32, c_p, c_p]),
+    "mx_adamw_mix_grouped": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_f32, c_p, c_p]),
+    "mx_adamw_mix_grouped_at": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
+    "mx_adamw_mix_bf16_grouped": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_f32, c_p, c_p]),
+    "mx_adamw_mix_bf16_grouped_at": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
     "mx_gather": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p]),
     "mx_scatter": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p]),
     "mx_topk_work_bytes": (ctypes.c_size_t, [c_i64]),

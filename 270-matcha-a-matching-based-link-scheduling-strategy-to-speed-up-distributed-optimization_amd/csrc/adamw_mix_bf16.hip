@@ -54,6 +54,7 @@
 #include "mx_common.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 constexpr int kTPB = 256;
@@ -221,6 +222,81 @@ __device__ __forceinline__ F4 adam4(const F4& x, const F4& g, F4& m, F4& v, cons
     return out;
 }
 
+// Per-parameter-group launches (mx_adamw_mix_bf16_grouped): the columns of a segment are cut into runs that
+// each carry their own weight decay and learning-rate scale (mx_param_runs; the tables are read when
+// the kernel runs).  Element of run r: lr_r = fmul(lr, s_r), then the update above with wd -> wd_r and
+// lr -> lr_r.  The ungrouped instantiations carry none of this: their argument block is Hyper alone.
+struct Runs {
+    const int32_t* off;        // int32 [nseg + 1]: segment s owns runs [off[s], off[s + 1])
+    const int64_t* end;        // int64 [nruns]: exclusive end column within the segment, ascending
+    const float* wd;           // float [nruns]
+    const float* scale;        // float [nruns]
+};
+struct HyperG : Hyper {
+    Runs rn;
+};
+template <bool GROUPED>
+using HyperOf = std::conditional_t<GROUPED, HyperG, Hyper>;
+
+// what a run derives from the launch's learning rate and bias corrections
+__device__ __forceinline__ Step run_step(float lr, float bc1, float bc2s, float wd, float scale, int decoupled) {
+    const float lr_r = lr * scale;                                   // one rounding; scale 1.0 gives lr
+    Step s;
+    s.nss = -__fdiv_rn(lr_r, bc1);
+    s.bc2s = bc2s;
+    s.dec = wd != 0.0f && decoupled;
+    s.l2 = wd != 0.0f && !decoupled;
+    s.decay = __builtin_fmaf(-lr_r, wd, 1.0f);
+    return s;
+}
+
+// adam4's update of one element with the run's own decay
+__device__ __forceinline__ float adam1(float x, float g, float& m, float& v, const Step& s, float wd, const Hyper& h) {
+    const float x1 = s.dec ? x * s.decay : x;
+    const float g1 = s.l2 ? __builtin_fmaf(wd, x, g) : g;
+    const float dm = g1 - m;
+    m = __builtin_fmaf(h.omb1, dm, m);
+    const float gg = g1 * g1;
+    const float bv = h.beta2 * v;
+    v = __builtin_fmaf(h.omb2, gg, bv);
+    const float root = __builtin_sqrtf(v);
+    const float den = __fdiv_rn(root, s.bc2s) + h.eps;
+    return __builtin_fmaf(s.nss, __fdiv_rn(m, den), x1);
+}
+
+// a chunk that lies in one run (the whole work item does): the run's constants are scalars
+__device__ __forceinline__ F4 adam4_run(const F4& x, const F4& g, F4& m, F4& v, const Step& s, float wd, const Hyper& h) {
+    F4 out;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        float mt = m[t], vt = v[t];
+        out[t] = adam1(x[t], g[t], mt, vt, s, wd, h);
+        m[t] = mt;
+        v[t] = vt;
+    }
+    return out;
+}
+
+// a chunk of a work item that holds a run boundary: every element walks forward from the work item's
+// first run `r` to its own (a chunk may span four runs) and derives its constants itself.  The walk
+// stops at the segment's last run, so columns at or past the segment's length (zero-filled, never
+// stored) read inside the tables.
+__device__ __forceinline__ F4 adam4_walk(const F4& x, const F4& g, F4& m, F4& v, int64_t c, int r, int rhi, float lr,
+                                         float bc1, float bc2s, const HyperG& h) {
+    F4 out;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        while (r + 1 < rhi && h.rn.end[r] <= c + t) ++r;
+        const float wd = h.rn.wd[r];
+        const Step s = run_step(lr, bc1, bc2s, wd, h.rn.scale[r], h.decoupled);
+        float mt = m[t], vt = v[t];
+        out[t] = adam1(x[t], g[t], mt, vt, s, wd, h);
+        m[t] = mt;
+        v[t] = vt;
+    }
+    return out;
+}
+
 template <int NS>
 struct PlanLds {
     int32_t w[mx::kPlanHeader + 2 * NS + NS * kMaxM];
@@ -235,7 +311,8 @@ __device__ __forceinline__ int64_t round_of(int64_t iter, const int64_t* iter_de
 }
 
 // NS rows x TW columns per work item; a layout tile (mx_adamw_mix_bf16_tile) is `split` work items.
-template <int NS, int TW, bool NT>
+// GROUPED: per-run weight decay and learning-rate scale (see Runs above).
+template <int NS, int TW, bool NT, bool GROUPED>
 __global__ __launch_bounds__(kTPB) void adamw_mix_bf16_rows(float* const* __restrict__ w_ptrs,
                                                             uint16_t* const* __restrict__ g_ptrs,
                                                             float* const* __restrict__ m_ptrs,
@@ -246,7 +323,7 @@ __global__ __launch_bounds__(kTPB) void adamw_mix_bf16_rows(float* const* __rest
                                                             int64_t total_tiles, int split,
                                                             const int32_t* __restrict__ plan, int64_t iter,
                                                             const int64_t* __restrict__ iter_dev, int n_local, int M,
-                                                            float alpha, Hyper h) {
+                                                            float alpha, HyperOf<GROUPED> h) {
     constexpr int C4 = TW / 4;            // 4-element chunks per row per work item
     constexpr int NQ = TW / 256;          // 256-column passes per row
     constexpr int NI = NS * NQ;           // items per work item (<= 64: one per lane of wave 0)
@@ -265,6 +342,11 @@ __global__ __launch_bounds__(kTPB) void adamw_mix_bf16_rows(float* const* __rest
 
     struct Geo {
         int64_t base, col0, lim;             // base: the segment's row of the pointer tables
+        // GROUPED only: the first run that ends past col0, the end of the segment's runs, whether that
+        // run covers the whole work item, and its pair
+        int r0, rhi;
+        bool uni;
+        float wd, scale;
     };
     auto geo = [&](int64_t work) {
         const int64_t tile = work / split;
@@ -277,6 +359,22 @@ __global__ __launch_bounds__(kTPB) void adamw_mix_bf16_rows(float* const* __rest
         gq.base = (int64_t)lo * n_local;
         gq.col0 = (tile - tile_off[lo]) * ((int64_t)TW * split) + (work % split) * TW;
         gq.lim = seg_len[lo];
+        gq.r0 = gq.rhi = 0;
+        gq.uni = true;
+        gq.wd = gq.scale = 0.0f;
+        if constexpr (GROUPED) {
+            int a = h.rn.off[lo], b = h.rn.off[lo + 1];
+            gq.rhi = b;
+            while (a < b) {                  // wave-uniform: the first run with end > col0
+                const int mid = (a + b) >> 1;
+                if (h.rn.end[mid] <= gq.col0) a = mid + 1; else b = mid;
+            }
+            gq.r0 = a < gq.rhi ? a : gq.rhi - 1;             // a work item wholly past the segment's length
+            const int64_t last = gq.col0 + TW < gq.lim ? gq.col0 + TW : gq.lim;
+            gq.uni = h.rn.end[gq.r0] >= last;
+            gq.wd = h.rn.wd[gq.r0];
+            gq.scale = h.rn.scale[gq.r0];
+        }
         return gq;
     };
     // wide accesses only where the (segment, row)'s w, m and v are 16-byte and g and p 8-byte aligned
@@ -326,9 +424,14 @@ __global__ __launch_bounds__(kTPB) void adamw_mix_bf16_rows(float* const* __rest
     auto mixes = [&](int r) { return active && (deg[r] > 0 || idle); };
     auto degree = [&](int r) { return mixes(r) ? deg[r] : 0; };
     Step st;
+    float lr_g = 0.0f, bc1_g = 1.0f;         // GROUPED: what run_step needs per work item / per element
     {
         const int64_t bi = (tstep < h.n_bias ? tstep : h.n_bias) - 1;
         const float lr = h.lr_dev ? *h.lr_dev : h.lr;
+        if constexpr (GROUPED) {
+            lr_g = lr;
+            bc1_g = h.bias[2 * bi];
+        }
         st.nss = -__fdiv_rn(lr, h.bias[2 * bi]);
         st.bc2s = h.bias[2 * bi + 1];
         st.dec = h.wd != 0.0f && h.decoupled;
@@ -365,7 +468,14 @@ __global__ __launch_bounds__(kTPB) void adamw_mix_bf16_rows(float* const* __rest
                 const int64_t c = gq.col0 + (int64_t)(at % C4 + lane) * 4;
                 const bool vec = vec_of(gq, k);
                 const F4 g = h.gscale ? scale4(widen4(G[t]), h.gscale[k]) : widen4(G[t]);
-                lds[at + lane] = adam4(X[t], g, Mv[t], Vv[t], st, h);
+                if constexpr (GROUPED) {
+                    // st is the parked work item's own (set at the top of its loop pass), never the
+                    // prefetched one's
+                    lds[at + lane] = gq.uni ? adam4_run(X[t], g, Mv[t], Vv[t], st, gq.wd, h)
+                                            : adam4_walk(X[t], g, Mv[t], Vv[t], c, gq.r0, gq.rhi, lr_g, bc1_g, st.bc2s, h);
+                } else {
+                    lds[at + lane] = adam4(X[t], g, Mv[t], Vv[t], st, h);
+                }
                 store_f32<NT>(m_ptrs[gq.base + k], c, gq.lim, vec, Mv[t]);
                 store_f32<NT>(v_ptrs[gq.base + k], c, gq.lim, vec, Vv[t]);
                 if (h.zero_grads) store_b16<NT>(g_ptrs[gq.base + k], c, gq.lim, vec, U2{0u, 0u});
@@ -421,6 +531,9 @@ __global__ __launch_bounds__(kTPB) void adamw_mix_bf16_rows(float* const* __rest
     };
     for (int64_t i = 0; i < niter; ++i) {
         if (i) __syncthreads();              // every wave is done reading the previous tile
+        if constexpr (GROUPED) {
+            if (cur.uni) st = run_step(lr_g, bc1_g, st.bc2s, cur.wd, cur.scale, h.decoupled);
+        }
         park(cur, 0);
         for (int j0 = kB; j0 < E; j0 += kB) {
             issue(cur, j0);
@@ -476,10 +589,11 @@ struct Args {
     int64_t iter;
     const int64_t* iter_dev;
     Hyper h;
+    Runs rn;
     hipStream_t st;
 };
 
-template <int NS, int TW, bool NT>
+template <int NS, int TW, bool NT, bool GROUPED>
 int launch(const Args& a) {
     const mx_adamw_mix_bf16_call* c = a.c;
     const int split = pick(c->n_local).tile / TW;
@@ -493,23 +607,26 @@ int launch(const Args& a) {
     if (flat && g_tune.wgpc > 0) {
         static const int stat = [] {                           // static LDS of this instantiation
             hipFuncAttributes fa{};
-            return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(adamw_mix_bf16_rows<NS, TW, NT>)) ==
+            return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(adamw_mix_bf16_rows<NS, TW, NT, GROUPED>)) ==
                            hipSuccess
                        ? (int)fa.sharedSizeBytes : 0;
         }();
         pad = mx::lds_cap_pad(stat, g_tune.wgpc);
     }
-    hipLaunchKernelGGL((adamw_mix_bf16_rows<NS, TW, NT>), dim3((unsigned)grid), dim3(kTPB), pad, a.st, c->w_ptrs_dev,
+    HyperOf<GROUPED> hy;
+    static_cast<Hyper&>(hy) = a.h;
+    if constexpr (GROUPED) hy.rn = a.rn;
+    hipLaunchKernelGGL((adamw_mix_bf16_rows<NS, TW, NT, GROUPED>), dim3((unsigned)grid), dim3(kTPB), pad, a.st, c->w_ptrs_dev,
                        c->g_ptrs_dev, c->m_ptrs_dev, c->v_ptrs_dev, c->p_ptrs_dev, c->seg_len_dev, c->tile_off_dev,
                        c->nseg, c->total_tiles, split, c->plan_dev, a.iter, a.iter_dev, c->n_local, c->M, c->alpha,
-                       a.h);
+                       hy);
     MX_LAUNCH_CHECK();
     return MX_OK;
 }
 
-int adamw_mix_bf16(const mx_adamw_mix_bf16_call* c, const float* gscale, int64_t iter, const int64_t* iter_dev,
-                   int64_t step, const int64_t* step_dev, float lr, const float* lr_dev, void* stream,
-                   const char* who) {
+int adamw_mix_bf16(const mx_adamw_mix_bf16_call* c, const mx_param_runs* runs, const float* gscale, int64_t iter,
+                   const int64_t* iter_dev, int64_t step, const int64_t* step_dev, float lr, const float* lr_dev,
+                   void* stream, const char* who) {
     MX_CHECK(c, "%s: null call record", who);
     MX_CHECK(c->w_ptrs_dev && c->g_ptrs_dev && c->m_ptrs_dev && c->v_ptrs_dev && c->p_ptrs_dev && c->seg_len_dev &&
                  c->tile_off_dev && c->plan_dev && c->bias_dev,
@@ -522,6 +639,8 @@ int adamw_mix_bf16(const mx_adamw_mix_bf16_call* c, const float* gscale, int64_t
     MX_CHECK(c->n_bias >= 1, "%s: n_bias=%lld < 1", who, (long long)c->n_bias);
     MX_CHECK(iter >= 0, "%s: iter < 0", who);
     MX_CHECK(step_dev || step >= 1, "%s: optimizer step %lld < 1", who, (long long)step);
+    MX_CHECK(!runs || (runs->run_off_dev && runs->run_end_dev && runs->wd_dev && runs->lr_scale_dev && runs->nruns >= 1),
+             "%s: parameter runs with a null table or nruns < 1", who);
     if (c->total_tiles <= 0) return MX_OK;
     const Cls cl = pick(c->n_local);
     // bytes the round moves: w, m, v read + written, g read (+ zeroed), p written
@@ -531,8 +650,11 @@ int adamw_mix_bf16(const mx_adamw_mix_bf16_call* c, const float* gscale, int64_t
     const Args a{c, iter, iter_dev,
                  Hyper{lr, c->wd, c->omb1, c->beta2, c->omb2, c->eps, lr_dev, gscale, c->bias_dev, c->n_bias, step, step_dev,
                        c->decoupled != 0, c->zero_grads != 0},
+                 runs ? Runs{runs->run_off_dev, runs->run_end_dev, runs->wd_dev, runs->lr_scale_dev} : Runs{},
                  mx::as_stream(stream)};
-#define MX_ADAMW(N, TW) (nt ? launch<N, TW, true>(a) : launch<N, TW, false>(a))
+#define MX_ADAMW(N, TW)                                                                             \
+    (runs ? (nt ? launch<N, TW, true, true>(a) : launch<N, TW, false, true>(a))                    \
+          : (nt ? launch<N, TW, true, false>(a) : launch<N, TW, false, false>(a)))
     switch (cl.ns) {
         case 8: return MX_ADAMW(8, 512);
         case 16: return MX_ADAMW(16, 512);
@@ -592,24 +714,39 @@ extern "C" int mx_adamw_mix_bf16_get(const char* key) {
 
 extern "C" int mx_adamw_mix_bf16(const mx_adamw_mix_bf16_call* c, int64_t iter, int64_t step, float lr,
                                  const float* lr_dev, void* stream) {
-    return adamw_mix_bf16(c, nullptr, iter, nullptr, step, nullptr, lr, lr_dev, stream, "mx_adamw_mix_bf16");
+    return adamw_mix_bf16(c, nullptr, nullptr, iter, nullptr, step, nullptr, lr, lr_dev, stream, "mx_adamw_mix_bf16");
 }
 
 extern "C" int mx_adamw_mix_bf16_scaled(const mx_adamw_mix_bf16_call* c, const float* gscale_dev, int64_t iter,
                                         int64_t step, float lr, const float* lr_dev, void* stream) {
-    return adamw_mix_bf16(c, gscale_dev, iter, nullptr, step, nullptr, lr, lr_dev, stream, "mx_adamw_mix_bf16_scaled");
+    return adamw_mix_bf16(c, nullptr, gscale_dev, iter, nullptr, step, nullptr, lr, lr_dev, stream, "mx_adamw_mix_bf16_scaled");
 }
 
 extern "C" int mx_adamw_mix_bf16_at(const mx_adamw_mix_bf16_call* c, const int64_t* iter_dev, int64_t n_iters,
                                     const int64_t* step_dev, float lr, const float* lr_dev, void* stream) {
     MX_CHECK(iter_dev && step_dev, "mx_adamw_mix_bf16_at: null iteration or step counter");
-    return adamw_mix_bf16(c, nullptr, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream, "mx_adamw_mix_bf16_at");
+    return adamw_mix_bf16(c, nullptr, nullptr, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream, "mx_adamw_mix_bf16_at");
 }
 
 extern "C" int mx_adamw_mix_bf16_scaled_at(const mx_adamw_mix_bf16_call* c, const float* gscale_dev,
                                            const int64_t* iter_dev, int64_t n_iters, const int64_t* step_dev,
                                            float lr, const float* lr_dev, void* stream) {
     MX_CHECK(iter_dev && step_dev, "mx_adamw_mix_bf16_scaled_at: null iteration or step counter");
-    return adamw_mix_bf16(c, gscale_dev, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream,
+    return adamw_mix_bf16(c, nullptr, gscale_dev, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream,
                           "mx_adamw_mix_bf16_scaled_at");
+}
+
+extern "C" int mx_adamw_mix_bf16_grouped(const mx_adamw_mix_bf16_call* c, const mx_param_runs* runs,
+                                         const float* gscale_dev, int64_t iter, int64_t step, float lr,
+                                         const float* lr_dev, void* stream) {
+    return adamw_mix_bf16(c, runs, gscale_dev, iter, nullptr, step, nullptr, lr, lr_dev, stream,
+                          "mx_adamw_mix_bf16_grouped");
+}
+
+extern "C" int mx_adamw_mix_bf16_grouped_at(const mx_adamw_mix_bf16_call* c, const mx_param_runs* runs,
+                                            const float* gscale_dev, const int64_t* iter_dev, int64_t n_iters,
+                                            const int64_t* step_dev, float lr, const float* lr_dev, void* stream) {
+    MX_CHECK(iter_dev && step_dev, "mx_adamw_mix_bf16_grouped_at: null iteration or step counter");
+    return adamw_mix_bf16(c, runs, gscale_dev, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream,
+                          "mx_adamw_mix_bf16_grouped_at");
 }

@@ -36,3 +36,38 @@ size_t lds_cap_pad(int static_bytes, int wg_per_cu) {
 
 extern "C" const char* mx_version(void) { return "matcha-gossip gfx950 0.1"; }
 extern "C" const char* mx_last_error(void) { return mx::g_err; }
+
+// the host-side validator of the per-parameter-group run tables (mx_param_runs, see the header)
+extern "C" int mx_param_runs_check(const int64_t* seg_len_host, int nseg, const int32_t* run_off_host,
+                                   const int64_t* run_end_host, const float* wd_host, const float* lr_scale_host) {
+    MX_CHECK(seg_len_host && run_off_host && run_end_host && wd_host && lr_scale_host,
+             "mx_param_runs_check: null argument");
+    MX_CHECK(nseg >= 1, "mx_param_runs_check: nseg=%d < 1", nseg);
+    MX_CHECK(run_off_host[0] == 0, "mx_param_runs_check: run_off[0]=%d != 0", run_off_host[0]);
+    for (int s = 0; s < nseg; ++s) {
+        const int a = run_off_host[s], b = run_off_host[s + 1];
+        MX_CHECK(seg_len_host[s] >= 0, "mx_param_runs_check: segment %d has a negative length", s);
+        MX_CHECK(b >= a, "mx_param_runs_check: run_off descends at segment %d", s);
+        if (seg_len_host[s] == 0) {
+            MX_CHECK(b == a, "mx_param_runs_check: segment %d is empty but has runs (an empty run)", s);
+            continue;
+        }
+        MX_CHECK(b > a, "mx_param_runs_check: segment %d has no runs", s);
+        int64_t prev = 0;
+        for (int r = a; r < b; ++r) {
+            const int64_t e = run_end_host[r];
+            MX_CHECK(e != prev, "mx_param_runs_check: run %d of segment %d is empty", r - a, s);
+            MX_CHECK(e > prev, "mx_param_runs_check: run ends of segment %d are not ascending at run %d", s, r - a);
+            prev = e;
+            const float wd = wd_host[r], sc = lr_scale_host[r];
+            // x - x is 0 for finite x only (NaN for NaN and the infinities): no <cmath> needed
+            MX_CHECK(wd >= 0.0f && wd - wd == 0.0f, "mx_param_runs_check: weight decay of run %d of segment %d is "
+                     "negative or not finite", r - a, s);
+            MX_CHECK(sc >= 0.0f && sc - sc == 0.0f, "mx_param_runs_check: lr scale of run %d of segment %d is "
+                     "negative or not finite", r - a, s);
+        }
+        MX_CHECK(prev == seg_len_host[s], "mx_param_runs_check: the last run of segment %d ends at %lld, not at the "
+                 "segment's length %lld", s, (long long)prev, (long long)seg_len_host[s]);
+    }
+    return MX_OK;
+}

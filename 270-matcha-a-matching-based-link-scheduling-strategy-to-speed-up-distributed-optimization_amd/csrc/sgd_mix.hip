@@ -27,6 +27,7 @@
 #include "mx_common.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 constexpr int kTPB = 256;
@@ -119,6 +120,66 @@ __device__ __forceinline__ F4 sgd4(const F4& x, const F4& g, F4& m, float nlr, c
     return out;
 }
 
+// Per-parameter-group launches (mx_sgd_mix_grouped): the columns of a segment are cut into runs that
+// each carry their own weight decay and learning-rate scale (mx_param_runs; the tables are read when
+// the kernel runs).  Element of run r: lr_r = fmul(lr, s_r), then the update above with wd -> wd_r and
+// lr -> lr_r.  The ungrouped instantiations carry none of this: their argument block is Hyper alone.
+struct Runs {
+    const int32_t* off;    // int32 [nseg + 1]: segment s owns runs [off[s], off[s + 1])
+    const int64_t* end;    // int64 [nruns]: exclusive end column within the segment, ascending
+    const float* wd;       // float [nruns]
+    const float* scale;    // float [nruns]
+};
+struct HyperG : Hyper {
+    Runs rn;
+};
+template <bool GROUPED>
+using HyperOf = std::conditional_t<GROUPED, HyperG, Hyper>;
+
+// sgd4's update of one element with the run's own decay and (negated) learning rate
+template <bool MOM>
+__device__ __forceinline__ float sgd1(float x, float g, float& m, float nlr, float wd, const Hyper& h) {
+    float d = wd != 0.0f ? __builtin_fmaf(wd, x, g) : g;
+    if constexpr (MOM) {
+        const float scaled = h.mom * m;
+        m = scaled + d;
+        d = h.nesterov ? __builtin_fmaf(h.mom, m, d) : m;
+    }
+    return __builtin_fmaf(nlr, d, x);
+}
+
+// a chunk that lies in one run (the whole work item does): the run's constants are scalars
+template <bool MOM>
+__device__ __forceinline__ F4 sgd4_run(const F4& x, const F4& g, F4& m, float nlr, float wd, const Hyper& h) {
+    F4 out;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        float mt = MOM ? m[t] : 0.0f;
+        out[t] = sgd1<MOM>(x[t], g[t], mt, nlr, wd, h);
+        if constexpr (MOM) m[t] = mt;
+    }
+    return out;
+}
+
+// a chunk of a work item that holds a run boundary: every element walks forward from the work item's
+// first run `r` to its own (a chunk may span four runs) and derives its constants itself.  The walk
+// stops at the segment's last run, so columns at or past the segment's length (zero-filled, never
+// stored) read inside the tables.
+template <bool MOM>
+__device__ __forceinline__ F4 sgd4_walk(const F4& x, const F4& g, F4& m, int64_t c, int r, int rhi, float lr,
+                                        const HyperG& h) {
+    F4 out;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        while (r + 1 < rhi && h.rn.end[r] <= c + t) ++r;
+        const float lr_r = lr * h.rn.scale[r];                       // one rounding; scale 1.0 gives lr
+        float mt = MOM ? m[t] : 0.0f;
+        out[t] = sgd1<MOM>(x[t], g[t], mt, -lr_r, h.rn.wd[r], h);
+        if constexpr (MOM) m[t] = mt;
+    }
+    return out;
+}
+
 template <int NS>
 struct PlanLds {
     int32_t w[mx::kPlanHeader + 2 * NS + NS * kMaxM];
@@ -133,7 +194,8 @@ __device__ __forceinline__ int64_t round_of(int64_t iter, const int64_t* iter_de
 }
 
 // NS rows x TW columns per work item; a layout tile (mx_sgd_mix_tile) is `split` work items.
-template <int NS, int TW, bool NT, bool MOM>
+// GROUPED: per-run weight decay and learning-rate scale (see Runs above).
+template <int NS, int TW, bool NT, bool MOM, bool GROUPED>
 __global__ __launch_bounds__(kTPB) void sgd_mix_rows(float* const* __restrict__ x_ptrs,
                                                      float* const* __restrict__ g_ptrs,
                                                      float* const* __restrict__ m_ptrs,
@@ -142,7 +204,7 @@ __global__ __launch_bounds__(kTPB) void sgd_mix_rows(float* const* __restrict__ 
                                                      int64_t total_tiles, int split,
                                                      const int32_t* __restrict__ plan, int64_t iter,
                                                      const int64_t* __restrict__ iter_dev, int n_local, int M,
-                                                     float alpha, Hyper h) {
+                                                     float alpha, HyperOf<GROUPED> h) {
     constexpr int C4 = TW / 4;            // 16-byte chunks per row per work item
     constexpr int NQ = TW / 256;          // 256-column passes per row
     constexpr int NI = NS * NQ;           // items per work item (<= 64: one per lane of wave 0)
@@ -161,6 +223,11 @@ __global__ __launch_bounds__(kTPB) void sgd_mix_rows(float* const* __restrict__ 
 
     struct Geo {
         int64_t base, col0, lim;             // base: the segment's row of the pointer tables
+        // GROUPED only: the first run that ends past col0, the end of the segment's runs, whether that
+        // run covers the whole work item, and its pair
+        int r0, rhi;
+        bool uni;
+        float wd, scale;
     };
     auto geo = [&](int64_t work) {
         const int64_t tile = work / split;
@@ -173,6 +240,22 @@ __global__ __launch_bounds__(kTPB) void sgd_mix_rows(float* const* __restrict__ 
         gq.base = (int64_t)lo * n_local;
         gq.col0 = (tile - tile_off[lo]) * ((int64_t)TW * split) + (work % split) * TW;
         gq.lim = seg_len[lo];
+        gq.r0 = gq.rhi = 0;
+        gq.uni = true;
+        gq.wd = gq.scale = 0.0f;
+        if constexpr (GROUPED) {
+            int a = h.rn.off[lo], b = h.rn.off[lo + 1];
+            gq.rhi = b;
+            while (a < b) {                  // wave-uniform: the first run with end > col0
+                const int mid = (a + b) >> 1;
+                if (h.rn.end[mid] <= gq.col0) a = mid + 1; else b = mid;
+            }
+            gq.r0 = a < gq.rhi ? a : gq.rhi - 1;             // a work item wholly past the segment's length
+            const int64_t last = gq.col0 + TW < gq.lim ? gq.col0 + TW : gq.lim;
+            gq.uni = h.rn.end[gq.r0] >= last;
+            gq.wd = h.rn.wd[gq.r0];
+            gq.scale = h.rn.scale[gq.r0];
+        }
         return gq;
     };
     // 16-byte accesses only where x, g and m of the (segment, row) are all 16-byte aligned
@@ -218,6 +301,8 @@ __global__ __launch_bounds__(kTPB) void sgd_mix_rows(float* const* __restrict__ 
     // other row stores x' as it is
     auto mixes = [&](int r) { return active && (deg[r] > 0 || idle); };
     auto degree = [&](int r) { return mixes(r) ? deg[r] : 0; };
+    // GROUPED: the launch's learning rate; the parked work item's -lr_r is derived in park from its own
+    // Geo, never from the prefetched one's
     const float nlr = -(h.lr_dev ? *h.lr_dev : h.lr);
 
     // deal the items (row r, pass q) = r * NQ + q to the waves: wave 0 ranks them by weight
@@ -249,7 +334,12 @@ __global__ __launch_bounds__(kTPB) void sgd_mix_rows(float* const* __restrict__ 
                 const int64_t c = gq.col0 + (int64_t)(at % C4 + lane) * 4;
                 const bool vec = vec_of(gq, k);
                 const F4 g = h.gscale ? scale4(G[t], h.gscale[k]) : G[t];
-                lds[at + lane] = sgd4<MOM>(X[t], g, Mv[t], nlr, h);
+                if constexpr (GROUPED) {
+                    lds[at + lane] = gq.uni ? sgd4_run<MOM>(X[t], g, Mv[t], -(-nlr * gq.scale), gq.wd, h)
+                                            : sgd4_walk<MOM>(X[t], g, Mv[t], c, gq.r0, gq.rhi, -nlr, h);
+                } else {
+                    lds[at + lane] = sgd4<MOM>(X[t], g, Mv[t], nlr, h);
+                }
                 if constexpr (MOM) store_chunk<NT>(m_ptrs[gq.base + k], c, gq.lim, vec, Mv[t]);
                 if (h.zero_grads) store_chunk<NT>(g_ptrs[gq.base + k], c, gq.lim, vec, F4{0.0f, 0.0f, 0.0f, 0.0f});
             }
@@ -356,10 +446,11 @@ struct Args {
     int64_t iter;
     const int64_t* iter_dev;
     Hyper h;
+    Runs rn;
     hipStream_t st;
 };
 
-template <int NS, int TW, bool NT, bool MOM>
+template <int NS, int TW, bool NT, bool MOM, bool GROUPED>
 int launch(const Args& a) {
     const mx_sgd_mix_call* c = a.c;
     const int split = pick(c->n_local).tile / TW;
@@ -373,20 +464,23 @@ int launch(const Args& a) {
     if (flat && g_tune.wgpc > 0) {
         static const int stat = [] {                           // static LDS of this instantiation
             hipFuncAttributes fa{};
-            return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(sgd_mix_rows<NS, TW, NT, MOM>)) == hipSuccess
+            return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(sgd_mix_rows<NS, TW, NT, MOM, GROUPED>)) == hipSuccess
                        ? (int)fa.sharedSizeBytes : 0;
         }();
         pad = mx::lds_cap_pad(stat, g_tune.wgpc);
     }
-    hipLaunchKernelGGL((sgd_mix_rows<NS, TW, NT, MOM>), dim3((unsigned)grid), dim3(kTPB), pad, a.st, c->x_ptrs_dev,
+    HyperOf<GROUPED> hy;
+    static_cast<Hyper&>(hy) = a.h;
+    if constexpr (GROUPED) hy.rn = a.rn;
+    hipLaunchKernelGGL((sgd_mix_rows<NS, TW, NT, MOM, GROUPED>), dim3((unsigned)grid), dim3(kTPB), pad, a.st, c->x_ptrs_dev,
                        c->g_ptrs_dev, c->m_ptrs_dev, c->seg_len_dev, c->tile_off_dev, c->nseg, c->total_tiles, split,
-                       c->plan_dev, a.iter, a.iter_dev, c->n_local, c->M, c->alpha, a.h);
+                       c->plan_dev, a.iter, a.iter_dev, c->n_local, c->M, c->alpha, hy);
     MX_LAUNCH_CHECK();
     return MX_OK;
 }
 
-int sgd_mix(const mx_sgd_mix_call* c, const float* gscale, int64_t iter, const int64_t* iter_dev, float lr,
-            const float* lr_dev, void* stream, const char* who) {
+int sgd_mix(const mx_sgd_mix_call* c, const mx_param_runs* runs, const float* gscale, int64_t iter,
+            const int64_t* iter_dev, float lr, const float* lr_dev, void* stream, const char* who) {
     MX_CHECK(c, "%s: null call record", who);
     MX_CHECK(c->x_ptrs_dev && c->g_ptrs_dev && c->seg_len_dev && c->tile_off_dev && c->plan_dev,
              "%s: null pointer", who);
@@ -399,6 +493,8 @@ int sgd_mix(const mx_sgd_mix_call* c, const float* gscale, int64_t iter, const i
     MX_CHECK((c->mom != 0.0f) == (c->m_ptrs_dev != nullptr), "%s: the momentum table is given exactly when mom != 0",
              who);
     MX_CHECK(c->mom != 0.0f || !c->nesterov, "%s: nesterov needs momentum", who);
+    MX_CHECK(!runs || (runs->run_off_dev && runs->run_end_dev && runs->wd_dev && runs->lr_scale_dev && runs->nruns >= 1),
+             "%s: parameter runs with a null table or nruns < 1", who);
     if (c->total_tiles <= 0) return MX_OK;
     const Cls cl = pick(c->n_local);
     const bool mom = c->mom != 0.0f;
@@ -407,10 +503,12 @@ int sgd_mix(const mx_sgd_mix_call* c, const float* gscale, int64_t iter, const i
     const bool nt = g_tune.nontemporal == 2 ? (ws <= ((int64_t)32 << 20) || ws > ((int64_t)320 << 20))
                                             : g_tune.nontemporal != 0;
     const Args a{c, iter, iter_dev, Hyper{lr, c->wd, c->mom, lr_dev, gscale, c->nesterov != 0, c->zero_grads != 0},
+                 runs ? Runs{runs->run_off_dev, runs->run_end_dev, runs->wd_dev, runs->lr_scale_dev} : Runs{},
                  mx::as_stream(stream)};
-#define MX_SGD(N, TW)                                                                              \
-    (nt ? (mom ? launch<N, TW, true, true>(a) : launch<N, TW, true, false>(a))                     \
-        : (mom ? launch<N, TW, false, true>(a) : launch<N, TW, false, false>(a)))
+#define MX_SGD_G(N, TW, G)                                                                         \
+    (nt ? (mom ? launch<N, TW, true, true, G>(a) : launch<N, TW, true, false, G>(a))               \
+        : (mom ? launch<N, TW, false, true, G>(a) : launch<N, TW, false, false, G>(a)))
+#define MX_SGD(N, TW) (runs ? MX_SGD_G(N, TW, true) : MX_SGD_G(N, TW, false))
     switch (cl.ns) {
         case 8: return MX_SGD(8, 512);
         case 16: return MX_SGD(16, 512);
@@ -418,6 +516,7 @@ int sgd_mix(const mx_sgd_mix_call* c, const float* gscale, int64_t iter, const i
         default: return MX_SGD(64, 256);
     }
 #undef MX_SGD
+#undef MX_SGD_G
 }
 }  // namespace
 
@@ -469,22 +568,34 @@ extern "C" int mx_sgd_mix_get(const char* key) {
 }
 
 extern "C" int mx_sgd_mix(const mx_sgd_mix_call* c, int64_t iter, float lr, const float* lr_dev, void* stream) {
-    return sgd_mix(c, nullptr, iter, nullptr, lr, lr_dev, stream, "mx_sgd_mix");
+    return sgd_mix(c, nullptr, nullptr, iter, nullptr, lr, lr_dev, stream, "mx_sgd_mix");
 }
 
 extern "C" int mx_sgd_mix_scaled(const mx_sgd_mix_call* c, const float* gscale_dev, int64_t iter, float lr,
                                  const float* lr_dev, void* stream) {
-    return sgd_mix(c, gscale_dev, iter, nullptr, lr, lr_dev, stream, "mx_sgd_mix_scaled");
+    return sgd_mix(c, nullptr, gscale_dev, iter, nullptr, lr, lr_dev, stream, "mx_sgd_mix_scaled");
 }
 
 extern "C" int mx_sgd_mix_at(const mx_sgd_mix_call* c, const int64_t* iter_dev, int64_t n_iters, float lr,
                              const float* lr_dev, void* stream) {
     MX_CHECK(iter_dev, "mx_sgd_mix_at: null iteration counter");
-    return sgd_mix(c, nullptr, n_iters, iter_dev, lr, lr_dev, stream, "mx_sgd_mix_at");
+    return sgd_mix(c, nullptr, nullptr, n_iters, iter_dev, lr, lr_dev, stream, "mx_sgd_mix_at");
 }
 
 extern "C" int mx_sgd_mix_scaled_at(const mx_sgd_mix_call* c, const float* gscale_dev, const int64_t* iter_dev,
                                     int64_t n_iters, float lr, const float* lr_dev, void* stream) {
     MX_CHECK(iter_dev, "mx_sgd_mix_scaled_at: null iteration counter");
-    return sgd_mix(c, gscale_dev, n_iters, iter_dev, lr, lr_dev, stream, "mx_sgd_mix_scaled_at");
+    return sgd_mix(c, nullptr, gscale_dev, n_iters, iter_dev, lr, lr_dev, stream, "mx_sgd_mix_scaled_at");
+}
+
+extern "C" int mx_sgd_mix_grouped(const mx_sgd_mix_call* c, const mx_param_runs* runs, const float* gscale_dev,
+                                  int64_t iter, float lr, const float* lr_dev, void* stream) {
+    return sgd_mix(c, runs, gscale_dev, iter, nullptr, lr, lr_dev, stream, "mx_sgd_mix_grouped");
+}
+
+extern "C" int mx_sgd_mix_grouped_at(const mx_sgd_mix_call* c, const mx_param_runs* runs, const float* gscale_dev,
+                                     const int64_t* iter_dev, int64_t n_iters, float lr, const float* lr_dev,
+                                     void* stream) {
+    MX_CHECK(iter_dev, "mx_sgd_mix_grouped_at: null iteration counter");
+    return sgd_mix(c, runs, gscale_dev, n_iters, iter_dev, lr, lr_dev, stream, "mx_sgd_mix_grouped_at");
 }

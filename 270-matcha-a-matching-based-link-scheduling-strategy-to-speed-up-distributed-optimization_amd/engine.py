@@ -146,6 +146,158 @@ def clip_value(clip_grad_norm, who):
     return v
 
 
+class ParamShape:
+    """What a param_groups predicate sees for a parameter known by its shape only (param_runs on the host)."""
+
+    def __init__(self, shape):
+        self.shape = tuple(int(d) for d in shape)
+        self.ndim = len(self.shape)
+
+    def numel(self):
+        return int(math.prod(self.shape))
+
+    def dim(self):
+        return self.ndim
+
+
+PARAM_GROUP_KEYS = ("params", "columns", "weight_decay", "lr_scale")
+
+
+def _group_value(v, what):
+    """A weight decay or lr scale of a parameter group: the fp32 rounding of a finite Python float >= 0."""
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"param_groups: {what} must be a finite number >= 0") from None
+    with np.errstate(over="ignore", under="ignore"):
+        v32 = float(np.float32(v)) if math.isfinite(v) else v
+    if not (math.isfinite(v32) and v32 >= 0.0):
+        raise ValueError(f"param_groups: {what} must be a finite number >= 0, not {v!r}")
+    return v32
+
+
+def param_runs(numel, named_shapes, param_groups, default_wd):
+    """Resolve torch-style parameter groups to the run list of the fused launches (mx_param_runs):
+    [(start, end, weight_decay, lr_scale), ...], half-open column ranges that cover [0, numel) in
+    order, adjacent ranges with equal pairs merged.  A pure host function.
+
+    numel         -- columns of a worker row
+    named_shapes  -- [(name, parameter or shape), ...] in the order the row is laid out
+                     (models[0].named_parameters()), or None for a group built from numel alone
+    param_groups  -- a list of dicts with exactly one selector each:
+                       "params":  a list of names, or a predicate fn(name, param) -> bool (param is what
+                                  named_shapes carries; a bare shape is wrapped as a ParamShape)
+                       "columns": a list of half-open (start, end) column ranges
+                     and optionally "weight_decay" (default: default_wd) and "lr_scale" (default 1.0);
+                     columns no group selects take the defaults
+    ValueError: overlapping groups, an unknown name, an empty or out-of-range column range, a negative
+    or non-finite value, an unknown key, no or two selectors, "params" without named_shapes, and
+    named_shapes that do not add up to numel."""
+    numel = int(numel)
+    if numel < 1:
+        raise ValueError(f"param_runs: numel={numel} < 1")
+    default = (_group_value(default_wd, "the default weight_decay"), 1.0)
+    spans = None
+    if named_shapes is not None:
+        spans, off = {}, 0
+        order = []
+        for name, par in named_shapes:
+            if not hasattr(par, "shape"):
+                par = ParamShape(par)
+            k = int(math.prod(tuple(par.shape)))
+            if name in spans:
+                raise ValueError(f"param_runs: parameter name {name!r} appears twice")
+            spans[name] = (off, off + k)
+            order.append((name, par))
+            off += k
+        if off != numel:
+            raise ValueError(f"param_runs: the named parameters hold {off} elements, the row {numel}")
+    pieces = []                              # (start, end, wd, scale) of every selected range
+    for gi, g in enumerate(param_groups):
+        if not isinstance(g, dict):
+            raise ValueError(f"param_groups[{gi}]: a group is a dict")
+        for key in g:
+            if key not in PARAM_GROUP_KEYS:
+                raise ValueError(f"param_groups[{gi}]: unknown key {key!r} (known: {', '.join(PARAM_GROUP_KEYS)})")
+        if ("params" in g) == ("columns" in g):
+            raise ValueError(f"param_groups[{gi}]: give exactly one of 'params' and 'columns'")
+        pair = (_group_value(g.get("weight_decay", default[0]), f"weight_decay of group {gi}"),
+                _group_value(g.get("lr_scale", 1.0), f"lr_scale of group {gi}"))
+        if "params" in g:
+            if spans is None:
+                raise ValueError(f"param_groups[{gi}]: 'params' needs a group built from models; a numel-only "
+                                 "group selects by 'columns'")
+            sel = g["params"]
+            if callable(sel):
+                names = [name for name, par in order if sel(name, par)]
+            else:
+                names = list(sel)
+                for name in names:
+                    if name not in spans:
+                        raise ValueError(f"param_groups[{gi}]: unknown parameter name {name!r}")
+            ranges = [spans[name] for name in names]
+            ranges = [r for r in ranges if r[1] > r[0]]          # a parameter without elements selects nothing
+        else:
+            ranges = []
+            for rg in g["columns"]:
+                try:
+                    a, b = (int(v) for v in rg)
+                except (TypeError, ValueError):
+                    raise ValueError(f"param_groups[{gi}]: a column range is a (start, end) pair") from None
+                if not (0 <= a < b <= numel):
+                    raise ValueError(f"param_groups[{gi}]: column range [{a}, {b}) is empty or outside [0, {numel})")
+                ranges.append((a, b))
+        pieces += [(a, b) + pair for a, b in ranges]
+    pieces.sort(key=lambda t: (t[0], t[1]))
+    runs, at = [], 0
+
+    def push(a, b, pair):
+        if runs and runs[-1][2:] == pair:
+            runs[-1] = (runs[-1][0], b) + pair
+        else:
+            runs.append((a, b) + pair)
+
+    for a, b, wd, sc in pieces:
+        if a < at:
+            raise ValueError(f"param_groups: columns [{a}, {min(b, at)}) are selected twice (overlapping groups)")
+        if a > at:
+            push(at, a, default)
+        push(a, b, (wd, sc))
+        at = b
+    if at < numel:
+        push(at, numel, default)
+    return runs
+
+
+class ParamRunsRec(ctypes.Structure):
+    """mx_param_runs (include/matcha_gossip.h): the run tables of a grouped fused launch."""
+    _fields_ = [("run_off_dev", ctypes.c_void_p), ("run_end_dev", ctypes.c_void_p), ("wd_dev", ctypes.c_void_p),
+                ("lr_scale_dev", ctypes.c_void_p), ("nruns", ctypes.c_int32)]
+
+
+class ParamRuns:
+    """The device tables of a run list (param_runs) over ONE segment of `numel` columns, checked by
+    mx_param_runs_check on the host before they are uploaded, and the record the _grouped entry points
+    take.  Built once by attach_sgd / attach_adamw(param_groups=...); keeps the tables alive."""
+
+    def __init__(self, numel, runs):
+        self.runs = list(runs)
+        seg_len = np.asarray([int(numel)], dtype=np.int64)
+        off = np.asarray([0, len(self.runs)], dtype=np.int32)
+        end = np.asarray([r[1] for r in self.runs], dtype=np.int64)
+        wd = np.asarray([r[2] for r in self.runs], dtype=np.float32)
+        scale = np.asarray([r[3] for r in self.runs], dtype=np.float32)
+        check(lib.mx_param_runs_check(seg_len.ctypes.data, 1, off.ctypes.data, end.ctypes.data, wd.ctypes.data,
+                                      scale.ctypes.data), "mx_param_runs_check")
+        self.run_off = torch.from_numpy(off).cuda()
+        self.run_end = torch.from_numpy(end).cuda()
+        self.wd = torch.from_numpy(wd).cuda()
+        self.lr_scale = torch.from_numpy(scale).cuda()
+        self.rec = ParamRunsRec(self.run_off.data_ptr(), self.run_end.data_ptr(), self.wd.data_ptr(),
+                                self.lr_scale.data_ptr(), len(self.runs))
+        self.addr = ctypes.addressof(self.rec)
+
+
 ADAM_BIAS_MAX = 1 << 21     # entries (16 MB): reached at beta2 ~ 0.99999
 
 
@@ -1114,6 +1266,9 @@ class VirtualWorkerGroup:
         self.master_arena = self.master_rows = None   # attach_sgd(master_weights=True): fp32 masters of bf16 rows
         self._adamw = None                   # attach_adamw: the fused AdamW + mixing launch's state
         self._clip = None                    # attach_*(clip_grad_norm=...): the norm launch's state (GradNorm)
+        self._runs = None                    # attach_*(param_groups=...): the run tables (ParamRuns)
+        self.param_runs = None               # ... and the merged run list [(start, end, weight_decay, lr_scale)]
+        self._named = list(models[0].named_parameters()) if models is not None else None
         self.clip_grad_norm = None
         self.grad_norms = self.grad_scales = None
         self._round_ctrs = {}                # device_rounds(K): per-round counters, one tensor per K
@@ -1320,6 +1475,18 @@ class VirtualWorkerGroup:
         self._clip = GradNorm([self.numel], lay, self.grad_arena.element_size(), clip)
         self.grad_norms, self.grad_scales = self._clip.norms, self._clip.scales
 
+    def _attach_groups(self, param_groups, default_wd, who):
+        """attach_*(param_groups=...): None keeps the ungrouped launches (no tables); otherwise the
+        groups are resolved (param_runs), checked and uploaded once"""
+        if param_groups is None:
+            return
+        try:
+            runs = param_runs(self.numel, self._named, list(param_groups), default_wd)
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}") from None
+        self._runs = ParamRuns(self.numel, runs)
+        self.param_runs = runs
+
     def grad_norm(self, stream=None):
         """Enqueue the norm launches alone (csrc/grad_norm.hip) and return `grad_norms`: every worker's
         gradient 2-norm, fp32 CUDA [n_local], valid once the stream reaches it; `grad_scales` holds the
@@ -1330,7 +1497,7 @@ class VirtualWorkerGroup:
         return self.grad_norms
 
     def attach_sgd(self, momentum=0.0, weight_decay=0.0, nesterov=False, zero_grads=True, master_weights=False,
-                   clip_grad_norm=None):
+                   clip_grad_norm=None, param_groups=None):
         """Give the group torch.optim.SGD's state (dampening 0) so that one launch per iteration
         applies every worker's update and the round's mix (csrc/sgd_mix.hip; the reference's
         optimizer.step() + zero_grad() + communicate(), train_mpi.py:131-142).
@@ -1363,7 +1530,19 @@ class VirtualWorkerGroup:
         (fp32 CUDA [n_local]) holds the norms BEFORE clipping -- what torch's function returns -- and
         `grad_scales` the factors, after every step and after grad_norm().  Unlike torch, the gradients
         in memory are never rewritten scaled: they are zeroed under zero_grads and otherwise left as
-        backward wrote them.  Clipping has no state: checkpoints are unchanged and load either way."""
+        backward wrote them.  Clipping has no state: checkpoints are unchanged and load either way.
+
+        param_groups=[{...}, ...] is torch.optim's param_groups for the two hyperparameters recipes
+        vary per parameter: every group selects parameters ("params": names of
+        models[0].named_parameters(), or a predicate fn(name, param) -> bool) or columns ("columns":
+        half-open ranges, the only selector of a numel-only group) and gives them their own
+        "weight_decay" (default: this call's) and / or "lr_scale" (default 1.0: the step's learning
+        rate is multiplied by it, one fp32 rounding).  Columns no group selects take this call's
+        values.  See param_runs for the errors.  The groups are resolved once to column runs
+        (`param_runs`: [(start, end, weight_decay, lr_scale)]) whose tables live on the device, and
+        every step then goes through the _grouped entry points; None keeps today's launches.  Groups
+        are hyperparameters, not state: checkpoints are unchanged.  Momentum, nesterov and the clip
+        norm (one per worker over all its groups) are the whole row's."""
         clip = clip_value(clip_grad_norm, "attach_sgd")
         if self._sgd is not None:
             raise RuntimeError("attach_sgd: already attached")
@@ -1407,6 +1586,7 @@ class VirtualWorkerGroup:
         else:
             lay = SgdLayout([self.numel], [[p] for p in self._row_ptrs], row_ptrs(self.grad_arena),
                             row_ptrs(self.mom_arena) if momentum != 0.0 else None, self.n_local)
+        self._attach_groups(param_groups, weight_decay, "attach_sgd")
         call = lay.call(self.engine, weight_decay, momentum, nesterov, zero_grads)
         if self._adopted is not None:
             for r, m in enumerate(self._adopted):
@@ -1418,11 +1598,15 @@ class VirtualWorkerGroup:
         self.lr_dev = torch.zeros(1, dtype=torch.float32, device="cuda")   # sgd_device_round's learning rate
         self.sgd_hyper = {"momentum": momentum, "weight_decay": weight_decay, "nesterov": bool(nesterov),
                           "zero_grads": bool(zero_grads)}
+        if self.param_runs is not None:      # groups are hyperparameters too; without them the dict is as before
+            self.sgd_hyper["param_groups"] = self.param_runs
         self._sgd = (lay, call, ctypes.addressof(call))
         self._sgd_fn = (_sgd_mix_bf16, lib.mx_sgd_mix_bf16_at, "mx_sgd_mix_bf16") if mixed else \
                        (_sgd_mix, lib.mx_sgd_mix_at, "mx_sgd_mix")
         self._sgd_fn_scaled = (lib.mx_sgd_mix_bf16_scaled, lib.mx_sgd_mix_bf16_scaled_at) if mixed else \
                               (lib.mx_sgd_mix_scaled, lib.mx_sgd_mix_scaled_at)
+        self._sgd_fn_grouped = (lib.mx_sgd_mix_bf16_grouped, lib.mx_sgd_mix_bf16_grouped_at) if mixed else \
+                               (lib.mx_sgd_mix_grouped, lib.mx_sgd_mix_grouped_at)
         self._attach_clip(lay, clip)
 
     def master_from_rows(self):
@@ -1448,7 +1632,13 @@ class VirtualWorkerGroup:
         alone -- and returns whether the round mixed."""
         call = self._sgd_state()
         it = self.engine.round_index(it)
-        if self._clip is not None:               # the norm launches, then the launch that applies the factors
+        if self._runs is not None:               # per-group decay / lr scale (with the clip factors, if any)
+            s = stream_ptr(stream)
+            if self._clip is not None:
+                self._clip.enqueue(s)
+            rc = self._sgd_fn_grouped[0](call, self._runs.addr, self._clip.scale_ptr if self._clip else None, it, lr,
+                                         None, s)
+        elif self._clip is not None:             # the norm launches, then the launch that applies the factors
             s = stream_ptr(stream)
             self._clip.enqueue(s)
             rc = self._sgd_fn_scaled[0](call, self._clip.scale_ptr, it, lr, None, s)
@@ -1465,7 +1655,13 @@ class VirtualWorkerGroup:
         counter outside the schedule makes the launch a no-op: no SGD step either."""
         call = self._sgd_state()
         s = stream_ptr(stream)
-        if self._clip is not None:
+        if self._runs is not None:
+            if self._clip is not None:
+                self._clip.enqueue(s)
+            check(self._sgd_fn_grouped[1](call, self._runs.addr, self._clip.scale_ptr if self._clip else None,
+                                          self.iter_dev.data_ptr(), self.engine.T, 0.0, self.lr_dev.data_ptr(), s),
+                  self._sgd_fn[2] + "_grouped_at")
+        elif self._clip is not None:
             self._clip.enqueue(s)
             check(self._sgd_fn_scaled[1](call, self._clip.scale_ptr, self.iter_dev.data_ptr(), self.engine.T, 0.0,
                                          self.lr_dev.data_ptr(), s), self._sgd_fn[2] + "_scaled_at")
@@ -1487,7 +1683,7 @@ class VirtualWorkerGroup:
 
     # ------------------------------------------------------------------ fused AdamW + mixing
     def attach_adamw(self, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled=True, zero_grads=True,
-                     master_weights=False, clip_grad_norm=None):
+                     master_weights=False, clip_grad_norm=None, param_groups=None):
         """Give the group torch.optim.AdamW's state (decoupled=False: torch.optim.Adam's, the decay as
         an L2 term in the gradient; no amsgrad, no maximize) so that one launch per iteration applies
         every worker's update and the round's mix (csrc/adamw_mix.hip).
@@ -1510,7 +1706,13 @@ class VirtualWorkerGroup:
         clip_grad_norm=X is attach_sgd's: torch.nn.utils.clip_grad_norm_(model.parameters(), X) per
         worker as one extra read of the gradient arena; exp_avg and exp_avg_sq see the clipped
         gradient, `grad_norms` / `grad_scales` hold the pre-clip norms and the factors, and the
-        gradients in memory are never rewritten scaled."""
+        gradients in memory are never rewritten scaled.
+
+        param_groups=[{...}, ...] is attach_sgd's: per-group "weight_decay" (default: this call's) and
+        "lr_scale" over parameters selected by name, by predicate or by column range -- the usual
+        "no decay for biases and normalisation scales" is
+        [{"params": lambda name, p: p.ndim <= 1, "weight_decay": 0.0}].  Betas and eps are the whole
+        row's.  `param_runs` holds the resolved runs; None keeps today's launches."""
         clip = clip_value(clip_grad_norm, "attach_adamw")
         if self._adamw is not None:
             raise RuntimeError("attach_adamw: already attached")
@@ -1558,6 +1760,7 @@ class VirtualWorkerGroup:
         else:
             lay = AdamwLayout([self.numel], [[p] for p in self._row_ptrs], row_ptrs(self.grad_arena),
                               row_ptrs(self.exp_avg_arena), row_ptrs(self.exp_avg_sq_arena), self.n_local, bias)
+        self._attach_groups(param_groups, weight_decay, "attach_adamw")
         call = lay.call(self.engine, betas, eps, weight_decay, decoupled, zero_grads)
         if self._adopted is not None:
             for r, m in enumerate(self._adopted):
@@ -1571,11 +1774,15 @@ class VirtualWorkerGroup:
         self.opt_step_dev = torch.ones(1, dtype=torch.int64, device="cuda")
         self.adamw_hyper = {"betas": betas, "eps": eps, "weight_decay": weight_decay, "decoupled": bool(decoupled),
                             "zero_grads": bool(zero_grads)}
+        if self.param_runs is not None:      # groups are hyperparameters too; without them the dict is as before
+            self.adamw_hyper["param_groups"] = self.param_runs
         self._adamw = (lay, call, ctypes.addressof(call))
         self._adamw_fn = (_adamw_mix_bf16, lib.mx_adamw_mix_bf16_at, "mx_adamw_mix_bf16") if mixed else \
                          (_adamw_mix, lib.mx_adamw_mix_at, "mx_adamw_mix")
         self._adamw_fn_scaled = (lib.mx_adamw_mix_bf16_scaled, lib.mx_adamw_mix_bf16_scaled_at) if mixed else \
                                 (lib.mx_adamw_mix_scaled, lib.mx_adamw_mix_scaled_at)
+        self._adamw_fn_grouped = (lib.mx_adamw_mix_bf16_grouped, lib.mx_adamw_mix_bf16_grouped_at) if mixed else \
+                                 (lib.mx_adamw_mix_grouped, lib.mx_adamw_mix_grouped_at)
         self._attach_clip(lay, clip)
 
     def _adamw_state(self):
@@ -1590,7 +1797,13 @@ class VirtualWorkerGroup:
         all-zero round is the optimizer step alone -- and returns whether the round mixed."""
         call = self._adamw_state()
         it = self.engine.round_index(it)
-        if self._clip is not None:               # the norm launches, then the launch that applies the factors
+        if self._runs is not None:               # per-group decay / lr scale (with the clip factors, if any)
+            s = stream_ptr(stream)
+            if self._clip is not None:
+                self._clip.enqueue(s)
+            rc = self._adamw_fn_grouped[0](call, self._runs.addr, self._clip.scale_ptr if self._clip else None, it,
+                                           self.opt_step + 1, lr, None, s)
+        elif self._clip is not None:             # the norm launches, then the launch that applies the factors
             s = stream_ptr(stream)
             self._clip.enqueue(s)
             rc = self._adamw_fn_scaled[0](call, self._clip.scale_ptr, it, self.opt_step + 1, lr, None, s)
@@ -1610,7 +1823,13 @@ class VirtualWorkerGroup:
         touched."""
         call = self._adamw_state()
         s = stream_ptr(stream)
-        if self._clip is not None:
+        if self._runs is not None:
+            if self._clip is not None:
+                self._clip.enqueue(s)
+            check(self._adamw_fn_grouped[1](call, self._runs.addr, self._clip.scale_ptr if self._clip else None,
+                                            self.iter_dev.data_ptr(), self.engine.T, self.opt_step_dev.data_ptr(), 0.0,
+                                            self.lr_dev.data_ptr(), s), self._adamw_fn[2] + "_grouped_at")
+        elif self._clip is not None:
             self._clip.enqueue(s)
             check(self._adamw_fn_scaled[1](call, self._clip.scale_ptr, self.iter_dev.data_ptr(), self.engine.T,
                                            self.opt_step_dev.data_ptr(), 0.0, self.lr_dev.data_ptr(), s),

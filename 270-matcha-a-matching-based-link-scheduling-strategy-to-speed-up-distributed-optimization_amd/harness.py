@@ -197,7 +197,7 @@ class VirtualTrainer:
     step for all workers is a handful of batched launches plus the gossip kernel."""
 
     def __init__(self, args, model_fn, n_batches, device="cuda", batched=False, graph=False, fused_sgd=False,
-                 fused_adamw=False, adamw_hyper=None, clip_grad_norm=None):
+                 fused_adamw=False, adamw_hyper=None, clip_grad_norm=None, param_groups=None):
         """fused_sgd=True (non-batched, uncompressed): the workers' optimizer.step() /
         zero_grad() and the gossip round run as ONE launch (VirtualWorkerGroup.attach_sgd /
         sgd_communicate, csrc/sgd_mix.hip): backward() accumulates into the group's gradient arena,
@@ -219,6 +219,11 @@ class VirtualTrainer:
         gradient arena, csrc/grad_norm.hip).  `grad_norm_log` collects every round's pre-clip norms
         (a float32 CPU tensor [size] per round) and the epoch stats carry each worker's last one.  The
         other paths keep torch's optimizers and do not clip: asking for it there is a ValueError.
+
+        param_groups=[{...}, ...] (with fused_sgd or fused_adamw): attach_sgd / attach_adamw's keyword,
+        per-group weight decay and learning-rate scale inside the fused step (e.g. no decay for biases
+        and normalisation scales: [{"params": lambda name, p: p.ndim <= 1, "weight_decay": 0.0}]).
+        A ValueError on the other paths, whose torch optimizers are built with one group.
 
         graph=True (with batched=True, decentralized gossip, one GPU): once the learning rate
         is constant within an epoch, the whole training iteration -- vmap'd forward / backward,
@@ -244,6 +249,9 @@ class VirtualTrainer:
         if clip_grad_norm is not None and not (self.fused_sgd or self.fused_adamw):
             raise ValueError("clip_grad_norm is honoured by the fused optimizer steps only (fused_sgd=True or "
                              "fused_adamw=True): the other paths step torch's optimizers and do not clip")
+        if param_groups is not None and not (self.fused_sgd or self.fused_adamw):
+            raise ValueError("param_groups is honoured by the fused optimizer steps only (fused_sgd=True or "
+                             "fused_adamw=True): the other paths step torch's optimizers with one group")
         self.grad_norm_log = []
         self.GP = make_topology(args, 0, size, args.epoch * n_batches)
         self.models = []
@@ -262,12 +270,13 @@ class VirtualTrainer:
         if self.fused_sgd:
             # all-bfloat16 models: fp32 master weights, updated and mixed by the launch (csrc/sgd_mix_bf16.hip)
             self.group.attach_sgd(args.momentum, 5e-4, args.nesterov, master_weights=mixed,
-                                  clip_grad_norm=clip_grad_norm)
+                                  clip_grad_norm=clip_grad_norm, param_groups=param_groups)
         if self.fused_adamw:
             # all-bfloat16 models: fp32 master weights, as above (csrc/adamw_mix_bf16.hip)
             hyper = {"betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 5e-4, "decoupled": True}
             hyper.update(adamw_hyper or {})
-            self.group.attach_adamw(**hyper, master_weights=mixed, clip_grad_norm=clip_grad_norm)
+            self.group.attach_adamw(**hyper, master_weights=mixed, clip_grad_norm=clip_grad_norm,
+                                    param_groups=param_groups)
         sync_rows(self.group.rows)
         if mixed:
             self.group.master_from_rows()                        # the masters of the synchronized rows

@@ -576,6 +576,64 @@ int mx_adamw_mix_bf16_scaled_at(const mx_adamw_mix_bf16_call* call, const float*
                                 const int64_t* iter_dev, int64_t n_iters, const int64_t* step_dev, float lr,
                                 const float* lr_dev, void* stream);
 
+/* ---------------------------------------------------------------- per-parameter-group hyperparameters
+ * torch.optim's param_groups with their own weight_decay and their own learning-rate multiplier, for the
+ * four fused launches above.  The columns [0, seg_len) of every segment are cut into RUNS, half-open
+ * column ranges that share one pair (wd_r, s_r); both are fp32, finite and >= 0.  With lr the launch's
+ * learning rate (the argument, or *lr_dev), every element of run r gets the entry point's update with
+ *   lr_r = fmul(lr, s_r)               one fp32 rounding; s_r = 1.0f gives lr exactly
+ *   wd -> wd_r                         the "wd != 0" tests are made per run
+ *   lr -> lr_r                         SGD:   x' = fmaf(-lr_r, d, x)
+ *                                      AdamW: decay = fmaf(-lr_r, wd_r, 1), ss = fdiv(lr_r, bc1)
+ * and nothing else changes: momentum, betas, eps, the bias table, nesterov, decoupled, zero_grads, the
+ * clip factor (gscale_dev: one norm per worker over all its runs), the mix of the x' values, the launch-side
+ * no-ops and the host-side refusals are the _scaled entry points'.  s_r = 0 freezes the weights of a run
+ * while its optimizer state still advances.  The call record's own wd is ignored.
+ * mx_param_runs, built once and kept alive by the caller; the tables are device memory READ WHEN THE
+ * KERNEL RUNS (a graph-captured launch stays valid when they are rewritten):
+ *   run_off_dev   int32 [nseg + 1]: segment s owns runs [run_off[s], run_off[s + 1])
+ *   run_end_dev   int64 [nruns]: exclusive end column of each run within its segment, strictly ascending
+ *                 per segment, the last equal to the segment's length
+ *   wd_dev, lr_scale_dev   float [nruns]
+ *   nruns         run_off[nseg]
+ * mx_param_runs_check validates HOST copies of the tables before they are uploaded (no GPU needed):
+ * MX_ERR_INVALID with a message for a null argument, nseg < 1, run_off[0] != 0, a segment of positive
+ * length without runs (a zero-length segment has none), an empty run, ends that are not ascending, a last
+ * end that is not the segment's length, and a negative or non-finite wd or scale.  The launches trust the
+ * device tables: they steer arithmetic only, never an address that is written.
+ * mx_*_grouped(call, runs, gscale_dev, ...): runs == NULL is the _scaled entry point bit for bit (and
+ * gscale_dev may be NULL as there); a non-NULL runs with a null table or nruns < 1 is MX_ERR_INVALID,
+ * nothing launched.  A work item (see the kernels) that lies inside one run -- every large tensor -- takes
+ * the run's pair as scalars; one that holds a boundary resolves the run per element. */
+typedef struct mx_param_runs {
+    const int32_t* run_off_dev;
+    const int64_t* run_end_dev;
+    const float* wd_dev;
+    const float* lr_scale_dev;
+    int32_t nruns;
+} mx_param_runs;
+int mx_param_runs_check(const int64_t* seg_len_host, int nseg, const int32_t* run_off_host,
+                        const int64_t* run_end_host, const float* wd_host, const float* lr_scale_host);
+int mx_sgd_mix_grouped(const mx_sgd_mix_call* call, const mx_param_runs* runs, const float* gscale_dev, int64_t iter,
+                       float lr, const float* lr_dev, void* stream);
+int mx_sgd_mix_grouped_at(const mx_sgd_mix_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                          const int64_t* iter_dev, int64_t n_iters, float lr, const float* lr_dev, void* stream);
+int mx_sgd_mix_bf16_grouped(const mx_sgd_mix_bf16_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                            int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_sgd_mix_bf16_grouped_at(const mx_sgd_mix_bf16_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                               const int64_t* iter_dev, int64_t n_iters, float lr, const float* lr_dev,
+                               void* stream);
+int mx_adamw_mix_grouped(const mx_adamw_mix_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                         int64_t iter, int64_t step, float lr, const float* lr_dev, void* stream);
+int mx_adamw_mix_grouped_at(const mx_adamw_mix_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                            const int64_t* iter_dev, int64_t n_iters, const int64_t* step_dev, float lr,
+                            const float* lr_dev, void* stream);
+int mx_adamw_mix_bf16_grouped(const mx_adamw_mix_bf16_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                              int64_t iter, int64_t step, float lr, const float* lr_dev, void* stream);
+int mx_adamw_mix_bf16_grouped_at(const mx_adamw_mix_bf16_call* call, const mx_param_runs* runs,
+                                 const float* gscale_dev, const int64_t* iter_dev, int64_t n_iters,
+                                 const int64_t* step_dev, float lr, const float* lr_dev, void* stream);
+
 /* ---------------------------------------------------------------- flatten / unflatten
  * mx_gather replaces flatten_tensors (comm_helpers.py:12-30): flat[off[s] + i] = src[s][i].
  * mx_scatter is the copy_ loop of reset_model over unflatten_tensors views

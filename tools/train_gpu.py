@@ -64,7 +64,12 @@ def main():
     ap.add_argument("--clip-grad-norm", default=None, type=float, metavar="X", help="--fused-sgd / --fused-adamw: "
                     "torch.nn.utils.clip_grad_norm_(model.parameters(), X) per worker inside the fused step (one "
                     "extra read of the gradients); an error on the paths that keep torch's optimizers")
+    ap.add_argument("--no-decay-1d", action="store_true", help="--fused-sgd / --fused-adamw: weight decay 0 for "
+                    "parameters with ndim <= 1 (biases, normalisation scales), as a parameter group of the fused "
+                    "step; an error on the paths that keep torch's optimizers")
     a = ap.parse_args()
+    if a.no_decay_1d and not (a.fused_sgd or a.fused_adamw):
+        ap.error("--no-decay-1d is honoured by the fused optimizer steps only: add --fused-sgd or --fused-adamw")
     if a.clip_grad_norm is not None and not (a.fused_sgd or a.fused_adamw):
         ap.error("--clip-grad-norm is honoured by the fused optimizer steps only: add --fused-sgd or --fused-adamw "
                  "(the other paths step torch's optimizers and do not clip)")
@@ -73,6 +78,8 @@ def main():
     if a.clip_grad_norm is not None and world > 1:
         ap.error("--clip-grad-norm: one process per GPU trains with torch's optimizers (no fused step yet) and "
                  "does not clip")
+    if a.no_decay_1d and world > 1:
+        ap.error("--no-decay-1d: one process per GPU trains with torch's optimizers (no fused step yet)")
     args = H.HarnessArgs(name=a.name, description=a.description, model=a.model, lr=a.lr, momentum=a.momentum,
                          epoch=a.epoch, bs=a.bs, warmup=a.warmup, nesterov=a.nesterov, matcha=a.matcha,
                          budget=a.budget, graphid=a.graphid, savePath=a.savePath, save=a.save,
@@ -95,7 +102,9 @@ def main():
         tr = H.VirtualTrainer(args, model_fn, a.batches, batched=a.batched or a.graph, graph=a.graph,
                               fused_sgd=a.fused_sgd, fused_adamw=a.fused_adamw,
                               adamw_hyper={"betas": (a.beta1, a.beta2), "eps": a.eps, "weight_decay": a.wd},
-                              clip_grad_norm=a.clip_grad_norm)
+                              clip_grad_norm=a.clip_grad_norm,
+                              param_groups=[{"params": lambda name, p: p.ndim <= 1, "weight_decay": 0.0}]
+                              if a.no_decay_1d else None)
         if a.resume:
             tr.load(a.resume)
     import time
