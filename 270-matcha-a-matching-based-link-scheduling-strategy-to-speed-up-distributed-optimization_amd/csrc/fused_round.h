@@ -1,0 +1,484 @@
+// fused_round.h -- the scaffold the fused optimizer rounds share (sgd_mix.hip, sgd_mix_bf16.hip,
+// adamw_mix.hip, adamw_mix_bf16.hip): one row kernel that stages a work item's updated rows in LDS and
+// runs the mixing round on them, and the host side that picks its class, grid and streaming mode.
+//
+// A family supplies a compile-time policy type `Update` and nothing else:
+//     Hyper                 the launch's argument block (fields lr, lr_dev, gscale, zero_grads and its own)
+//     Tabs                  its pointer tables, one `T* const*` per array, in kernel-argument order
+//     Lane                  what a lane keeps in flight: kB chunks of every array it reads
+//     State                 what a launch (and, grouped, a work item) derives from Hyper
+//     vec_of(tb, gq, k)     the alignment rule of the (segment, row): true = wide accesses
+//     load<NT>(...)         issues the loads of chunk t into Lane
+//     no_step(st, h)        launch-uniform: true = no such optimizer step, the launch writes nothing
+//     setup(st, h)          the per-launch constants
+//     begin_item<G>(...)    the per-work-item constants of a grouped launch
+//     update<G>(...)        the optimizer update of chunk t in registers: returns x' for LDS
+//     keep<NT>(...)         stores the state the lane owns and, with zero_grads, the zeros over g
+//     finish<NT>(...)       stores a mixed chunk (and, bf16 families, its rounded image)
+// Everything a policy decides is decided at compile time; the kernel has no run-time branch on the family.
+// A new optimizer is a new policy type plus its entry points: nothing in this file changes.
+//
+// In place: a tile's x' of every row is parked in LDS (barrier) before any x row of it is stored, and
+// different work items never share a column.  State arrays are read and written by the same lane only, so
+// they are stored when their chunk is staged.  Because every row is read in every round, the first loads
+// are issued before the round, the step and the plan record are looked at; every return happens before
+// any store and is taken by the whole block.
+#pragma once
+#include "fused_host.h"
+#include "mx_common.h"
+
+#include <type_traits>
+
+namespace mx {
+namespace fused {
+
+constexpr int kTPB = 256;
+constexpr int kMaxM = 32;
+constexpr int kWV = kTPB / 64;
+// 16-byte chunks of every array a lane has in flight at once: 2 keeps the 8-row SGD kernel at 68 VGPRs
+// (7 waves per SIMD) and measured 3 % faster on the headline shape than 4 (94 VGPRs, 5 waves); for AdamW
+// it is 32 VGPRs of loads in flight (the bf16 families hold g in 2 registers, not 4)
+constexpr int kB = 2;
+
+typedef float F4 __attribute__((ext_vector_type(4)));
+typedef float F2 __attribute__((ext_vector_type(2)));
+typedef __bf16 B2 __attribute__((ext_vector_type(2)));
+typedef uint32_t U2 __attribute__((ext_vector_type(2)));      // 4 bf16: one 8-byte access
+
+// global (not flat) accesses: counted on vmcnt only, so the LDS waits of the partner walk do not
+// drain the HBM stream (see mix.hip)
+template <typename T>
+using GPtr = __attribute__((address_space(1))) T*;
+
+template <bool NT>
+__device__ __forceinline__ F4 ld16(const float* p) {
+    const GPtr<const F4> g = (GPtr<const F4>)(p);
+    if constexpr (NT) return __builtin_nontemporal_load(g);
+    else return *g;
+}
+template <bool NT>
+__device__ __forceinline__ void st16(float* p, const F4& v) {
+    const GPtr<F4> g = (GPtr<F4>)(p);
+    if constexpr (NT) __builtin_nontemporal_store(v, g);
+    else *g = v;
+}
+template <bool NT>
+__device__ __forceinline__ U2 ld8(const uint16_t* p) {
+    const GPtr<const U2> g = (GPtr<const U2>)(p);
+    if constexpr (NT) return __builtin_nontemporal_load(g);
+    else return *g;
+}
+template <bool NT>
+__device__ __forceinline__ void st8(uint16_t* p, const U2& v) {
+    const GPtr<U2> g = (GPtr<U2>)(p);
+    if constexpr (NT) __builtin_nontemporal_store(v, g);
+    else *g = v;
+}
+__device__ __forceinline__ float ld4(const float* p) { return *(GPtr<const float>)(p); }
+__device__ __forceinline__ void st4(float* p, float v) { *(GPtr<float>)(p) = v; }
+__device__ __forceinline__ uint32_t ld2(const uint16_t* p) { return *(GPtr<const uint16_t>)(p); }
+__device__ __forceinline__ void st2(uint16_t* p, uint32_t v) { *(GPtr<uint16_t>)(p) = (uint16_t)v; }
+__device__ __forceinline__ bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+__device__ __forceinline__ bool al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+
+// one lane's chunk of 4 elements at column c of `row`: one wide access on the vector path (`vec`: the
+// family's alignment rule holds for the (segment, row)) when the chunk is in range, else one access per
+// element, zero-filled from `lim` on; nothing is ever stored at or past `lim`
+template <bool NT>
+__device__ __forceinline__ F4 load_chunk(const float* row, int64_t c, int64_t lim, bool vec) {
+    if (vec && c + 4 <= lim) return ld16<NT>(row + c);
+    F4 v;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) v[t] = (c + t < lim) ? ld4(row + c + t) : 0.0f;
+    return v;
+}
+template <bool NT>
+__device__ __forceinline__ void store_chunk(float* row, int64_t c, int64_t lim, bool vec, const F4& v) {
+    if (vec && c + 4 <= lim) {
+        st16<NT>(row + c, v);
+        return;
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (c + t < lim) st4(row + c + t, v[t]);
+}
+template <bool NT>
+__device__ __forceinline__ U2 load_chunk(const uint16_t* row, int64_t c, int64_t lim, bool vec) {
+    if (vec && c + 4 <= lim) return ld8<NT>(row + c);
+    U2 v;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const uint32_t lo = (c + 2 * t < lim) ? ld2(row + c + 2 * t) : 0u;
+        const uint32_t hi = (c + 2 * t + 1 < lim) ? ld2(row + c + 2 * t + 1) : 0u;
+        v[t] = lo | (hi << 16);
+    }
+    return v;
+}
+template <bool NT>
+__device__ __forceinline__ void store_chunk(uint16_t* row, int64_t c, int64_t lim, bool vec, const U2& v) {
+    if (vec && c + 4 <= lim) {
+        st8<NT>(row + c, v);
+        return;
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        if (c + 2 * t < lim) st2(row + c + 2 * t, v[t] & 0xFFFFu);
+        if (c + 2 * t + 1 < lim) st2(row + c + 2 * t + 1, v[t] >> 16);
+    }
+}
+
+// f32() of 4 bf16: the exact widening bits << 16 (an fp32 chunk is its own widening)
+__device__ __forceinline__ F4 widen4(const U2& g) {
+    F4 v;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        v[2 * t] = __builtin_bit_cast(float, g[t] << 16);
+        v[2 * t + 1] = __builtin_bit_cast(float, g[t] & 0xFFFF0000u);
+    }
+    return v;
+}
+__device__ __forceinline__ F4 widen4(const F4& g) { return g; }
+
+// the one rounding: fp32 -> bf16, to nearest even (v_cvt_pk_bf16_f32; NaN stays NaN)
+__device__ __forceinline__ U2 pack4(const F4& a) {
+    U2 v;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const F2 f = {a[2 * t], a[2 * t + 1]};
+        v[t] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f, B2));
+    }
+    return v;
+}
+
+__device__ __forceinline__ void fma4(F4& a, float w, const F4& x) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) a[t] = __builtin_fmaf(w, x[t], a[t]);
+}
+
+// the clip factor of the row (mx_*_scaled): g' = fmul(gscale[r], f32(g)), before anything else in the update
+__device__ __forceinline__ F4 scale4(const F4& g, float s) {
+    F4 v;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) v[t] = s * g[t];
+    return v;
+}
+// row k's gradient chunk as the update sees it: widened, and scaled where the launch has clip factors
+template <class G, class H>
+__device__ __forceinline__ F4 grad_of(const G& g, const H& h, int k) {
+    return h.gscale ? scale4(widen4(g), h.gscale[k]) : widen4(g);
+}
+
+// Per-parameter-group launches (mx_*_grouped): the columns of a segment are cut into runs that each
+// carry their own weight decay and learning-rate scale (mx_param_runs; the tables are read when the
+// kernel runs).  Element of run r: lr_r = fmul(lr, s_r), then the family's update with wd -> wd_r and
+// lr -> lr_r.  The ungrouped instantiations carry none of this: their argument block is Hyper alone.
+struct Runs {
+    const int32_t* off;    // int32 [nseg + 1]: segment s owns runs [off[s], off[s + 1])
+    const int64_t* end;    // int64 [nruns]: exclusive end column within the segment, ascending
+    const float* wd;       // float [nruns]
+    const float* scale;    // float [nruns]
+};
+template <class Hyper>
+struct Grouped : Hyper {
+    Runs rn;
+};
+template <class Hyper, bool GROUPED>
+using GroupedIf = std::conditional_t<GROUPED, Grouped<Hyper>, Hyper>;
+template <class Update, bool GROUPED>
+using HyperOf = GroupedIf<typename Update::Hyper, GROUPED>;
+
+// where a work item lies
+struct Geo {
+    int64_t base, col0, lim;             // base: the segment's row of the pointer tables
+    // GROUPED only: the first run that ends past col0, the end of the segment's runs, whether that
+    // run covers the whole work item, and its pair
+    int r0, rhi;
+    bool uni;
+    float wd, scale;
+};
+
+template <int NS>
+struct PlanLds {
+    int32_t w[mx::kPlanHeader + 2 * NS + NS * kMaxM];
+};
+
+// The round to run: `iter`, or with iter_dev (graph-replayable launches) the device counter
+// *iter_dev, `iter` then being the schedule length; outside [0, length) the launch is a no-op.
+__device__ __forceinline__ int64_t round_of(int64_t iter, const int64_t* iter_dev) {
+    if (!iter_dev) return iter;
+    const int64_t v = *iter_dev;
+    return (v >= 0 && v < iter) ? v : -1;
+}
+
+// NS rows x TW columns per work item; a layout tile (mx_*_tile) is `split` work items.
+// GROUPED: per-run weight decay and learning-rate scale (see Runs above).  T...: Update::Tabs' members.
+template <class Update, int NS, int TW, bool NT, bool GROUPED, class... T>
+__global__ __launch_bounds__(kTPB) void fused_round_rows(T __restrict__... tabs,
+                                                         const int64_t* __restrict__ seg_len,
+                                                         const int64_t* __restrict__ tile_off, int nseg,
+                                                         int64_t total_tiles, int split,
+                                                         const int32_t* __restrict__ plan, int64_t iter,
+                                                         const int64_t* __restrict__ iter_dev, int n_local, int M,
+                                                         float alpha, HyperOf<Update, GROUPED> h) {
+    constexpr int C4 = TW / 4;            // 4-element chunks per row per work item
+    constexpr int NQ = TW / 256;          // 256-column passes per row
+    constexpr int NI = NS * NQ;           // items per work item (<= 64: one per lane of wave 0)
+    constexpr int E = NS * C4 / kTPB;     // chunks staged per lane
+    static_assert(NQ >= 1 && NI <= 64 && NI % kWV == 0 && E % kB == 0 && E * kTPB == NS * C4 && C4 % 64 == 0,
+                  "fused row kernel geometry");
+    __shared__ F4 lds[NS * C4];
+    __shared__ PlanLds<NS> sp;
+    __shared__ int32_t wl[kWV][NI / kWV];
+    const typename Update::Tabs tb{tabs...};
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t total_work = total_tiles * split;
+    const int64_t niter = total_work > blockIdx.x ? (total_work - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
+    if (niter == 0) return;                  // block-uniform, before any barrier
+
+    auto geo = [&](int64_t work) {
+        const int64_t tile = work / split;
+        int lo = 0, hi = nseg;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (tile_off[mid] <= tile) lo = mid; else hi = mid;
+        }
+        Geo gq;
+        gq.base = (int64_t)lo * n_local;
+        gq.col0 = (tile - tile_off[lo]) * ((int64_t)TW * split) + (work % split) * TW;
+        gq.lim = seg_len[lo];
+        gq.r0 = gq.rhi = 0;
+        gq.uni = true;
+        gq.wd = gq.scale = 0.0f;
+        if constexpr (GROUPED) {
+            int a = h.rn.off[lo], b = h.rn.off[lo + 1];
+            gq.rhi = b;
+            while (a < b) {                  // wave-uniform: the first run with end > col0
+                const int mid = (a + b) >> 1;
+                if (h.rn.end[mid] <= gq.col0) a = mid + 1; else b = mid;
+            }
+            gq.r0 = a < gq.rhi ? a : gq.rhi - 1;             // a work item wholly past the segment's length
+            const int64_t last = gq.col0 + TW < gq.lim ? gq.col0 + TW : gq.lim;
+            gq.uni = h.rn.end[gq.r0] >= last;
+            gq.wd = h.rn.wd[gq.r0];
+            gq.scale = h.rn.scale[gq.r0];
+        }
+        return gq;
+    };
+    typename Update::Lane ln;
+    auto issue = [&](const Geo& gq, int j0) {
+#pragma unroll
+        for (int t = 0; t < kB; ++t) {
+            const int at = wave * 64 + kTPB * (j0 + t);
+            const int k = at / C4;                                   // wave-uniform row
+            if (k < n_local) {
+                const int64_t c = gq.col0 + (int64_t)(at % C4 + lane) * 4;
+                Update::template load<NT>(ln, t, tb, gq, k, c, Update::vec_of(tb, gq, k));
+            }
+        }
+    };
+    // the first chunks' loads fly while the round and its plan record are fetched: every row is read
+    // in every round, so they wait for nothing
+    Geo cur = geo(blockIdx.x);
+    issue(cur, 0);
+    const int64_t rnd = round_of(iter, iter_dev);
+    if (rnd < 0) return;                     // counter outside the schedule: nothing is written
+    typename Update::State st;
+    if (Update::no_step(st, h)) return;      // no such optimizer step: nothing is written
+    {
+        const int64_t W = mx::plan_words(n_local, M);
+        const int32_t* rec = plan + rnd * W;
+        for (int i = tid; i < W; i += kTPB) sp.w[i] = rec[i];
+    }
+    __syncthreads();
+    if (sp.w[2] & 2) return;                 // peer-reads record: not this kernel's (nothing is written)
+    const bool active = sp.w[0] != 0;
+    const bool idle = (sp.w[2] & 1) != 0;
+    const int32_t* deg = sp.w + mx::kPlanHeader;
+    const float* sw = reinterpret_cast<const float*>(deg + n_local);
+    const int32_t* src = deg + 2 * n_local;
+    // rows that get the FMA chain (degree > 0, or every row of an active round in idle mode 1); every
+    // other row stores x' as it is
+    auto mixes = [&](int r) { return active && (deg[r] > 0 || idle); };
+    auto degree = [&](int r) { return mixes(r) ? deg[r] : 0; };
+    Update::setup(st, h);
+
+    // deal the items (row r, pass q) = r * NQ + q to the waves: wave 0 ranks them by weight
+    // (degree + 1), snake order over the waves
+    if (wave == 0) {
+        const int r = lane / NQ;
+        const int w = (lane < NI && r < n_local) ? degree(r) + 1 : 0;
+        int rank = 0;
+        for (int j = 0; j < NI; ++j) {
+            const int wj = __builtin_amdgcn_readlane(w, j);
+            rank += (wj > w) || (wj == w && j < lane);
+        }
+        const int round = rank / kWV, within = rank % kWV;
+        if (lane < NI) wl[(round & 1) ? kWV - 1 - within : within][round] = w > 0 ? lane : -1;
+    }
+    __syncthreads();
+    // ranks grow along a wave's list, so its unused (-1) entries form a suffix
+    int nmy = 0;
+    while (nmy < NI / kWV && wl[wave][nmy] >= 0) ++nmy;
+    nmy = __builtin_amdgcn_readfirstlane(nmy);
+
+    // the update of the chunks in flight: x' parked in LDS, the lane's state (and the zeros over g) stored
+    auto park = [&](const Geo& gq, int j0) {
+#pragma unroll
+        for (int t = 0; t < kB; ++t) {
+            const int at = wave * 64 + kTPB * (j0 + t);
+            const int k = at / C4;
+            if (k < n_local) {
+                const int64_t c = gq.col0 + (int64_t)(at % C4 + lane) * 4;
+                const bool vec = Update::vec_of(tb, gq, k);
+                lds[at + lane] = Update::template update<GROUPED>(ln, t, k, c, gq, st, h);
+                Update::template keep<NT>(ln, t, tb, gq, k, c, vec, h);
+            }
+        }
+    };
+    // the mixing walk: partners in ascending matching order, the self term last, one __builtin_fmaf per step
+    auto mix_tile = [&](const Geo& g) {
+        auto finish = [&](int it, F4& acc) {
+            const int r = it / NQ;
+            const int col = (it % NQ) * 64 + lane;
+            const F4 self = lds[r * C4 + col];
+            if (mixes(r)) fma4(acc, sw[r], self);                    // the self term, last
+            else acc = self;                                         // x' as it is
+            Update::template finish<NT>(tb, g, r, g.col0 + (int64_t)col * 4, Update::vec_of(tb, g, r), acc);
+        };
+        int p = 0;
+        for (; p + 1 < nmy; p += 2) {            // two items interleaved
+            const int ia = __builtin_amdgcn_readfirstlane(wl[wave][p]);
+            const int ib = __builtin_amdgcn_readfirstlane(wl[wave][p + 1]);
+            const int ra = ia / NQ, rb = ib / NQ;
+            const int ca = (ia % NQ) * 64 + lane, cb = (ib % NQ) * 64 + lane;
+            const int da = degree(ra), db = degree(rb);
+            const int dmin = da < db ? da : db;
+            F4 a = {0.0f, 0.0f, 0.0f, 0.0f}, b = {0.0f, 0.0f, 0.0f, 0.0f};
+            int e = 0;
+            for (; e < dmin; ++e) {
+                const int sa = __builtin_amdgcn_readfirstlane(src[ra * M + e]);
+                const int sb = __builtin_amdgcn_readfirstlane(src[rb * M + e]);
+                const F4 xa = lds[sa * C4 + ca];
+                const F4 xb = lds[sb * C4 + cb];
+                fma4(a, alpha, xa);
+                fma4(b, alpha, xb);
+            }
+            for (int ea = e; ea < da; ++ea)
+                fma4(a, alpha, lds[__builtin_amdgcn_readfirstlane(src[ra * M + ea]) * C4 + ca]);
+            for (int eb = e; eb < db; ++eb)
+                fma4(b, alpha, lds[__builtin_amdgcn_readfirstlane(src[rb * M + eb]) * C4 + cb]);
+            finish(ia, a);
+            finish(ib, b);
+        }
+        if (p < nmy) {
+            const int ia = __builtin_amdgcn_readfirstlane(wl[wave][p]);
+            const int ra = ia / NQ, ca = (ia % NQ) * 64 + lane;
+            const int da = degree(ra);
+            F4 a = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int e = 0; e < da; ++e)
+                fma4(a, alpha, lds[__builtin_amdgcn_readfirstlane(src[ra * M + e]) * C4 + ca]);
+            finish(ia, a);
+        }
+    };
+    for (int64_t i = 0; i < niter; ++i) {
+        if (i) __syncthreads();              // every wave is done reading the previous tile
+        // the parked work item's constants come from its own Geo (`cur`), never the prefetched one's
+        Update::template begin_item<GROUPED>(st, cur, h);
+        park(cur, 0);
+        for (int j0 = kB; j0 < E; j0 += kB) {
+            issue(cur, j0);
+            park(cur, j0);
+        }
+        __syncthreads();                     // every row's x' is staged before any x row is written
+        Geo nxt = cur;
+        if (i + 1 < niter) {                 // the next work item's first loads fly while this one is mixed
+            nxt = geo(blockIdx.x + (i + 1) * gridDim.x);
+            issue(nxt, 0);
+        }
+        mix_tile(cur);
+        cur = nxt;
+    }
+}
+
+// ---------------------------------------------------------------- host side (fused_host.h, fused_round.cpp)
+
+// the launch-independent fields every call record carries, and what the entry point adds
+struct Round {
+    const int64_t* seg_len;
+    const int64_t* tile_off;
+    const int32_t* plan;
+    int64_t total_tiles;
+    int nseg, n_local, M;
+    float alpha;
+    int64_t iter;
+    const int64_t* iter_dev;
+    hipStream_t stream;
+};
+
+// the checks common to the four call records (`who`: the entry point called; the family has looked at
+// the record's pointers), then the record's Round
+template <class Call>
+int check_round(const Call* c, int64_t iter, const int64_t* iter_dev, void* stream, const char* who, Round* r) {
+    MX_CHECK(c->nseg >= 1 && c->n_local >= 1, "%s: nseg=%d n_local=%d", who, c->nseg, c->n_local);
+    MX_CHECK(c->n_slots == c->n_local, "%s: n_slots=%d != n_local=%d (every partner must be a local row)", who,
+             c->n_slots, c->n_local);
+    MX_CHECK(c->n_local <= 64, "%s: n_local=%d exceeds 64", who, c->n_local);
+    MX_CHECK(c->M >= 1 && c->M <= kMaxM, "%s: M=%d outside [1, %d]", who, c->M, kMaxM);
+    *r = Round{c->seg_len_dev, c->tile_off_dev, c->plan_dev, c->total_tiles, c->nseg, c->n_local, c->M, c->alpha,
+               iter, iter_dev, mx::as_stream(stream)};
+    return MX_OK;
+}
+// the last check of every family, after its own (the order of the checks decides which of two faults is
+// reported)
+inline int check_runs(const mx_param_runs* runs, const char* who) {
+    MX_CHECK(!runs || (runs->run_off_dev && runs->run_end_dev && runs->wd_dev && runs->lr_scale_dev && runs->nruns >= 1),
+             "%s: parameter runs with a null table or nruns < 1", who);
+    return MX_OK;
+}
+
+template <class Update, int NS, int TW, bool NT, bool GROUPED, class... T>
+int launch(const Tune& tune, const Round& r, const typename Update::Hyper& h, const mx_param_runs* runs, T... tabs) {
+    const auto kernel = fused_round_rows<Update, NS, TW, NT, GROUPED, T...>;
+    const int split = pick(r.n_local).tile / TW;
+    bool flat = false;
+    const int64_t grid = tune.grid_of(NS, r.total_tiles * split, &flat);
+    size_t pad = 0;
+    if (flat && tune.wgpc > 0) {
+        static const int stat = [kernel] {                     // static LDS of this instantiation
+            hipFuncAttributes fa{};
+            return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel)) == hipSuccess ? (int)fa.sharedSizeBytes
+                                                                                                   : 0;
+        }();
+        pad = mx::lds_cap_pad(stat, tune.wgpc);
+    }
+    HyperOf<Update, GROUPED> hy;
+    static_cast<typename Update::Hyper&>(hy) = h;
+    if constexpr (GROUPED) hy.rn = Runs{runs->run_off_dev, runs->run_end_dev, runs->wd_dev, runs->lr_scale_dev};
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kTPB), pad, r.stream, tabs..., r.seg_len, r.tile_off, r.nseg,
+                       r.total_tiles, split, r.plan, r.iter, r.iter_dev, r.n_local, r.M, r.alpha, hy);
+    MX_LAUNCH_CHECK();
+    return MX_OK;
+}
+
+// the instantiation of a checked call: row class x streaming mode x grouped (runs != NULL)
+template <class Update, class... T>
+int dispatch(const Tune& tune, const Round& r, bool nt, const typename Update::Hyper& h, const mx_param_runs* runs,
+             T... tabs) {
+#define MX_FUSED(N, TW)                                                                                       \
+    (runs ? (nt ? launch<Update, N, TW, true, true>(tune, r, h, runs, tabs...)                              \
+                : launch<Update, N, TW, false, true>(tune, r, h, runs, tabs...))                             \
+          : (nt ? launch<Update, N, TW, true, false>(tune, r, h, runs, tabs...)                             \
+                : launch<Update, N, TW, false, false>(tune, r, h, runs, tabs...)))
+    switch (pick(r.n_local).ns) {
+        case 8: return MX_FUSED(8, 512);
+        case 16: return MX_FUSED(16, 512);
+        case 32: return MX_FUSED(32, 512);
+        default: return MX_FUSED(64, 256);
+    }
+#undef MX_FUSED
+}
+
+}  // namespace fused
+}  // namespace mx

@@ -124,7 +124,7 @@ class Kind:
              "g": _bits(grp.grads) if self.mixed else grp.grads.cpu().numpy()}
         if self.adam:
             s["m"], s["v"] = grp.exp_avg_rows.cpu().numpy(), grp.exp_avg_sq_rows.cpu().numpy()
-        else:
+        elif grp.momentum_rows is not None:             # no "m" without momentum
             s["m"] = grp.momentum_rows.cpu().numpy()
         if self.mixed:
             s["p"] = _bits(grp.rows)

@@ -168,6 +168,53 @@ def test_boundaries(pkg, O, kind, name, idle):
         assert not np.array_equal(_u32(last[2]["m"][:, a:b]), _u32(last[1]["m"][:, a:b]))
 
 
+@pytest.mark.parametrize("name", ["g0", "g16", "ring32", "er64"])
+@pytest.mark.parametrize("kind,momentum", [(k, m) for k in KINDS for m in ((True, False) if k.startswith("sgd") else (True,))])
+def test_every_instantiation(pkg, O, kind, momentum, name):
+    """every (family x row class x streaming x grouped x momentum) instantiation of the row kernel, in a
+    persistent grid of 2 workgroups: plain and grouped launches, streaming hints on and off, SGD with and
+    without a momentum buffer, three carried rounds each, bit-equal to the specification"""
+    K = GKind(kind)
+    partner, alpha = _topology(pkg, name)
+    n, P = partner.shape[1], 4097
+    flags = _flags3(partner)
+    topo = Topo(partner, alpha, flags)
+    hyper = None if momentum else (SGD_HYPER[0], 0.0, False)
+    get, put = K.tuning(pkg)
+    saved = get()
+    for runs in (None, RUNS):
+        rng = np.random.default_rng([KINDS.index(kind), n, int(momentum), 13])
+        X = rng.standard_normal((n, P)).astype(F32)
+        Gs = [K.grads(rng, (n, P)) for _ in range(3)]
+        want = None
+        for nt in (1, 0):
+            put(grid=2, nontemporal=nt)
+            try:
+                grp = K.group(pkg, topo, P, True, hyper=hyper, groups=None if runs is None else _groups(runs))
+                assert (grp.param_runs == runs) if runs else not grp.param_runs
+                K.put_x(grp, X)
+                s = {"m": None, **K.state(grp)}          # no momentum buffer: m stays None
+                got = []
+                for it in range(3):
+                    K.put_g(grp, Gs[it])
+                    K.step(grp, it, LR)
+                    got.append(K.state(grp))
+            finally:
+                put(**saved)
+            if want is None:                            # the specification once per (plain / grouped)
+                want = []
+                one_run = [(0, P, K.hyper[3] if K.adam else K.hyper[0], 1.0)]      # the ungrouped launch
+                for it in range(3):
+                    want.append(K.gspec(O, s, Gs[it], None, runs or one_run, it + 1, partner, flags[it], alpha, LR))
+                    s = {**s, **want[-1]}
+            for it in range(3):
+                for k, w in want[it].items():
+                    if w is not None:
+                        assert Kind.same(got[it], want[it], [k]), \
+                            f"{kind} momentum={momentum} {name} grouped={runs is not None} nontemporal={nt} round {it}: {k}"
+    assert get() == saved
+
+
 @pytest.mark.parametrize("name", ["g0", "ring32"])
 @pytest.mark.parametrize("kind", KINDS)
 def test_persistent_loop(pkg, kind, name):

@@ -176,6 +176,65 @@ def test_ipc_knobs_and_publish_rows_validation(pkg):
     assert L.mx_snapshot_publish_rows(fake, 8, fake, 8, 0, 2, fake, 5, fake, 8, 0, None) == 0      # nothing to do
 
 
+FUSED = ("mx_sgd_mix", "mx_sgd_mix_bf16", "mx_adamw_mix", "mx_adamw_mix_bf16")
+FUSED_DEFAULTS = {b"nontemporal": 2, b"wgpc": 0, b"blocks_per_cu": 2, b"flat_small": 256, b"grid": 0}
+
+
+def test_fused_round_knobs_are_per_family(pkg):
+    """mx_*_set / _get of the four fused optimizer rounds: the defaults, every key set on one family read
+    back from that family alone, the refusals (naming the entry point called), values restored."""
+    L = pkg.lib
+    INV = pkg._lib.MX_ERR_INVALID
+    get = {f: getattr(L, f + "_get") for f in FUSED}
+    put = {f: getattr(L, f + "_set") for f in FUSED}
+    for f in FUSED:
+        assert {k: get[f](k) for k in FUSED_DEFAULTS} == FUSED_DEFAULTS, f
+    changed = {b"nontemporal": 0, b"wgpc": 5, b"blocks_per_cu": 3, b"flat_small": 17, b"grid": 7}
+    try:
+        for f in FUSED:
+            for k, v in changed.items():
+                assert put[f](k, v) == 0 and get[f](k) == v, (f, k)
+                for o in FUSED:
+                    if o != f:
+                        assert get[o](k) == FUSED_DEFAULTS[k], (f, k, o)
+                assert put[f](k, FUSED_DEFAULTS[k]) == 0 and get[f](k) == FUSED_DEFAULTS[k], (f, k)
+            for k, v in ((b"wgpc", 33), (b"blocks_per_cu", 0), (b"flat_small", 4097), (b"grid", 65537), (b"no_such_knob", 1)):
+                assert put[f](k, v) == INV, (f, k)
+                assert (f + "_set:").encode() in L.mx_last_error(), (f, k, L.mx_last_error())
+            assert {k: get[f](k) for k in FUSED_DEFAULTS} == FUSED_DEFAULTS, f     # a refusal changes nothing
+            assert get[f](b"no_such_knob") == INV
+    finally:
+        for f in FUSED:
+            for k, v in FUSED_DEFAULTS.items():
+                put[f](k, v)
+
+
+def test_fused_round_layouts_agree(pkg):
+    """mx_*_tile / mx_*_layout of the four fused optimizer rounds: 1024 / 1024 / 512 / 256 columns by row
+    class, the same offsets from all four -- ceil(len / tile) accumulated -- and the refusals."""
+    L = pkg.lib
+    INV = pkg._lib.MX_ERR_INVALID
+    lens = np.array([0, 1, 1023, 1024, 1025, 4097], np.int64)
+    for n_slots in (1, 8, 9, 16, 17, 32, 33, 64):
+        tile = 1024 if n_slots <= 16 else 512 if n_slots <= 32 else 256
+        want = [0] + np.cumsum((lens + tile - 1) // tile).tolist()
+        for f in FUSED:
+            assert getattr(L, f + "_tile")(n_slots) == tile, (f, n_slots)
+            off = np.full(len(lens) + 1, -1, np.int64)
+            assert getattr(L, f + "_layout")(lens.ctypes.data, len(lens), n_slots, off.ctypes.data) == 0
+            assert off.tolist() == want, (f, n_slots)
+    off = np.zeros(len(lens) + 1, np.int64)
+    neg = np.array([5, -1], np.int64)
+    for f in FUSED:
+        lay = getattr(L, f + "_layout")
+        for n_slots in (0, 65):
+            assert getattr(L, f + "_tile")(n_slots) == 0
+            assert lay(lens.ctypes.data, len(lens), n_slots, off.ctypes.data) == INV
+            assert (f + "_layout:").encode() in L.mx_last_error()
+        assert lay(neg.ctypes.data, 2, 8, off.ctypes.data) == INV
+        assert (f + "_layout:").encode() in L.mx_last_error()
+
+
 def test_mix_call_struct_layout_matches_header(pkg, tmp_path):
     """engine.MixCall (the ctypes mirror of mx_mix_call) has the C struct's size and field offsets:
     a C program built against include/matcha_gossip.h prints them."""
