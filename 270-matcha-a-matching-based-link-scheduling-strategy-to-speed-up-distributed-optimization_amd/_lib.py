@@ -39,52 +39,12 @@ SIGNATURES = {
     "mx_gossip_mix_bf16_packed": (c_int, [c_p, c_i64, c_p]),
     "mx_gossip_mix_bf16_at": (c_int, [c_p, c_p, c_p, c_p, c_int, c_i64, c_int, c_p, c_p, c_i64, c_int, c_int, c_f32,
                                       c_p]),
-    "mx_sgd_mix_tile": (c_int, [c_int]),
-    "mx_sgd_mix_layout": (c_int, [c_p, c_int, c_int, c_p]),
-    "mx_sgd_mix_set": (c_int, [ctypes.c_char_p, c_int]),
-    "mx_sgd_mix_get": (c_int, [ctypes.c_char_p]),
-    "mx_sgd_mix": (c_int, [c_p, c_i64, c_f32, c_p, c_p]),
-    "mx_sgd_mix_at": (c_int, [c_p, c_p, c_i64, c_f32, c_p, c_p]),
-    "mx_sgd_mix_bf16_tile": (c_int, [c_int]),
-    "mx_sgd_mix_bf16_layout": (c_int, [c_p, c_int, c_int, c_p]),
-    "mx_sgd_mix_bf16_set": (c_int, [ctypes.c_char_p, c_int]),
-    "mx_sgd_mix_bf16_get": (c_int, [ctypes.c_char_p]),
-    "mx_sgd_mix_bf16": (c_int, [c_p, c_i64, c_f32, c_p, c_p]),
-    "mx_sgd_mix_bf16_at": (c_int, [c_p, c_p, c_i64, c_f32, c_p, c_p]),
-    "mx_adamw_mix_tile": (c_int, [c_int]),
-    "mx_adamw_mix_layout": (c_int, [c_p, c_int, c_int, c_p]),
-    "mx_adamw_mix_set": (c_int, [ctypes.c_char_p, c_int]),
-    "mx_adamw_mix_get": (c_int, [ctypes.c_char_p]),
-    "mx_adamw_mix": (c_int, [c_p, c_i64, c_i64, c_f32, c_p, c_p]),
-    "mx_adamw_mix_at": (c_int, [c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
-    "mx_adamw_mix_bf16_tile": (c_int, [c_int]),
-    "mx_adamw_mix_bf16_layout": (c_int, [c_p, c_int, c_int, c_p]),
-    "mx_adamw_mix_bf16_set": (c_int, [ctypes.c_char_p, c_int]),
-    "mx_adamw_mix_bf16_get": (c_int, [ctypes.c_char_p]),
-    "mx_adamw_mix_bf16": (c_int, [c_p, c_i64, c_i64, c_f32, c_p, c_p]),
-    "mx_adamw_mix_bf16_at": (c_int, [c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
     "mx_grad_norm_cols": (c_int, []),
     "mx_grad_norm_layout": (c_i64, [c_p, c_int, c_int, c_p]),
     "mx_grad_norm_set": (c_int, [ctypes.c_char_p, c_int]),
     "mx_grad_norm_get": (c_int, [ctypes.c_char_p]),
     "mx_grad_norm": (c_int, [c_p, c_p]),
-    "mx_sgd_mix_scaled": (c_int, [c_p, c_p, c_i64, c_f32, c_p, c_p]),
-    "mx_sgd_mix_scaled_at": (c_int, [c_p, c_p, c_p, c_i64, c_f32, c_p, c_p]),
-    "mx_sgd_mix_bf16_scaled": (c_int, [c_p, c_p, c_i64, c_f32, c_p, c_p]),
-    "mx_sgd_mix_bf16_scaled_at": (c_int, [c_p, c_p, c_p, c_i64, c_f32, c_p, c_p]),
-    "mx_adamw_mix_scaled": (c_int, [c_p, c_p, c_i64, c_i64, c_f32, c_p, c_p]),
-    "mx_adamw_mix_scaled_at": (c_int, [c_p, c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
-    "mx_adamw_mix_bf16_scaled": (c_int, [c_p, c_p, c_i64, c_i64, c_f32, c_p, c_p]),
-    "mx_adamw_mix_bf16_scaled_at": (c_int, [c_p, c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
     "mx_param_runs_check": (c_int, [c_p, c_int, c_p, c_p, c_p, c_p]),
-    "mx_sgd_mix_grouped": (c_int, [c_p, c_p, c_p, c_i64, c_f32, c_p, c_p]),
-    "mx_sgd_mix_grouped_at": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_f32, c_p, c_p]),
-    "mx_sgd_mix_bf16_grouped": (c_int, [c_p, c_p, c_p, c_i64, c_f32, c_p, c_p]),
-    "mx_sgd_mix_bf16_grouped_at": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_f32, c_p, c_p]),
-    "mx_adamw_mix_grouped": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_f32, c_p, c_p]),
-    "mx_adamw_mix_grouped_at": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
-    "mx_adamw_mix_bf16_grouped": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_f32, c_p, c_p]),
-    "mx_adamw_mix_bf16_grouped_at": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_p, c_f32, c_p, c_p]),
     "mx_gather": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p]),
     "mx_scatter": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p]),
     "mx_topk_work_bytes": (ctypes.c_size_t, [c_i64]),
@@ -141,6 +101,25 @@ SIGNATURES = {
     "mx_ipc_close": (c_int, [c_p]),
     "mx_ipc_free": (c_int, [c_p]),
 }
+
+
+def _fused_signatures(base, step):
+    """The ten entry points of a fused optimizer + mixing family (mx_sgd_mix, ...): tile, layout, knobs, and
+    the launch in three modes (plain; _scaled: + the clip factors; _grouped: + the parameter runs and the
+    clip factors), each eager (iter, [step,] lr, lr_dev, stream) and graph-replayable (_at: iter_dev,
+    n_iters, [step_dev,] lr, lr_dev, stream).  `step`: the Adam families' optimizer-step argument."""
+    eager = [c_i64] + [c_i64] * step + [c_f32, c_p, c_p]
+    at = [c_p, c_i64] + [c_p] * step + [c_f32, c_p, c_p]
+    sig = {base + "_tile": (c_int, [c_int]), base + "_layout": (c_int, [c_p, c_int, c_int, c_p]),
+           base + "_set": (c_int, [ctypes.c_char_p, c_int]), base + "_get": (c_int, [ctypes.c_char_p])}
+    for mode, records in (("", 1), ("_scaled", 2), ("_grouped", 3)):         # leading pointers: the call record, ...
+        sig[base + mode] = (c_int, [c_p] * records + eager)
+        sig[base + mode + "_at"] = (c_int, [c_p] * records + at)
+    return sig
+
+
+for _base, _step in (("mx_sgd_mix", 0), ("mx_sgd_mix_bf16", 0), ("mx_adamw_mix", 1), ("mx_adamw_mix_bf16", 1)):
+    SIGNATURES.update(_fused_signatures(_base, _step))
 
 
 MX_OK, MX_ERR_INVALID, MX_ERR_HIP, MX_ERR_RCCL, MX_ERR_RNG, MX_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5

@@ -12,6 +12,7 @@ Per round (reference: decenCommunicator.communicate, communicator.py:133-158):
        by the precomputed plan record of this iteration.
 Everything is enqueued on one HIP stream; nothing is copied to or from the host per round.
 """
+import collections
 import ctypes
 import math
 import sys
@@ -39,7 +40,9 @@ def mix_kernel_name(n_slots):
     return lib.mx_mix_kernel_name(int(n_slots)).decode()
 
 
-_TUNE_GEN = [0]     # bumped on every knob change: layouts re-check their tile size only then
+# bumped by set_mix_tuning alone: the mixing kernel's tile depends on its knobs (unroll), so a Layout
+# re-checks its tile after a change.  The fused rounds' tile depends on the row count only
+_TUNE_GEN = [0]
 _mix_packed = lib.mx_gossip_mix_packed
 _mix_bf16_packed = lib.mx_gossip_mix_bf16_packed
 
@@ -59,63 +62,6 @@ def set_mix_tuning(**knobs):
     _TUNE_GEN[0] += 1
     for k, v in knobs.items():
         check(lib.mx_mix_set(k.encode(), int(v)), "mx_mix_set")
-
-
-SGD_TUNE_KEYS = ("nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid")
-_sgd_mix = lib.mx_sgd_mix
-
-
-def sgd_mix_tuning():
-    """Current knobs of the fused SGD + mixing kernel (include/matcha_gossip.h, mx_sgd_mix_set)."""
-    return {k: int(lib.mx_sgd_mix_get(k.encode())) for k in SGD_TUNE_KEYS}
-
-
-def set_sgd_mix_tuning(**knobs):
-    _TUNE_GEN[0] += 1
-    for k, v in knobs.items():
-        check(lib.mx_sgd_mix_set(k.encode(), int(v)), "mx_sgd_mix_set")
-
-
-_sgd_mix_bf16 = lib.mx_sgd_mix_bf16
-
-
-def sgd_mix_bf16_tuning():
-    """Current knobs of the mixed-precision fused SGD + mixing kernel (mx_sgd_mix_bf16_set)."""
-    return {k: int(lib.mx_sgd_mix_bf16_get(k.encode())) for k in SGD_TUNE_KEYS}
-
-
-def set_sgd_mix_bf16_tuning(**knobs):
-    _TUNE_GEN[0] += 1
-    for k, v in knobs.items():
-        check(lib.mx_sgd_mix_bf16_set(k.encode(), int(v)), "mx_sgd_mix_bf16_set")
-
-
-_adamw_mix = lib.mx_adamw_mix
-
-
-def adamw_mix_tuning():
-    """Current knobs of the fused AdamW + mixing kernel (mx_adamw_mix_set)."""
-    return {k: int(lib.mx_adamw_mix_get(k.encode())) for k in SGD_TUNE_KEYS}
-
-
-def set_adamw_mix_tuning(**knobs):
-    _TUNE_GEN[0] += 1
-    for k, v in knobs.items():
-        check(lib.mx_adamw_mix_set(k.encode(), int(v)), "mx_adamw_mix_set")
-
-
-_adamw_mix_bf16 = lib.mx_adamw_mix_bf16
-
-
-def adamw_mix_bf16_tuning():
-    """Current knobs of the mixed-precision fused AdamW + mixing kernel (mx_adamw_mix_bf16_set)."""
-    return {k: int(lib.mx_adamw_mix_bf16_get(k.encode())) for k in SGD_TUNE_KEYS}
-
-
-def set_adamw_mix_bf16_tuning(**knobs):
-    _TUNE_GEN[0] += 1
-    for k, v in knobs.items():
-        check(lib.mx_adamw_mix_bf16_set(k.encode(), int(v)), "mx_adamw_mix_bf16_set")
 
 
 GRAD_NORM_TUNE_KEYS = ("blocks_per_cu", "grid")
@@ -720,48 +666,6 @@ class SgdMixCall(ctypes.Structure):
                 ("zero_grads", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
-class SgdLayout:
-    """Pointer tables of the fused SGD + mixing kernel (csrc/sgd_mix.hip): row r's copy of segment s,
-    its gradient and -- unless m_ptrs is None (no momentum) -- its momentum buffer, fp32, lengths in
-    floats.  x_ptrs / g_ptrs / m_ptrs are lists over the rows of per-segment device addresses."""
-
-    def __init__(self, seg_lens, x_ptrs, g_ptrs, m_ptrs, n_local):
-        nseg = len(seg_lens)
-        seg_len = np.asarray(seg_lens, dtype=np.int64)
-        tile_off = np.zeros(nseg + 1, dtype=np.int64)
-        check(lib.mx_sgd_mix_layout(seg_len.ctypes.data, nseg, n_local, tile_off.ctypes.data), "mx_sgd_mix_layout")
-
-        def table(rows):
-            t = np.zeros((nseg, n_local), dtype=np.int64)
-            for r, ptrs in enumerate(rows):
-                t[:, r] = ptrs
-            return torch.from_numpy(t).to("cuda")
-
-        self.nseg, self.n_local = nseg, n_local
-        self.tile = int(lib.mx_sgd_mix_tile(n_local))
-        self.total_tiles = int(tile_off[-1])
-        self.x_ptrs, self.g_ptrs = table(x_ptrs), table(g_ptrs)
-        self.m_ptrs = table(m_ptrs) if m_ptrs is not None else None
-        self.seg_len = torch.from_numpy(seg_len).to("cuda")
-        self.tile_off = torch.from_numpy(tile_off).to("cuda")
-        self.tune_gen = _TUNE_GEN[0]
-
-    def check_tile(self):
-        """After a knob change: the tile this layout was built for is still the kernel's (as
-        GossipEngine.mix does for Layout)."""
-        if self.tune_gen != _TUNE_GEN[0]:
-            if self.tile != lib.mx_sgd_mix_tile(self.n_local):
-                raise MXError("layout built for another fused SGD + mixing tile size")
-            self.tune_gen = _TUNE_GEN[0]
-
-    def call(self, engine, wd, mom, nesterov, zero_grads):
-        return SgdMixCall(self.x_ptrs.data_ptr(), self.g_ptrs.data_ptr(),
-                          self.m_ptrs.data_ptr() if self.m_ptrs is not None else None, self.seg_len.data_ptr(),
-                          self.tile_off.data_ptr(), engine._plan_ptr, self.total_tiles, self.nseg, engine.n_slots,
-                          engine.n_local, engine.M, engine.alpha32, float(np.float32(wd)), float(np.float32(mom)),
-                          int(bool(nesterov)), int(bool(zero_grads)), 0)
-
-
 class AdamwMixCall(ctypes.Structure):
     """mx_adamw_mix_call (include/matcha_gossip.h): the fused AdamW + mixing launch's arguments, packed once."""
     _fields_ = [("x_ptrs_dev", ctypes.c_void_p), ("g_ptrs_dev", ctypes.c_void_p), ("m_ptrs_dev", ctypes.c_void_p),
@@ -774,55 +678,6 @@ class AdamwMixCall(ctypes.Structure):
                 ("zero_grads", ctypes.c_int32)]
 
 
-class AdamwLayout:
-    """Pointer tables of the fused AdamW + mixing kernel (csrc/adamw_mix.hip): row r's copy of segment s,
-    its gradient, exp_avg and exp_avg_sq, fp32, lengths in floats, and the bias-correction table
-    (adam_bias_table) on the device.  x_ptrs / g_ptrs / m_ptrs / v_ptrs are lists over the rows of
-    per-segment device addresses."""
-
-    def __init__(self, seg_lens, x_ptrs, g_ptrs, m_ptrs, v_ptrs, n_local, bias):
-        nseg = len(seg_lens)
-        seg_len = np.asarray(seg_lens, dtype=np.int64)
-        tile_off = np.zeros(nseg + 1, dtype=np.int64)
-        check(lib.mx_adamw_mix_layout(seg_len.ctypes.data, nseg, n_local, tile_off.ctypes.data),
-              "mx_adamw_mix_layout")
-
-        def table(rows):
-            t = np.zeros((nseg, n_local), dtype=np.int64)
-            for r, ptrs in enumerate(rows):
-                t[:, r] = ptrs
-            return torch.from_numpy(t).to("cuda")
-
-        self.nseg, self.n_local = nseg, n_local
-        self.tile = int(lib.mx_adamw_mix_tile(n_local))
-        self.total_tiles = int(tile_off[-1])
-        self.x_ptrs, self.g_ptrs, self.m_ptrs, self.v_ptrs = table(x_ptrs), table(g_ptrs), table(m_ptrs), table(v_ptrs)
-        self.seg_len = torch.from_numpy(seg_len).to("cuda")
-        self.tile_off = torch.from_numpy(tile_off).to("cuda")
-        bias = np.ascontiguousarray(bias, dtype=np.float32)
-        if bias.ndim != 2 or bias.shape[1] != 2 or bias.shape[0] < 1:
-            raise ValueError("bias table: float32 [n_bias, 2]")
-        self.n_bias = int(bias.shape[0])
-        self.bias = torch.from_numpy(bias).to("cuda")
-        self.tune_gen = _TUNE_GEN[0]
-
-    def check_tile(self):
-        if self.tune_gen != _TUNE_GEN[0]:
-            if self.tile != lib.mx_adamw_mix_tile(self.n_local):
-                raise MXError("layout built for another fused AdamW + mixing tile size")
-            self.tune_gen = _TUNE_GEN[0]
-
-    def call(self, engine, betas, eps, wd, decoupled, zero_grads):
-        """betas are the Python floats: omb1 / omb2 are rounded from the fp64 values 1 - beta."""
-        b1, b2 = float(betas[0]), float(betas[1])
-        return AdamwMixCall(self.x_ptrs.data_ptr(), self.g_ptrs.data_ptr(), self.m_ptrs.data_ptr(),
-                            self.v_ptrs.data_ptr(), self.seg_len.data_ptr(), self.tile_off.data_ptr(),
-                            engine._plan_ptr, self.bias.data_ptr(), self.total_tiles, self.n_bias, self.nseg,
-                            engine.n_slots, engine.n_local, engine.M, engine.alpha32, float(np.float32(wd)),
-                            float(np.float32(1.0 - b1)), float(np.float32(b2)), float(np.float32(1.0 - b2)),
-                            float(np.float32(eps)), int(bool(decoupled)), int(bool(zero_grads)))
-
-
 class SgdBf16Call(ctypes.Structure):
     """mx_sgd_mix_bf16_call (include/matcha_gossip.h): the mixed-precision fused launch's arguments."""
     _fields_ = [("w_ptrs_dev", ctypes.c_void_p), ("g_ptrs_dev", ctypes.c_void_p), ("m_ptrs_dev", ctypes.c_void_p),
@@ -831,49 +686,6 @@ class SgdBf16Call(ctypes.Structure):
                 ("n_slots", ctypes.c_int32), ("n_local", ctypes.c_int32), ("M", ctypes.c_int32),
                 ("alpha", ctypes.c_float), ("wd", ctypes.c_float), ("mom", ctypes.c_float),
                 ("nesterov", ctypes.c_int32), ("zero_grads", ctypes.c_int32), ("pad_", ctypes.c_int32)]
-
-
-class SgdBf16Layout:
-    """Pointer tables of the mixed-precision fused kernel (csrc/sgd_mix_bf16.hip): row r's fp32 master of
-    segment s, its bfloat16 gradient, its fp32 momentum buffer (m_ptrs None without momentum) and its
-    bfloat16 model row, lengths in elements.  Each argument is a list over the rows of per-segment
-    device addresses."""
-
-    def __init__(self, seg_lens, w_ptrs, g_ptrs, m_ptrs, p_ptrs, n_local):
-        nseg = len(seg_lens)
-        seg_len = np.asarray(seg_lens, dtype=np.int64)
-        tile_off = np.zeros(nseg + 1, dtype=np.int64)
-        check(lib.mx_sgd_mix_bf16_layout(seg_len.ctypes.data, nseg, n_local, tile_off.ctypes.data),
-              "mx_sgd_mix_bf16_layout")
-
-        def table(rows):
-            t = np.zeros((nseg, n_local), dtype=np.int64)
-            for r, ptrs in enumerate(rows):
-                t[:, r] = ptrs
-            return torch.from_numpy(t).to("cuda")
-
-        self.nseg, self.n_local = nseg, n_local
-        self.tile = int(lib.mx_sgd_mix_bf16_tile(n_local))
-        self.total_tiles = int(tile_off[-1])
-        self.w_ptrs, self.g_ptrs, self.p_ptrs = table(w_ptrs), table(g_ptrs), table(p_ptrs)
-        self.m_ptrs = table(m_ptrs) if m_ptrs is not None else None
-        self.seg_len = torch.from_numpy(seg_len).to("cuda")
-        self.tile_off = torch.from_numpy(tile_off).to("cuda")
-        self.tune_gen = _TUNE_GEN[0]
-
-    def check_tile(self):
-        if self.tune_gen != _TUNE_GEN[0]:
-            if self.tile != lib.mx_sgd_mix_bf16_tile(self.n_local):
-                raise MXError("layout built for another mixed-precision fused SGD + mixing tile size")
-            self.tune_gen = _TUNE_GEN[0]
-
-    def call(self, engine, wd, mom, nesterov, zero_grads):
-        return SgdBf16Call(self.w_ptrs.data_ptr(), self.g_ptrs.data_ptr(),
-                           self.m_ptrs.data_ptr() if self.m_ptrs is not None else None, self.p_ptrs.data_ptr(),
-                           self.seg_len.data_ptr(), self.tile_off.data_ptr(), engine._plan_ptr, self.total_tiles,
-                           self.nseg, engine.n_slots, engine.n_local, engine.M, engine.alpha32,
-                           float(np.float32(wd)), float(np.float32(mom)), int(bool(nesterov)),
-                           int(bool(zero_grads)), 0)
 
 
 class AdamwBf16Call(ctypes.Structure):
@@ -888,18 +700,105 @@ class AdamwBf16Call(ctypes.Structure):
                 ("decoupled", ctypes.c_int32), ("zero_grads", ctypes.c_int32)]
 
 
-class AdamwBf16Layout:
-    """Pointer tables of the mixed-precision fused AdamW kernel (csrc/adamw_mix_bf16.hip): row r's fp32
-    master of segment s, its bfloat16 gradient, its fp32 exp_avg and exp_avg_sq and its bfloat16 model
-    row, lengths in elements, and the bias-correction table (adam_bias_table) on the device.  Each
-    pointer argument is a list over the rows of per-segment device addresses."""
+SGD_TUNE_KEYS = ("nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid")
 
-    def __init__(self, seg_lens, w_ptrs, g_ptrs, m_ptrs, v_ptrs, p_ptrs, n_local, bias):
+# the ten entry points of a fused family, as suffixes of its C base name, in FusedFamily's field order
+_FUSED_ENTRIES = ("_tile", "_layout", "_set", "_get", "", "_at", "_scaled", "_scaled_at", "_grouped", "_grouped_at")
+
+FusedFamily = collections.namedtuple(
+    "FusedFamily", "base rec tables optional adam words "
+                   "tile tile_prefix set get run run_at scaled scaled_at grouped grouped_at")
+
+
+def _family(base, rec, tables, optional, adam, words):
+    """base     -- the C base name: every entry point is base + a suffix of _FUSED_ENTRIES
+    rec      -- the ctypes mirror of its call record (mx_<family>_call)
+    tables   -- its pointer tables in the record's order: table t is the layout's `t_ptrs` and the
+                record's `t_ptrs_dev`
+    optional -- the table that may be absent (None -> NULL): SGD's momentum
+    adam     -- the record carries a bias table and the launches an optimizer-step argument
+    words    -- what its messages call the kernel"""
+    return FusedFamily(base, rec, tuple(tables.split()), optional, adam, words,
+                       *(getattr(lib, base + suffix) for suffix in _FUSED_ENTRIES))
+
+
+# (optimizer, mixed precision) -> family; everything below reads this table
+FAMILIES = {
+    ("sgd", False): _family("mx_sgd_mix", SgdMixCall, "x g m", "m", False, "fused SGD + mixing"),
+    ("sgd", True): _family("mx_sgd_mix_bf16", SgdBf16Call, "w g m p", "m", False,
+                           "mixed-precision fused SGD + mixing"),
+    ("adamw", False): _family("mx_adamw_mix", AdamwMixCall, "x g m v", None, True, "fused AdamW + mixing"),
+    ("adamw", True): _family("mx_adamw_mix_bf16", AdamwBf16Call, "w g m v p", None, True,
+                             "mixed-precision fused AdamW + mixing"),
+}
+
+
+def _tuning_pair(fam):
+    """(<family>_tuning, set_<family>_tuning) of a fused family.  None of the knobs changes the tile
+    (include/matcha_gossip.h), so a set invalidates no layout."""
+    def tuning():
+        return {k: int(fam.get(k.encode())) for k in SGD_TUNE_KEYS}
+
+    def set_tuning(**knobs):
+        for k, v in knobs.items():
+            check(fam.set(k.encode(), int(v)), fam.base + "_set")
+
+    stem = fam.base[len("mx_"):]
+    tuning.__name__ = tuning.__qualname__ = stem + "_tuning"
+    set_tuning.__name__ = set_tuning.__qualname__ = "set_" + stem + "_tuning"
+    tuning.__doc__ = f"Current knobs of the {fam.words} kernel (include/matcha_gossip.h, {fam.base}_set)."
+    return tuning, set_tuning
+
+
+sgd_mix_tuning, set_sgd_mix_tuning = _tuning_pair(FAMILIES["sgd", False])
+sgd_mix_bf16_tuning, set_sgd_mix_bf16_tuning = _tuning_pair(FAMILIES["sgd", True])
+adamw_mix_tuning, set_adamw_mix_tuning = _tuning_pair(FAMILIES["adamw", False])
+adamw_mix_bf16_tuning, set_adamw_mix_bf16_tuning = _tuning_pair(FAMILIES["adamw", True])
+
+
+def _f32(v):
+    return float(np.float32(v))
+
+
+def sgd_hyper(wd, mom, nesterov, zero_grads):
+    """The SGD records' words after alpha: wd, mom, nesterov, zero_grads, pad_."""
+    return _f32(wd), _f32(mom), int(bool(nesterov)), int(bool(zero_grads)), 0
+
+
+def adam_hyper(betas, eps, wd, decoupled, zero_grads):
+    """The Adam records' words after alpha: wd, omb1, beta2, omb2, eps, decoupled, zero_grads.  betas are
+    the Python floats: omb1 / omb2 are rounded from the fp64 values 1 - beta."""
+    b1, b2 = float(betas[0]), float(betas[1])
+    return (_f32(wd), _f32(1.0 - b1), _f32(b2), _f32(1.0 - b2), _f32(eps), int(bool(decoupled)),
+            int(bool(zero_grads)))
+
+
+def pack_call(fam, tables, seg_len, tile_off, plan, bias, total_tiles, n_bias, nseg, n_slots, n_local, M, alpha32,
+              hyper):
+    """The call record of family `fam`, a pure function of integers and floats: `tables` are the device
+    addresses of its pointer tables in fam.tables order (None: an absent table, NULL), seg_len / tile_off
+    / plan / bias device addresses (bias and n_bias count for the Adam families only), `hyper` the words
+    of sgd_hyper / adam_hyper."""
+    head = (*tables, seg_len, tile_off, plan)
+    if fam.adam:
+        return fam.rec(*head, bias, total_tiles, n_bias, nseg, n_slots, n_local, M, alpha32, *hyper)
+    return fam.rec(*head, total_tiles, nseg, n_slots, n_local, M, alpha32, *hyper)
+
+
+class FusedLayout:
+    """Pointer tables of a fused optimizer + mixing kernel (`family`, set by the four classes below): one
+    int64 device table [nseg, n_local] per pointer list -- row r's copy of segment s -- as `<t>_ptrs` for
+    t in family.tables, the segment lengths (in elements) and the tile prefix; for the Adam families the
+    bias-correction table (adam_bias_table) too.  The tile depends on n_local alone (no knob enters it), so
+    a layout stays valid for its lifetime."""
+    family = None
+
+    def __init__(self, seg_lens, tables, n_local, bias=None):
+        fam = self.family
         nseg = len(seg_lens)
         seg_len = np.asarray(seg_lens, dtype=np.int64)
         tile_off = np.zeros(nseg + 1, dtype=np.int64)
-        check(lib.mx_adamw_mix_bf16_layout(seg_len.ctypes.data, nseg, n_local, tile_off.ctypes.data),
-              "mx_adamw_mix_bf16_layout")
+        check(fam.tile_prefix(seg_len.ctypes.data, nseg, n_local, tile_off.ctypes.data), fam.base + "_layout")
 
         def table(rows):
             t = np.zeros((nseg, n_local), dtype=np.int64)
@@ -908,35 +807,97 @@ class AdamwBf16Layout:
             return torch.from_numpy(t).to("cuda")
 
         self.nseg, self.n_local = nseg, n_local
-        self.tile = int(lib.mx_adamw_mix_bf16_tile(n_local))
+        self.tile = int(fam.tile(n_local))
         self.total_tiles = int(tile_off[-1])
-        self.w_ptrs, self.g_ptrs, self.p_ptrs = table(w_ptrs), table(g_ptrs), table(p_ptrs)
-        self.m_ptrs, self.v_ptrs = table(m_ptrs), table(v_ptrs)
+        for t, rows in zip(fam.tables, tables):
+            setattr(self, t + "_ptrs", None if rows is None and t == fam.optional else table(rows))
         self.seg_len = torch.from_numpy(seg_len).to("cuda")
         self.tile_off = torch.from_numpy(tile_off).to("cuda")
-        bias = np.ascontiguousarray(bias, dtype=np.float32)
-        if bias.ndim != 2 or bias.shape[1] != 2 or bias.shape[0] < 1:
-            raise ValueError("bias table: float32 [n_bias, 2]")
-        self.n_bias = int(bias.shape[0])
-        self.bias = torch.from_numpy(bias).to("cuda")
-        self.tune_gen = _TUNE_GEN[0]
+        self.bias, self.n_bias = None, 0
+        if fam.adam:
+            bias = np.ascontiguousarray(bias, dtype=np.float32)
+            if bias.ndim != 2 or bias.shape[1] != 2 or bias.shape[0] < 1:
+                raise ValueError("bias table: float32 [n_bias, 2]")
+            self.n_bias = int(bias.shape[0])
+            self.bias = torch.from_numpy(bias).to("cuda")
 
-    def check_tile(self):
-        if self.tune_gen != _TUNE_GEN[0]:
-            if self.tile != lib.mx_adamw_mix_bf16_tile(self.n_local):
-                raise MXError("layout built for another mixed-precision fused AdamW + mixing tile size")
-            self.tune_gen = _TUNE_GEN[0]
+    def _pack(self, engine, hyper):
+        """pack_call over this layout's addresses; n_slots, n_local and M are the engine's"""
+        fam = self.family
+        tables = [getattr(self, t + "_ptrs") for t in fam.tables]
+        return pack_call(fam, [t.data_ptr() if t is not None else None for t in tables], self.seg_len.data_ptr(),
+                         self.tile_off.data_ptr(), engine._plan_ptr, self.bias.data_ptr() if fam.adam else None,
+                         self.total_tiles, self.n_bias, self.nseg, engine.n_slots, engine.n_local, engine.M,
+                         engine.alpha32, hyper)
+
+
+class SgdLayout(FusedLayout):
+    """csrc/sgd_mix.hip: row r's copy of segment s, its gradient and -- unless m_ptrs is None (no momentum)
+    -- its momentum buffer, fp32, lengths in floats.  x_ptrs / g_ptrs / m_ptrs are lists over the rows of
+    per-segment device addresses."""
+    family = FAMILIES["sgd", False]
+
+    def __init__(self, seg_lens, x_ptrs, g_ptrs, m_ptrs, n_local):
+        super().__init__(seg_lens, (x_ptrs, g_ptrs, m_ptrs), n_local)
+
+    def call(self, engine, wd, mom, nesterov, zero_grads):
+        return self._pack(engine, sgd_hyper(wd, mom, nesterov, zero_grads))
+
+
+class SgdBf16Layout(FusedLayout):
+    """csrc/sgd_mix_bf16.hip: row r's fp32 master of segment s, its bfloat16 gradient, its fp32 momentum
+    buffer (m_ptrs None without momentum) and its bfloat16 model row, lengths in elements."""
+    family = FAMILIES["sgd", True]
+
+    def __init__(self, seg_lens, w_ptrs, g_ptrs, m_ptrs, p_ptrs, n_local):
+        super().__init__(seg_lens, (w_ptrs, g_ptrs, m_ptrs, p_ptrs), n_local)
+
+    call = SgdLayout.call
+
+
+class AdamwLayout(FusedLayout):
+    """csrc/adamw_mix.hip: row r's copy of segment s, its gradient, exp_avg and exp_avg_sq, fp32, lengths
+    in floats, and the bias-correction table on the device."""
+    family = FAMILIES["adamw", False]
+
+    def __init__(self, seg_lens, x_ptrs, g_ptrs, m_ptrs, v_ptrs, n_local, bias):
+        super().__init__(seg_lens, (x_ptrs, g_ptrs, m_ptrs, v_ptrs), n_local, bias)
 
     def call(self, engine, betas, eps, wd, decoupled, zero_grads):
-        """betas are the Python floats: omb1 / omb2 are rounded from the fp64 values 1 - beta."""
-        b1, b2 = float(betas[0]), float(betas[1])
-        return AdamwBf16Call(self.w_ptrs.data_ptr(), self.g_ptrs.data_ptr(), self.m_ptrs.data_ptr(),
-                             self.v_ptrs.data_ptr(), self.p_ptrs.data_ptr(), self.seg_len.data_ptr(),
-                             self.tile_off.data_ptr(), engine._plan_ptr, self.bias.data_ptr(), self.total_tiles,
-                             self.n_bias, self.nseg, engine.n_slots, engine.n_local, engine.M, engine.alpha32,
-                             float(np.float32(wd)), float(np.float32(1.0 - b1)), float(np.float32(b2)),
-                             float(np.float32(1.0 - b2)), float(np.float32(eps)), int(bool(decoupled)),
-                             int(bool(zero_grads)))
+        """betas are the Python floats (adam_hyper)"""
+        return self._pack(engine, adam_hyper(betas, eps, wd, decoupled, zero_grads))
+
+
+class AdamwBf16Layout(FusedLayout):
+    """csrc/adamw_mix_bf16.hip: row r's fp32 master of segment s, its bfloat16 gradient, its fp32 exp_avg
+    and exp_avg_sq and its bfloat16 model row, lengths in elements, and the bias-correction table."""
+    family = FAMILIES["adamw", True]
+
+    def __init__(self, seg_lens, w_ptrs, g_ptrs, m_ptrs, v_ptrs, p_ptrs, n_local, bias):
+        super().__init__(seg_lens, (w_ptrs, g_ptrs, m_ptrs, v_ptrs, p_ptrs), n_local, bias)
+
+    call = AdamwLayout.call
+
+
+FUSED_LAYOUTS = {("sgd", False): SgdLayout, ("sgd", True): SgdBf16Layout,          # keyed as FAMILIES
+                 ("adamw", False): AdamwLayout, ("adamw", True): AdamwBf16Layout}
+
+# what attach_sgd / attach_adamw hold in _sgd / _adamw: the layout, the packed call record and its address,
+# then the family's own fields side by side, so that a step reads its launch functions in one lookup
+FusedState = collections.namedtuple("FusedState", ("layout", "call", "addr") + FusedFamily._fields)
+
+# optimizer -> its name in messages, the other optimizer, and how attach_* says that bfloat16 rows need masters
+_OPTIMIZER_WORDS = {
+    "sgd": ("SGD", "adamw", "a bfloat16 group needs fp32 master weights for its SGD step"),
+    "adamw": ("AdamW", "sgd", "bfloat16 groups need fp32 master weights under AdamW"),
+}
+
+
+def _attached(state, opt):
+    """The FusedState in a group's _sgd / _adamw slot, or the error of a group without one."""
+    if state is None:
+        raise MXError(f"no {_OPTIMIZER_WORDS[opt][0]} state: call attach_{opt}() first")
+    return state
 
 
 class GradNormCall(ctypes.Structure):
@@ -1496,6 +1457,125 @@ class VirtualWorkerGroup:
         self._clip.enqueue(stream_ptr(stream))
         return self.grad_norms
 
+    def _fused_family(self, opt, master_weights, clip_grad_norm):
+        """What attach_sgd / attach_adamw refuse alike, before anything is allocated; returns the layout
+        class of (opt, mixed precision) and the checked clip norm."""
+        who = "attach_" + opt
+        name, other, needs_master = _OPTIMIZER_WORDS[opt]
+        clip = clip_value(clip_grad_norm, who)
+        if getattr(self, "_" + opt) is not None:
+            raise RuntimeError(f"{who}: already attached")
+        if getattr(self, "_" + other) is not None:
+            raise RuntimeError(f"{who}: the group already carries {_OPTIMIZER_WORDS[other][0]} state (attach_{other})")
+        if master_weights and self.dtype != torch.bfloat16:
+            raise ValueError(f"{who}: master_weights=True is for bfloat16 groups; fp32 rows are their own masters")
+        if self.dtype != torch.float32 and not master_weights:
+            raise NotImplementedError(f"{who}: {needs_master}: pass master_weights=True (the fp32 fused kernel does "
+                                      "not take bfloat16 rows)")
+        if self.engine.comm is not None or self.engine.max_remote:
+            raise NotImplementedError(f"{who}: one GPU only (nranks = 1, no transport): the partners' updated "
+                                      "rows must exist before any exchange")
+        if self._chunk_cols:
+            raise NotImplementedError(f"{who}: not with chunk_cols (the column-pipelined cross-GPU exchange)")
+        cls = FUSED_LAYOUTS[opt, bool(master_weights)]
+        if cls.family.tile(self.n_local) <= 0 or self.engine.M > 32:
+            raise NotImplementedError(f"{who}: {self.n_local} local rows / {self.engine.M} matchings exceed the "
+                                      "fused kernel's 64 rows / 32 matchings")
+        return who, cls, clip
+
+    def _state_arena(self):
+        return torch.zeros((self.n_local, self.ld), dtype=torch.float32, device="cuda")
+
+    def _attach_fused(self, checked, param_groups, state, bias, hyper, call_args):
+        """What attach_sgd / attach_adamw build alike once their own hyperparameters are checked (`checked`
+        is what _fused_family returned): the gradient arena, the masters of a mixed-precision group, the
+        layout over them and the optimizer's `state` arenas ({table name: arena or None}), the parameter
+        groups, the call record (layout.call(engine, *call_args)), the adopted parameters' .grad views,
+        lr_dev and the clip state.  Returns the FusedState for _sgd / _adamw."""
+        who, cls, clip = checked
+        fam = cls.family
+        self.grad_arena = torch.zeros((self.n_local, self.ld), dtype=self.dtype, device="cuda")
+        self.grads = self.grad_arena[:, :self.numel]
+        self.master_arena = self.master_rows = None
+        # x: the fp32 group's rows, their own masters; w / p: a bfloat16 group's fp32 masters and its rows
+        arenas = dict(state, g=self.grad_arena, x=self.arena, p=self.arena)
+        if "w" in fam.tables:
+            self.master_arena = self.arena.to(torch.float32)          # the exact widening, tails (zeros) included
+            self.master_rows = self.master_arena[:, :self.numel]
+            arenas["w"] = self.master_arena
+        tables = [arenas[t] for t in fam.tables]
+        tables = [None if a is None else [[a[r].data_ptr()] for r in range(self.n_local)] for a in tables]
+        lay = cls([self.numel], *tables, self.n_local, *([bias] if fam.adam else []))
+        self._attach_groups(param_groups, hyper["weight_decay"], who)
+        call = lay.call(self.engine, *call_args)
+        if self._adopted is not None:
+            for r, m in enumerate(self._adopted):
+                off = 0
+                for p in _params(m):
+                    k = p.numel()
+                    p.grad = self.grad_arena[r, off:off + k].view(p.shape)
+                    off += k
+        self.lr_dev = torch.zeros(1, dtype=torch.float32, device="cuda")   # the device rounds' learning rate
+        if self.param_runs is not None:      # groups are hyperparameters too; without them the dict is as before
+            hyper["param_groups"] = self.param_runs
+        self._attach_clip(lay, clip)
+        return FusedState(lay, call, ctypes.addressof(call), *fam)
+
+    def _fused_step(self, st, it, lr, stream):
+        """sgd_step / adamw_step: the norm launches of a clipping group, then ONE fused launch through the
+        entry point of the group's mode -- parameter groups (_grouped, with the clip factors or NULL),
+        else clipping (_scaled), else the plain one.  The mode is read at call time."""
+        it = self.engine.round_index(it)
+        s = stream_ptr(stream)
+        args = (it, self.opt_step + 1, lr, None, s) if st.adam else (it, lr, None, s)
+        clip = self._clip
+        if self._runs is not None:               # per-group decay / lr scale (with the clip factors, if any)
+            if clip is not None:
+                clip.enqueue(s)
+            rc = st.grouped(st.addr, self._runs.addr, clip.scale_ptr if clip is not None else None, *args)
+        elif clip is not None:                   # the norm launches, then the launch that applies the factors
+            clip.enqueue(s)
+            rc = st.scaled(st.addr, clip.scale_ptr, *args)
+        else:
+            rc = st.run(st.addr, *args)
+        if rc:
+            check(rc, st.base)
+        if st.adam:
+            self.opt_step += 1
+        return bool(self.engine.any_active[it])
+
+    def _fused_device_round(self, st, stream):
+        """sgd_device_round / adamw_device_round: _fused_step's three modes through the _at entry points,
+        then the counters' advance."""
+        s = stream_ptr(stream)
+        it = self.iter_dev.data_ptr()
+        lr = self.lr_dev.data_ptr()
+        args = (it, self.engine.T, self.opt_step_dev.data_ptr(), 0.0, lr, s) if st.adam else \
+               (it, self.engine.T, 0.0, lr, s)
+        clip = self._clip
+        if self._runs is not None:
+            if clip is not None:
+                clip.enqueue(s)
+            check(st.grouped_at(st.addr, self._runs.addr, clip.scale_ptr if clip is not None else None, *args),
+                  st.base + "_grouped_at")
+        elif clip is not None:
+            clip.enqueue(s)
+            check(st.scaled_at(st.addr, clip.scale_ptr, *args), st.base + "_scaled_at")
+        else:
+            check(st.run_at(st.addr, *args), st.base + "_at")
+        check(lib.mx_iter_advance(it, 1, s), "mx_iter_advance")
+        if st.adam:
+            check(lib.mx_iter_advance(self.opt_step_dev.data_ptr(), 1, s), "mx_iter_advance")
+
+    def _fused_communicate(self, step, lr):
+        it = self.iter
+        self.iter += 1
+        torch.cuda.synchronize()
+        tic = time.time()
+        step(it, lr)
+        self.wait_round()
+        return time.time() - tic
+
     def attach_sgd(self, momentum=0.0, weight_decay=0.0, nesterov=False, zero_grads=True, master_weights=False,
                    clip_grad_norm=None, param_groups=None):
         """Give the group torch.optim.SGD's state (dampening 0) so that one launch per iteration
@@ -1543,71 +1623,18 @@ class VirtualWorkerGroup:
         every step then goes through the _grouped entry points; None keeps today's launches.  Groups
         are hyperparameters, not state: checkpoints are unchanged.  Momentum, nesterov and the clip
         norm (one per worker over all its groups) are the whole row's."""
-        clip = clip_value(clip_grad_norm, "attach_sgd")
-        if self._sgd is not None:
-            raise RuntimeError("attach_sgd: already attached")
-        if self._adamw is not None:
-            raise RuntimeError("attach_sgd: the group already carries AdamW state (attach_adamw)")
-        if master_weights and self.dtype != torch.bfloat16:
-            raise ValueError("attach_sgd: master_weights=True is for bfloat16 groups; fp32 rows are their own masters")
-        if self.dtype != torch.float32 and not master_weights:
-            raise NotImplementedError("attach_sgd: a bfloat16 group needs fp32 master weights for its SGD step: "
-                                      "pass master_weights=True (the fp32 fused kernel does not take bfloat16 rows)")
-        mixed = bool(master_weights)
-        if self.engine.comm is not None or self.engine.max_remote:
-            raise NotImplementedError("attach_sgd: one GPU only (nranks = 1, no transport): the partners' updated "
-                                      "rows must exist before any exchange")
-        if self._chunk_cols:
-            raise NotImplementedError("attach_sgd: not with chunk_cols (the column-pipelined cross-GPU exchange)")
+        checked = self._fused_family("sgd", master_weights, clip_grad_norm)
         momentum, weight_decay = float(momentum), float(weight_decay)
         if nesterov and momentum == 0.0:
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        tile = lib.mx_sgd_mix_bf16_tile(self.n_local) if mixed else lib.mx_sgd_mix_tile(self.n_local)
-        if tile <= 0 or self.engine.M > 32:
-            raise NotImplementedError(f"attach_sgd: {self.n_local} local rows / {self.engine.M} matchings exceed the "
-                                      "fused kernel's 64 rows / 32 matchings")
-        self.grad_arena = torch.zeros((self.n_local, self.ld), dtype=self.dtype, device="cuda")
-        self.grads = self.grad_arena[:, :self.numel]
         self.mom_arena = self.momentum_rows = None
         if momentum != 0.0:
-            self.mom_arena = torch.zeros((self.n_local, self.ld), dtype=torch.float32, device="cuda")
+            self.mom_arena = self._state_arena()
             self.momentum_rows = self.mom_arena[:, :self.numel]
-        self.master_arena = self.master_rows = None
-
-        def row_ptrs(arena):
-            return [[arena[r].data_ptr()] for r in range(self.n_local)]
-
-        if mixed:
-            self.master_arena = self.arena.to(torch.float32)          # the exact widening, tails (zeros) included
-            self.master_rows = self.master_arena[:, :self.numel]
-            lay = SgdBf16Layout([self.numel], row_ptrs(self.master_arena), row_ptrs(self.grad_arena),
-                                row_ptrs(self.mom_arena) if momentum != 0.0 else None,
-                                [[p] for p in self._row_ptrs], self.n_local)
-        else:
-            lay = SgdLayout([self.numel], [[p] for p in self._row_ptrs], row_ptrs(self.grad_arena),
-                            row_ptrs(self.mom_arena) if momentum != 0.0 else None, self.n_local)
-        self._attach_groups(param_groups, weight_decay, "attach_sgd")
-        call = lay.call(self.engine, weight_decay, momentum, nesterov, zero_grads)
-        if self._adopted is not None:
-            for r, m in enumerate(self._adopted):
-                off = 0
-                for p in _params(m):
-                    k = p.numel()
-                    p.grad = self.grad_arena[r, off:off + k].view(p.shape)
-                    off += k
-        self.lr_dev = torch.zeros(1, dtype=torch.float32, device="cuda")   # sgd_device_round's learning rate
         self.sgd_hyper = {"momentum": momentum, "weight_decay": weight_decay, "nesterov": bool(nesterov),
                           "zero_grads": bool(zero_grads)}
-        if self.param_runs is not None:      # groups are hyperparameters too; without them the dict is as before
-            self.sgd_hyper["param_groups"] = self.param_runs
-        self._sgd = (lay, call, ctypes.addressof(call))
-        self._sgd_fn = (_sgd_mix_bf16, lib.mx_sgd_mix_bf16_at, "mx_sgd_mix_bf16") if mixed else \
-                       (_sgd_mix, lib.mx_sgd_mix_at, "mx_sgd_mix")
-        self._sgd_fn_scaled = (lib.mx_sgd_mix_bf16_scaled, lib.mx_sgd_mix_bf16_scaled_at) if mixed else \
-                              (lib.mx_sgd_mix_scaled, lib.mx_sgd_mix_scaled_at)
-        self._sgd_fn_grouped = (lib.mx_sgd_mix_bf16_grouped, lib.mx_sgd_mix_bf16_grouped_at) if mixed else \
-                               (lib.mx_sgd_mix_grouped, lib.mx_sgd_mix_grouped_at)
-        self._attach_clip(lay, clip)
+        self._sgd = self._attach_fused(checked, param_groups, {"m": self.mom_arena}, None, self.sgd_hyper,
+                                       (weight_decay, momentum, nesterov, zero_grads))
 
     def master_from_rows(self):
         """Redo the masters as the exact widening of `rows` (attach_sgd / attach_adamw(master_weights=True) groups).
@@ -1621,65 +1648,25 @@ class VirtualWorkerGroup:
             self.master_rows.copy_(self.rows)
 
     def _sgd_state(self):
-        if self._sgd is None:
-            raise MXError("no SGD state: call attach_sgd() first")
-        self._sgd[0].check_tile()
-        return self._sgd[2]
+        return _attached(self._sgd, "sgd").addr
 
     def sgd_step(self, it, lr, stream=None):
         """Enqueue ONE launch: every local worker's SGD update at learning rate `lr`, then round
         `it`'s mix of the updated rows.  Always launches -- an all-zero round is the SGD step
         alone -- and returns whether the round mixed."""
-        call = self._sgd_state()
-        it = self.engine.round_index(it)
-        if self._runs is not None:               # per-group decay / lr scale (with the clip factors, if any)
-            s = stream_ptr(stream)
-            if self._clip is not None:
-                self._clip.enqueue(s)
-            rc = self._sgd_fn_grouped[0](call, self._runs.addr, self._clip.scale_ptr if self._clip else None, it, lr,
-                                         None, s)
-        elif self._clip is not None:             # the norm launches, then the launch that applies the factors
-            s = stream_ptr(stream)
-            self._clip.enqueue(s)
-            rc = self._sgd_fn_scaled[0](call, self._clip.scale_ptr, it, lr, None, s)
-        else:
-            rc = self._sgd_fn[0](call, it, lr, None, stream_ptr(stream))
-        if rc:
-            check(rc, self._sgd_fn[2])
-        return bool(self.engine.any_active[it])
+        return self._fused_step(_attached(self._sgd, "sgd"), it, lr, stream)
 
     def sgd_device_round(self, stream=None):
         """Graph-replayable sgd_step: the round is read from `self.iter_dev` and the learning rate
         from `self.lr_dev` (a 1-element fp32 CUDA tensor) when the kernel runs, then the counter is
         advanced, so one captured launch pair serves every iteration and every learning rate.  A
         counter outside the schedule makes the launch a no-op: no SGD step either."""
-        call = self._sgd_state()
-        s = stream_ptr(stream)
-        if self._runs is not None:
-            if self._clip is not None:
-                self._clip.enqueue(s)
-            check(self._sgd_fn_grouped[1](call, self._runs.addr, self._clip.scale_ptr if self._clip else None,
-                                          self.iter_dev.data_ptr(), self.engine.T, 0.0, self.lr_dev.data_ptr(), s),
-                  self._sgd_fn[2] + "_grouped_at")
-        elif self._clip is not None:
-            self._clip.enqueue(s)
-            check(self._sgd_fn_scaled[1](call, self._clip.scale_ptr, self.iter_dev.data_ptr(), self.engine.T, 0.0,
-                                         self.lr_dev.data_ptr(), s), self._sgd_fn[2] + "_scaled_at")
-        else:
-            check(self._sgd_fn[1](call, self.iter_dev.data_ptr(), self.engine.T, 0.0, self.lr_dev.data_ptr(), s),
-                  self._sgd_fn[2] + "_at")
-        check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, s), "mx_iter_advance")
+        self._fused_device_round(_attached(self._sgd, "sgd"), stream)
 
     def sgd_communicate(self, lr):
         """optimizer.step() + zero_grad() + communicate() of every worker at the group's own
         iteration counter, as one launch; returns seconds like communicate()."""
-        it = self.iter
-        self.iter += 1
-        torch.cuda.synchronize()
-        tic = time.time()
-        self.sgd_step(it, lr)
-        self.wait_round()
-        return time.time() - tic
+        return self._fused_communicate(self.sgd_step, lr)
 
     # ------------------------------------------------------------------ fused AdamW + mixing
     def attach_adamw(self, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled=True, zero_grads=True,
@@ -1713,106 +1700,31 @@ class VirtualWorkerGroup:
         "no decay for biases and normalisation scales" is
         [{"params": lambda name, p: p.ndim <= 1, "weight_decay": 0.0}].  Betas and eps are the whole
         row's.  `param_runs` holds the resolved runs; None keeps today's launches."""
-        clip = clip_value(clip_grad_norm, "attach_adamw")
-        if self._adamw is not None:
-            raise RuntimeError("attach_adamw: already attached")
-        if self._sgd is not None:
-            raise RuntimeError("attach_adamw: the group already carries SGD state (attach_sgd)")
-        if master_weights and self.dtype != torch.bfloat16:
-            raise ValueError("attach_adamw: master_weights=True is for bfloat16 groups; fp32 rows are their own masters")
-        if self.dtype != torch.float32 and not master_weights:
-            raise NotImplementedError("attach_adamw: bfloat16 groups need fp32 master weights under AdamW: pass "
-                                      "master_weights=True (the fp32 fused kernel does not take bfloat16 rows)")
-        mixed = bool(master_weights)
-        if self.engine.comm is not None or self.engine.max_remote:
-            raise NotImplementedError("attach_adamw: one GPU only (nranks = 1, no transport): the partners' updated "
-                                      "rows must exist before any exchange")
-        if self._chunk_cols:
-            raise NotImplementedError("attach_adamw: not with chunk_cols (the column-pipelined cross-GPU exchange)")
-        tile = lib.mx_adamw_mix_bf16_tile(self.n_local) if mixed else lib.mx_adamw_mix_tile(self.n_local)
-        if tile <= 0 or self.engine.M > 32:
-            raise NotImplementedError(f"attach_adamw: {self.n_local} local rows / {self.engine.M} matchings exceed "
-                                      "the fused kernel's 64 rows / 32 matchings")
+        checked = self._fused_family("adamw", master_weights, clip_grad_norm)
         betas = (float(betas[0]), float(betas[1]))
         eps, weight_decay = float(eps), float(weight_decay)
         if eps < 0.0 or weight_decay < 0.0:
             raise ValueError("attach_adamw: eps and weight_decay must not be negative")
         bias = adam_bias_table(*betas)                               # ValueError for betas it cannot serve
-
-        def arena():
-            return torch.zeros((self.n_local, self.ld), dtype=torch.float32, device="cuda")
-
-        def row_ptrs(a):
-            return [[a[r].data_ptr()] for r in range(self.n_local)]
-
-        self.exp_avg_arena, self.exp_avg_sq_arena = arena(), arena()
-        self.grad_arena = torch.zeros((self.n_local, self.ld), dtype=self.dtype, device="cuda")
-        self.grads = self.grad_arena[:, :self.numel]
+        self.exp_avg_arena, self.exp_avg_sq_arena = self._state_arena(), self._state_arena()
         self.exp_avg_rows = self.exp_avg_arena[:, :self.numel]
         self.exp_avg_sq_rows = self.exp_avg_sq_arena[:, :self.numel]
-        self.master_arena = self.master_rows = None
-        if mixed:
-            self.master_arena = self.arena.to(torch.float32)          # the exact widening, tails (zeros) included
-            self.master_rows = self.master_arena[:, :self.numel]
-            lay = AdamwBf16Layout([self.numel], row_ptrs(self.master_arena), row_ptrs(self.grad_arena),
-                                  row_ptrs(self.exp_avg_arena), row_ptrs(self.exp_avg_sq_arena),
-                                  [[p] for p in self._row_ptrs], self.n_local, bias)
-        else:
-            lay = AdamwLayout([self.numel], [[p] for p in self._row_ptrs], row_ptrs(self.grad_arena),
-                              row_ptrs(self.exp_avg_arena), row_ptrs(self.exp_avg_sq_arena), self.n_local, bias)
-        self._attach_groups(param_groups, weight_decay, "attach_adamw")
-        call = lay.call(self.engine, betas, eps, weight_decay, decoupled, zero_grads)
-        if self._adopted is not None:
-            for r, m in enumerate(self._adopted):
-                off = 0
-                for p in _params(m):
-                    k = p.numel()
-                    p.grad = self.grad_arena[r, off:off + k].view(p.shape)
-                    off += k
-        self.lr_dev = torch.zeros(1, dtype=torch.float32, device="cuda")   # adamw_device_round's learning rate
-        self.opt_step = 0
-        self.opt_step_dev = torch.ones(1, dtype=torch.int64, device="cuda")
         self.adamw_hyper = {"betas": betas, "eps": eps, "weight_decay": weight_decay, "decoupled": bool(decoupled),
                             "zero_grads": bool(zero_grads)}
-        if self.param_runs is not None:      # groups are hyperparameters too; without them the dict is as before
-            self.adamw_hyper["param_groups"] = self.param_runs
-        self._adamw = (lay, call, ctypes.addressof(call))
-        self._adamw_fn = (_adamw_mix_bf16, lib.mx_adamw_mix_bf16_at, "mx_adamw_mix_bf16") if mixed else \
-                         (_adamw_mix, lib.mx_adamw_mix_at, "mx_adamw_mix")
-        self._adamw_fn_scaled = (lib.mx_adamw_mix_bf16_scaled, lib.mx_adamw_mix_bf16_scaled_at) if mixed else \
-                                (lib.mx_adamw_mix_scaled, lib.mx_adamw_mix_scaled_at)
-        self._adamw_fn_grouped = (lib.mx_adamw_mix_bf16_grouped, lib.mx_adamw_mix_bf16_grouped_at) if mixed else \
-                                 (lib.mx_adamw_mix_grouped, lib.mx_adamw_mix_grouped_at)
-        self._attach_clip(lay, clip)
+        state = self._attach_fused(checked, param_groups, {"m": self.exp_avg_arena, "v": self.exp_avg_sq_arena},
+                                   bias, self.adamw_hyper, (betas, eps, weight_decay, decoupled, zero_grads))
+        self.opt_step = 0
+        self.opt_step_dev = torch.ones(1, dtype=torch.int64, device="cuda")
+        self._adamw = state
 
     def _adamw_state(self):
-        if self._adamw is None:
-            raise MXError("no AdamW state: call attach_adamw() first")
-        self._adamw[0].check_tile()
-        return self._adamw[2]
+        return _attached(self._adamw, "adamw").addr
 
     def adamw_step(self, it, lr, stream=None):
         """Enqueue ONE launch: every local worker's AdamW update number opt_step + 1 at learning rate
         `lr`, then round `it`'s mix of the updated rows; opt_step += 1.  Always launches -- an
         all-zero round is the optimizer step alone -- and returns whether the round mixed."""
-        call = self._adamw_state()
-        it = self.engine.round_index(it)
-        if self._runs is not None:               # per-group decay / lr scale (with the clip factors, if any)
-            s = stream_ptr(stream)
-            if self._clip is not None:
-                self._clip.enqueue(s)
-            rc = self._adamw_fn_grouped[0](call, self._runs.addr, self._clip.scale_ptr if self._clip else None, it,
-                                           self.opt_step + 1, lr, None, s)
-        elif self._clip is not None:             # the norm launches, then the launch that applies the factors
-            s = stream_ptr(stream)
-            self._clip.enqueue(s)
-            rc = self._adamw_fn_scaled[0](call, self._clip.scale_ptr, it, self.opt_step + 1, lr, None, s)
-        else:
-            rc = self._adamw_fn[0](call, it, self.opt_step + 1, lr, None, stream_ptr(stream))
-        if rc:
-            check(rc, self._adamw_fn[2])
-        self.opt_step += 1
-        return bool(self.engine.any_active[it])
+        return self._fused_step(_attached(self._adamw, "adamw"), it, lr, stream)
 
     def adamw_device_round(self, stream=None):
         """Graph-replayable adamw_step: the round is read from `self.iter_dev`, the optimizer step from
@@ -1821,35 +1733,12 @@ class VirtualWorkerGroup:
         captured launch triple serves every iteration.  A round counter outside the schedule or a
         step below 1 makes the launch a no-op.  `self.opt_step` (adamw_step's host counter) is not
         touched."""
-        call = self._adamw_state()
-        s = stream_ptr(stream)
-        if self._runs is not None:
-            if self._clip is not None:
-                self._clip.enqueue(s)
-            check(self._adamw_fn_grouped[1](call, self._runs.addr, self._clip.scale_ptr if self._clip else None,
-                                            self.iter_dev.data_ptr(), self.engine.T, self.opt_step_dev.data_ptr(), 0.0,
-                                            self.lr_dev.data_ptr(), s), self._adamw_fn[2] + "_grouped_at")
-        elif self._clip is not None:
-            self._clip.enqueue(s)
-            check(self._adamw_fn_scaled[1](call, self._clip.scale_ptr, self.iter_dev.data_ptr(), self.engine.T,
-                                           self.opt_step_dev.data_ptr(), 0.0, self.lr_dev.data_ptr(), s),
-                  self._adamw_fn[2] + "_scaled_at")
-        else:
-            check(self._adamw_fn[1](call, self.iter_dev.data_ptr(), self.engine.T, self.opt_step_dev.data_ptr(), 0.0,
-                                    self.lr_dev.data_ptr(), s), self._adamw_fn[2] + "_at")
-        check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, s), "mx_iter_advance")
-        check(lib.mx_iter_advance(self.opt_step_dev.data_ptr(), 1, s), "mx_iter_advance")
+        self._fused_device_round(_attached(self._adamw, "adamw"), stream)
 
     def adamw_communicate(self, lr):
         """optimizer.step() + zero_grad() + communicate() of every worker at the group's own
         iteration counter, as one launch; returns seconds like communicate()."""
-        it = self.iter
-        self.iter += 1
-        torch.cuda.synchronize()
-        tic = time.time()
-        self.adamw_step(it, lr)
-        self.wait_round()
-        return time.time() - tic
+        return self._fused_communicate(self.adamw_step, lr)
 
     def state_dict(self):
         """Checkpoint: the workers' rows and the iteration counter (resume on the same schedule);

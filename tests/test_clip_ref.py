@@ -1,15 +1,13 @@
 """Global-norm gradient clipping, the parts that need no GPU: the specification in tests/clipref.py
-against torch on the CPU, and the new C ABI (struct layout, workspace size, host-side refusals)."""
+against torch on the CPU, and the new C ABI (workspace size, host-side refusals; the call record's layout
+is checked in tests/test_native_abi.py)."""
 import ctypes
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clipref
-from conftest import ROOT
 
 torch = pytest.importorskip("torch")
 
@@ -81,23 +79,6 @@ def test_end_to_end_against_clip_grad_norm_cpu():
         got = p.grad.numpy()
         assert np.all(np.abs(got - want) <= 2 * bound * np.abs(want) + 1e-45), r
     print(f"clip_grad_norm_ vs specification, 8 x 4097: max relative norm difference {worst:.3e} (bound {bound:.3e})")
-
-
-def test_grad_norm_call_struct_layout_matches_header(pkg, tmp_path):
-    """engine.GradNormCall has mx_grad_norm_call's size and field offsets (a C program built against
-    the header prints them)"""
-    E = importlib.import_module(pkg.__name__ + ".engine")
-    fields = [f for f, _ in E.GradNormCall._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "matcha_gossip.h"\nint main(void) {\n'
-                   '  printf("%zu", sizeof(mx_grad_norm_call));\n'
-                   + "".join(f'  printf(" %zu", offsetof(mx_grad_norm_call, {f}));\n' for f in fields)
-                   + "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    want = [ctypes.sizeof(E.GradNormCall)] + [getattr(E.GradNormCall, f).offset for f in fields]
-    assert got == want and got[0] == 64
 
 
 def test_workspace_size(pkg):

@@ -5,6 +5,7 @@ import os
 import re
 
 import numpy as np
+import pytest
 
 from conftest import ROOT
 
@@ -235,20 +236,108 @@ def test_fused_round_layouts_agree(pkg):
         assert (f + "_layout:").encode() in L.mx_last_error()
 
 
-def test_mix_call_struct_layout_matches_header(pkg, tmp_path):
-    """engine.MixCall (the ctypes mirror of mx_mix_call) has the C struct's size and field offsets:
-    a C program built against include/matcha_gossip.h prints them."""
+# C record -> (its ctypes mirror in engine, sizeof by the header's field list on an LP64 target)
+CALL_RECORDS = {"mx_mix_call": ("MixCall", 88), "mx_sgd_mix_call": ("SgdMixCall", 96),
+                "mx_sgd_mix_bf16_call": ("SgdBf16Call", 104), "mx_adamw_mix_call": ("AdamwMixCall", 128),
+                "mx_adamw_mix_bf16_call": ("AdamwBf16Call", 136), "mx_grad_norm_call": ("GradNormCall", 64),
+                "mx_param_runs": ("ParamRunsRec", 40)}
+
+
+def _header_fields(struct):
+    """the member names of `typedef struct <struct> { ... }` in include/matcha_gossip.h, in order"""
+    txt = open(os.path.join(ROOT, "include", "matcha_gossip.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (struct, struct), txt, flags=re.S).group(1)
+    names = []
+    for decl in body.split(";"):
+        names += [re.search(r"(\w+)\s*$", part).group(1) for part in decl.split(",") if part.strip()]
+    return names
+
+
+@pytest.mark.parametrize("struct", sorted(CALL_RECORDS))
+def test_call_struct_layout_matches_header(pkg, tmp_path, struct):
+    """Every ctypes mirror of a call record has the C struct's members -- all of them, by name and in
+    order, so a field dropped from the mirror's tail shows -- and its size and field offsets, which a C
+    program built against include/matcha_gossip.h prints."""
     import subprocess
     import importlib
     E = importlib.import_module(pkg.__name__ + ".engine")
-    fields = [f for f, _ in E.MixCall._fields_]
+    cls = getattr(E, CALL_RECORDS[struct][0])
+    fields = [f for f, _ in cls._fields_]
+    assert fields == _header_fields(struct)
     src = tmp_path / "layout.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "matcha_gossip.h"\nint main(void) {\n'
-                   '  printf("%zu", sizeof(mx_mix_call));\n'
-                   + "".join(f'  printf(" %zu", offsetof(mx_mix_call, {f}));\n' for f in fields)
+                   f'  printf("%zu", sizeof({struct}));\n'
+                   + "".join(f'  printf(" %zu", offsetof({struct}, {f}));\n' for f in fields)
                    + "  return 0;\n}\n")
     exe = tmp_path / "layout"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    want = [ctypes.sizeof(E.MixCall)] + [getattr(E.MixCall, f).offset for f in fields]
+    want = [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f in fields]
+    assert got == want and got[0] == CALL_RECORDS[struct][1]
+
+
+class _Addr:
+    """stands in for a device tensor: only its address is read"""
+
+    def __init__(self, addr):
+        self.addr = addr
+
+    def data_ptr(self):
+        return self.addr
+
+
+class _Engine:
+    """stands in for a GossipEngine: what a call record takes from it"""
+    _plan_ptr, n_slots, n_local, M, alpha32 = (1 << 40) + 99, 9, 8, 5, float(np.float32(2 / 7))
+
+
+@pytest.mark.parametrize("family,momentum", [("SgdLayout", True), ("SgdLayout", False), ("SgdBf16Layout", True),
+                                             ("SgdBf16Layout", False), ("AdamwLayout", True),
+                                             ("AdamwBf16Layout", True)])
+def test_call_records_are_packed_as_specified(pkg, family, momentum):
+    """layout.call(engine, ...) of the four fused layouts over distinct fake addresses: every field of the
+    record -- each pointer table in its own field (an absent momentum table NULL), the geometry (n_slots /
+    n_local / M the engine's, not the layout's), the hyperparameters as fp32 roundings with omb1 / omb2
+    rounded from the fp64 1 - beta, the flags 0 or 1 for any truthy input, pad_ 0."""
+    import importlib
+    E = importlib.import_module(pkg.__name__ + ".engine")
+    cls = getattr(E, family)
+    fam = cls.family
+    adam = "Adamw" in family
+    assert fam is E.FAMILIES["adamw" if adam else "sgd", "Bf16" in family] and fam.adam == adam
+    assert fam.tables == {"SgdLayout": ("x", "g", "m"), "SgdBf16Layout": ("w", "g", "m", "p"),
+                          "AdamwLayout": ("x", "g", "m", "v"), "AdamwBf16Layout": ("w", "g", "m", "v", "p")}[family]
+    assert fam.optional == (None if adam else "m")                         # only SGD's momentum may be absent
+
+    def f32(v):
+        return float(np.float32(v))
+
+    lay = object.__new__(cls)                     # the constructor uploads tables: only call() is under test
+    want = {}
+    k = 1 << 40
+    for t in fam.tables + ("seg_len", "tile_off", "bias"):
+        k += 1
+        absent = t == "m" and not momentum
+        name = t + "_ptrs" if t in fam.tables else t
+        setattr(lay, name, None if absent else _Addr(k))
+        if t != "bias" or adam:
+            want[name + "_dev"] = None if absent else k
+    lay.total_tiles, lay.nseg, lay.n_local, lay.n_bias = 77, 3, 64, 4321 if adam else 0
+    want.update(plan_dev=_Engine._plan_ptr, total_tiles=77, nseg=3, n_slots=9, n_local=8, M=5,
+                alpha=_Engine.alpha32, wd=f32(0.1), zero_grads=1)
+    if adam:
+        call = lay.call(_Engine, (0.9, 0.999), 1e-8, 0.1, "x", 2)
+        want.update(n_bias=4321, omb1=f32(1.0 - 0.9), beta2=f32(0.999), omb2=f32(1.0 - 0.999), eps=f32(1e-8),
+                    decoupled=1)
+        assert f32(1.0 - 0.9) != 1 - f32(0.9) and f32(1.0 - 0.9) != f32(1 - f32(0.9))     # the roundings differ
+    else:
+        call = lay.call(_Engine, 0.1, 0.9, "x", 2)
+        want.update(mom=f32(0.9), nesterov=1, pad_=0)
+    assert type(call) is fam.rec
+    got = {f: getattr(call, f) for f, _ in fam.rec._fields_}
     assert got == want
+    ptrs = [v for f, v in got.items() if f.endswith("_dev") and v is not None]
+    assert len(set(ptrs)) == len(ptrs)
+    zero = lay.call(_Engine, (0.9, 0.999), 1e-8, 0.1, 0, "") if adam else lay.call(_Engine, 0.1, 0.9, 0, None)
+    assert zero.zero_grads == 0 and (zero.decoupled if adam else zero.nesterov) == 0

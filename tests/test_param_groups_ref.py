@@ -1,19 +1,16 @@
 """Per-parameter-group weight decay and lr scale, the parts that need no GPU: the specification in
 tests/groupref.py against torch's optimizers built with real param_groups, the host-side resolution of
-groups to runs (param_runs), and the new C ABI (struct layout, mx_param_runs_check, the _grouped entry
-points' refusals)."""
+groups to runs (param_runs), and the new C ABI (mx_param_runs_check, the _grouped entry points' refusals;
+the runs record's layout is checked in tests/test_native_abi.py)."""
 import ctypes
 import importlib
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import groupref
 from adamref import bias_table
-from conftest import ROOT
 
 torch = pytest.importorskip("torch")
 
@@ -185,23 +182,6 @@ def test_param_runs_other_refusals(pkg):
 
 
 # ---------------------------------------------------------------- the C ABI
-def test_param_runs_struct_layout_matches_header(pkg, tmp_path):
-    """engine.ParamRunsRec has mx_param_runs's size and field offsets (a C program built against the header
-    prints them)"""
-    E = importlib.import_module(pkg.__name__ + ".engine")
-    fields = [f for f, _ in E.ParamRunsRec._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "matcha_gossip.h"\nint main(void) {\n'
-                   '  printf("%zu", sizeof(mx_param_runs));\n'
-                   + "".join(f'  printf(" %zu", offsetof(mx_param_runs, {f}));\n' for f in fields)
-                   + "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    want = [ctypes.sizeof(E.ParamRunsRec)] + [getattr(E.ParamRunsRec, f).offset for f in fields]
-    assert got == want and got[0] == 40
-
-
 def _check(pkg, seg, off, end, wd, sc):
     a = [np.asarray(seg, np.int64), np.asarray(off, np.int32), np.asarray(end, np.int64), np.asarray(wd, F32),
          np.asarray(sc, F32)]

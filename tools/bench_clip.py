@@ -100,7 +100,7 @@ def run_mode(mode, P, K, T, settle_ms, passes):
 
     s = pkg._lib.stream_ptr
     call = grp._adamw_state()
-    plain_fn, scaled_fn = grp._adamw_fn[0], grp._adamw_fn_scaled[0]
+    plain_fn, scaled_fn = grp._adamw.run, grp._adamw.scaled
     ones = torch.ones(N, dtype=torch.float32, device="cuda")
     step_no = [0]
     ga = grp.grad_arena

@@ -96,7 +96,7 @@ def run_mode(mode, P, K, T, settle_ms, passes):
 
     s = pkg._lib.stream_ptr
     call = grp._adamw_state()
-    plain_fn, grouped_fn = grp._adamw_fn[0], grp._adamw_fn_grouped[0]
+    plain_fn, grouped_fn = grp._adamw.run, grp._adamw.grouped
     tables = {"b_one_run": pkg.engine.ParamRuns(P, [(0, P, WD32, 1.0)]),
               "c_transformer": pkg.engine.ParamRuns(P, transformer_runs(P)),
               "d_alternating_64": pkg.engine.ParamRuns(P, alternating_runs(P))}
