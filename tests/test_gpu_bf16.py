@@ -25,7 +25,7 @@ _TOPOS = {}
 
 
 def _topology(pkg, name):
-    """(partner int32 [M][n], alpha) of the four topologies, built once"""
+    """(partner int32 [M][n], alpha) of the topologies, built once"""
     if name not in _TOPOS:
         if name == "g0":                           # graph 0, 8 workers: the 8-slot class
             gp = pkg.GraphProcessor(pkg.select_graph(0), 1.0, 0, 8, 4, True)
@@ -39,6 +39,10 @@ def _topology(pkg, name):
             np.random.seed(1234)
             gp = pkg.MatchaProcessor(base, 0.5, 0, 64, 4, False)
             _TOPOS[name] = (np.asarray(gp.neighbors_info, np.int32), float(gp.neighbor_weight))
+        elif name == "ring32":                     # the hand-written ring of tests/test_gpu_adamw_mix_bf16.py:
+            even = np.arange(32) ^ 1               # the 32-slot class
+            odd = (((np.arange(32) - 1) ^ 1) + 1) % 32
+            _TOPOS[name] = (np.stack([even, odd]).astype(np.int32), 0.3125)
         else:                                      # 3 workers by hand: the 8-slot class with unused slots
             # alpha = -2^-8: a worker at the largest finite bf16 with one active partner gets
             # (1 + 2^-8) * max - 2^-8 * x_j, finite in fp32 and past the halfway point to Inf
@@ -296,7 +300,7 @@ def test_knobs_change_no_bits(pkg, O, knobs):
     try:
         for k, v in knobs.items():
             assert L.mx_mix_bf16_set(k.encode(), v) == 0
-        for name in ("g0", "g16", "er64"):
+        for name in ("g0", "g16", "ring32", "er64"):
             partner, alpha = _topology(pkg, name)
             n = partner.shape[1]
             flags = _flag_kinds(partner, 6)[[6, 3, 9]]
