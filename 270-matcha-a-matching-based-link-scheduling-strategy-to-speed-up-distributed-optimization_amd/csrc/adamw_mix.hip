@@ -80,17 +80,17 @@ struct AdamwMix {
                                                 const GroupedIf<Hyper, GROUPED>& h) {
         return adam_chunk<GROUPED>(ln.X[t], grad_of(ln.G[t], h, k), ln.Mv[t], ln.Vv[t], c, gq, st, h);
     }
-    template <bool NT>
+    template <int SP>
     static __device__ __forceinline__ void keep(const Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
                                                 bool vec, const Hyper& h) {
-        store_chunk<NT>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
-        store_chunk<NT>(tb.v[gq.base + k], c, gq.lim, vec, ln.Vv[t]);
-        if (h.zero_grads) store_chunk<NT>(tb.g[gq.base + k], c, gq.lim, vec, F4{0.0f, 0.0f, 0.0f, 0.0f});
+        store_chunk<SP>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
+        store_chunk<SP>(tb.v[gq.base + k], c, gq.lim, vec, ln.Vv[t]);
+        if (h.zero_grads) store_chunk<SP>(tb.g[gq.base + k], c, gq.lim, vec, F4{0.0f, 0.0f, 0.0f, 0.0f});
     }
-    template <bool NT>
+    template <int SP>
     static __device__ __forceinline__ void finish(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
                                                   const F4& acc) {
-        store_chunk<NT>(tb.x[gq.base + k], c, gq.lim, vec, acc);
+        store_chunk<SP>(tb.x[gq.base + k], c, gq.lim, vec, acc);
     }
 };
 
@@ -111,10 +111,10 @@ int adamw_mix(const mx_adamw_mix_call* c, const mx_param_runs* runs, const float
     if (const int rc = check_runs(runs, who)) return rc;
     if (c->total_tiles <= 0) return MX_OK;
     // bytes the round moves: x, m, v read + written, g read (+ zeroed)
-    const bool nt = g_tune.streaming(c->total_tiles, pick(c->n_local).tile, c->n_local, 4 * (7 + (c->zero_grads ? 1 : 0)));
+    const int bpe = 4 * (7 + (c->zero_grads ? 1 : 0));
     const AdamHyper h{lr, c->wd, c->omb1, c->beta2, c->omb2, c->eps, lr_dev, gscale, c->bias_dev, c->n_bias, step, step_dev,
                       c->decoupled != 0, c->zero_grads != 0};
-    return dispatch<AdamwMix>(g_tune, r, nt, h, runs, c->x_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev, c->v_ptrs_dev);
+    return dispatch<AdamwMix>(g_tune, r, bpe, h, runs, c->x_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev, c->v_ptrs_dev);
 }
 }  // namespace
 

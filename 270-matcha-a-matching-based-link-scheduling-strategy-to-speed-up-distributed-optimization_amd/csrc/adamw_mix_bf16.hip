@@ -97,18 +97,18 @@ struct AdamwMixBf16 {
                                                 const GroupedIf<Hyper, GROUPED>& h) {
         return adam_chunk<GROUPED>(ln.X[t], grad_of(ln.G[t], h, k), ln.Mv[t], ln.Vv[t], c, gq, st, h);
     }
-    template <bool NT>
+    template <int SP>
     static __device__ __forceinline__ void keep(const Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
                                                 bool vec, const Hyper& h) {
-        store_chunk<NT>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
-        store_chunk<NT>(tb.v[gq.base + k], c, gq.lim, vec, ln.Vv[t]);
-        if (h.zero_grads) store_chunk<NT>(tb.g[gq.base + k], c, gq.lim, vec, U2{0u, 0u});
+        store_chunk<SP>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
+        store_chunk<SP>(tb.v[gq.base + k], c, gq.lim, vec, ln.Vv[t]);
+        if (h.zero_grads) store_chunk<SP>(tb.g[gq.base + k], c, gq.lim, vec, U2{0u, 0u});
     }
-    template <bool NT>
+    template <int SP>
     static __device__ __forceinline__ void finish(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
                                                   const F4& acc) {
-        store_chunk<NT>(tb.w[gq.base + k], c, gq.lim, vec, acc);
-        store_chunk<NT>(tb.p[gq.base + k], c, gq.lim, vec, pack4(acc));         // the model row: bf16 of the stored w
+        store_chunk<SP>(tb.w[gq.base + k], c, gq.lim, vec, acc);
+        store_chunk<SP>(tb.p[gq.base + k], c, gq.lim, vec, pack4(acc));         // the model row: bf16 of the stored w
     }
 };
 
@@ -129,10 +129,10 @@ int adamw_mix_bf16(const mx_adamw_mix_bf16_call* c, const mx_param_runs* runs, c
     if (const int rc = check_runs(runs, who)) return rc;
     if (c->total_tiles <= 0) return MX_OK;
     // bytes the round moves: w, m, v read + written, g read (+ zeroed), p written
-    const bool nt = g_tune.streaming(c->total_tiles, pick(c->n_local).tile, c->n_local, 28 + (c->zero_grads ? 2 : 0));
+    const int bpe = 28 + (c->zero_grads ? 2 : 0);
     const AdamHyper h{lr, c->wd, c->omb1, c->beta2, c->omb2, c->eps, lr_dev, gscale, c->bias_dev, c->n_bias, step, step_dev,
                       c->decoupled != 0, c->zero_grads != 0};
-    return dispatch<AdamwMixBf16>(g_tune, r, nt, h, runs, c->w_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev, c->v_ptrs_dev,
+    return dispatch<AdamwMixBf16>(g_tune, r, bpe, h, runs, c->w_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev, c->v_ptrs_dev,
                                   c->p_ptrs_dev);
 }
 }  // namespace

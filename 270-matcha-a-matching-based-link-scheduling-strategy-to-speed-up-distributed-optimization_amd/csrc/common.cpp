@@ -14,6 +14,7 @@ void set_error(const char* fmt, ...) {
 }
 
 int g_mean_wgpc = 3;
+int g_store_policy = 0;
 
 int lds_per_cu() {
     static int v = [] {

@@ -455,8 +455,9 @@ __global__ __launch_bounds__(256) void mean4_kernel(const f4v* rows, int nrows, 
 // The mixing kernel's tile geometry for up to 8 rows: one workgroup per 512-column tile (128
 // 4-float vectors).  The rows' 2 KB pieces are staged in LDS with 16-byte loads (each wave load is
 // 1 KB of one row), then every lane sums its column in the same order as mean4_kernel<TREE> (the
-// same adds, the same division: identical bits) and stores every other destination row.
-template <int TREE>
+// same adds, the same division: identical bits) and stores every other destination row under the
+// store policy SP (mx::StorePolicy, mx_mix_set "store_policy").
+template <int TREE, int SP = mx::kStoreNt>
 __global__ __launch_bounds__(256) void mean_tile_kernel(const f4v* rows, int nrows, int64_t ld, float size,
                                                         f4v* dst, int ndst, int64_t dst_ld) {
     constexpr int C4 = 128;
@@ -492,7 +493,7 @@ __global__ __launch_bounds__(256) void mean_tile_kernel(const f4v* rows, int nro
             if (r < nrows) acc = acc + v[r];
     }
     const f4v m = acc / size;
-    for (int d = h; d < ndst; d += 2) __builtin_nontemporal_store(m, dst + (int64_t)d * dst_ld + c0 + c);
+    for (int d = h; d < ndst; d += 2) mx::store16<SP>(dst + (int64_t)d * dst_ld + c0 + c, m);
 }
 
 inline unsigned grid_of(int64_t count) {
@@ -584,12 +585,23 @@ extern "C" int mx_mean_rows_to(const float* rows, int nrows, int64_t ld, int64_t
             // place 0.2796 -> 0.2590 ms at 3 per CU (0.73 -> 0.79 of 8 TB/s; tools/occ_sweep.py)
             const size_t pad = (int64_t)nrows * count * 4 > ((int64_t)64 << 20)
                                    ? mx::lds_cap_pad(8 * 128 * (int)sizeof(f4v), mx::g_mean_wgpc) : 0;
-            if (order == 1)
-                hipLaunchKernelGGL((mean_tile_kernel<0>), dim3((unsigned)nt), dim3(256), pad, st, r4, nrows, ld / 4, d, d4,
-                                   ndst, dst_ld / 4);
-            else
-                hipLaunchKernelGGL((mean_tile_kernel<1>), dim3((unsigned)nt), dim3(256), pad, st, r4, nrows, ld / 4, d, d4,
-                                   ndst, dst_ld / 4);
+            // store policy: forced, or auto -- the chosen policy above 320 MB of rows, nt below
+            const int pol = mx::g_store_policy > 0 ? mx::g_store_policy
+                            : (int64_t)nrows * count * 4 > mx::kStoreAutoBytes ? mx::kStoreAutoPolicy : mx::kStoreNt;
+#define MX_MEAN_TILE(T, P)                                                                                    \
+    hipLaunchKernelGGL((mean_tile_kernel<T, P>), dim3((unsigned)nt), dim3(256), pad, st, r4, nrows, ld / 4, d, d4, \
+                       ndst, dst_ld / 4)
+#define MX_MEAN_POL(T)                                                     \
+    do {                                                                   \
+        if (pol == mx::kStoreSc1) MX_MEAN_TILE(T, mx::kStoreSc1);          \
+        else if (pol == mx::kStoreSc1Nt) MX_MEAN_TILE(T, mx::kStoreSc1Nt); \
+        else if (pol == mx::kStoreSc0Sc1) MX_MEAN_TILE(T, mx::kStoreSc0Sc1); \
+        else MX_MEAN_TILE(T, mx::kStoreNt);                                \
+    } while (0)
+            if (order == 1) MX_MEAN_POL(0);
+            else MX_MEAN_POL(1);
+#undef MX_MEAN_POL
+#undef MX_MEAN_TILE
             MX_LAUNCH_CHECK();
             done4 = nt * 128;
         }

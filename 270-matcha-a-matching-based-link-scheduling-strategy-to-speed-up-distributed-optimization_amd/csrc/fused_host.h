@@ -23,11 +23,18 @@ struct Tune {
     int blocks_per_cu = 2; // persistent grids (32 / 64 rows, or more work items than flat_small x the grid)
     int flat_small = 256;  // 8 / 16 rows: one workgroup per work item up to flat_small x CUs x blocks_per_cu items
     int grid = 0;          // > 0: exact persistent grid size (tests: few workgroups looping over many work items)
+    int store_policy = 0;  // 16-byte stores of the streaming 8- / 16-row launches (mx::StorePolicy): 1 nt, 2 sc1,
+                           // 3 sc1 nt forced at every size; 0 = auto: kAutoPolicy for rounds moving > 320 MB, nt below
+                           // (nt: write-through measured 0.5-4 % slower in all four families on 8 x 25.6M,
+                           // tools/store_policy_ab.py, profiles/store_policy_ab.json "fused")
+    static constexpr int kAutoPolicy = 1;
 
     int set(const char* who, const char* key, int value);
     int get(const char* who, const char* key) const;
     // streaming hints for a round whose arrays hold `bytes_per_elem` bytes per (row, column)
     bool streaming(int64_t total_tiles, int tile, int n_local, int bytes_per_elem) const;
+    // the store policy of that round's launch (plain without streaming hints)
+    int policy(bool nt, int64_t total_tiles, int tile, int n_local, int bytes_per_elem) const;
     // the grid of `work` work items of an `ns`-row class: one workgroup each (flat; `wgpc` then caps the
     // workgroups per CU) or a persistent grid looping over them
     int64_t grid_of(int ns, int64_t work, bool* flat) const;

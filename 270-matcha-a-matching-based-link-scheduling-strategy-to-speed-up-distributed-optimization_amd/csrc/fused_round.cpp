@@ -43,6 +43,9 @@ int Tune::set(const char* who, const char* key, int value) {
     } else if (!strcmp(key, "grid")) {
         MX_CHECK(value >= 0 && value <= 65536, "%s: grid %d", who, value);
         grid = value;
+    } else if (!strcmp(key, "store_policy")) {
+        MX_CHECK(value >= 0 && value <= mx::kStoreSc1Nt, "%s: store_policy %d", who, value);
+        store_policy = value;
     } else {
         MX_CHECK(false, "%s: unknown key '%s'", who, key);
     }
@@ -56,6 +59,7 @@ int Tune::get(const char* who, const char* key) const {
     if (!strcmp(key, "blocks_per_cu")) return blocks_per_cu;
     if (!strcmp(key, "flat_small")) return flat_small;
     if (!strcmp(key, "grid")) return grid;
+    if (!strcmp(key, "store_policy")) return store_policy;
     mx::set_error("%s: unknown key '%s'", who, key);
     return MX_ERR_INVALID;
 }
@@ -64,6 +68,13 @@ bool Tune::streaming(int64_t total_tiles, int tile, int n_local, int bytes_per_e
     if (nontemporal != 2) return nontemporal != 0;
     const int64_t ws = total_tiles * (int64_t)tile * n_local * bytes_per_elem;   // bytes the round moves
     return ws <= ((int64_t)32 << 20) || ws > ((int64_t)320 << 20);
+}
+
+int Tune::policy(bool nt, int64_t total_tiles, int tile, int n_local, int bytes_per_elem) const {
+    if (!nt) return mx::kStorePlain;
+    if (store_policy > 0) return store_policy;
+    const int64_t ws = total_tiles * (int64_t)tile * n_local * bytes_per_elem;
+    return ws > mx::kStoreAutoBytes ? kAutoPolicy : mx::kStoreNt;
 }
 
 static int cu_count() {

@@ -13,8 +13,9 @@
 //     setup(st, h)          the per-launch constants
 //     begin_item<G>(...)    the per-work-item constants of a grouped launch
 //     update<G>(...)        the optimizer update of chunk t in registers: returns x' for LDS
-//     keep<NT>(...)         stores the state the lane owns and, with zero_grads, the zeros over g
-//     finish<NT>(...)       stores a mixed chunk (and, bf16 families, its rounded image)
+//     keep<SP>(...)         stores the state the lane owns and, with zero_grads, the zeros over g
+//     finish<SP>(...)       stores a mixed chunk (and, bf16 families, its rounded image)
+// (SP: the store policy, mx::StorePolicy -- its 16-byte stores; the 8-byte bf16 stores are plain or nt)
 // Everything a policy decides is decided at compile time; the kernel has no run-time branch on the family.
 // A new optimizer is a new policy type plus its entry points: nothing in this file changes.
 //
@@ -56,11 +57,9 @@ __device__ __forceinline__ F4 ld16(const float* p) {
     if constexpr (NT) return __builtin_nontemporal_load(g);
     else return *g;
 }
-template <bool NT>
+template <int SP>
 __device__ __forceinline__ void st16(float* p, const F4& v) {
-    const GPtr<F4> g = (GPtr<F4>)(p);
-    if constexpr (NT) __builtin_nontemporal_store(v, g);
-    else *g = v;
+    mx::store16<SP>(reinterpret_cast<F4*>(p), v);
 }
 template <bool NT>
 __device__ __forceinline__ U2 ld8(const uint16_t* p) {
@@ -68,10 +67,11 @@ __device__ __forceinline__ U2 ld8(const uint16_t* p) {
     if constexpr (NT) return __builtin_nontemporal_load(g);
     else return *g;
 }
-template <bool NT>
+// 8-byte stores never take a write-through policy (narrow sc1 stores cost 2.7x per byte): nt or plain
+template <int SP>
 __device__ __forceinline__ void st8(uint16_t* p, const U2& v) {
     const GPtr<U2> g = (GPtr<U2>)(p);
-    if constexpr (NT) __builtin_nontemporal_store(v, g);
+    if constexpr (SP != mx::kStorePlain) __builtin_nontemporal_store(v, g);
     else *g = v;
 }
 __device__ __forceinline__ float ld4(const float* p) { return *(GPtr<const float>)(p); }
@@ -92,10 +92,10 @@ __device__ __forceinline__ F4 load_chunk(const float* row, int64_t c, int64_t li
     for (int t = 0; t < 4; ++t) v[t] = (c + t < lim) ? ld4(row + c + t) : 0.0f;
     return v;
 }
-template <bool NT>
+template <int SP>
 __device__ __forceinline__ void store_chunk(float* row, int64_t c, int64_t lim, bool vec, const F4& v) {
     if (vec && c + 4 <= lim) {
-        st16<NT>(row + c, v);
+        st16<SP>(row + c, v);
         return;
     }
 #pragma unroll
@@ -114,10 +114,10 @@ __device__ __forceinline__ U2 load_chunk(const uint16_t* row, int64_t c, int64_t
     }
     return v;
 }
-template <bool NT>
+template <int SP>
 __device__ __forceinline__ void store_chunk(uint16_t* row, int64_t c, int64_t lim, bool vec, const U2& v) {
     if (vec && c + 4 <= lim) {
-        st8<NT>(row + c, v);
+        st8<SP>(row + c, v);
         return;
     }
 #pragma unroll
@@ -211,8 +211,9 @@ __device__ __forceinline__ int64_t round_of(int64_t iter, const int64_t* iter_de
 }
 
 // NS rows x TW columns per work item; a layout tile (mx_*_tile) is `split` work items.
-// GROUPED: per-run weight decay and learning-rate scale (see Runs above).  T...: Update::Tabs' members.
-template <class Update, int NS, int TW, bool NT, bool GROUPED, class... T>
+// GROUPED: per-run weight decay and learning-rate scale (see Runs above).  SP: the store policy of the
+// 16-byte stores (mx::StorePolicy; the loads follow NT).  T...: Update::Tabs' members.
+template <class Update, int NS, int TW, bool NT, bool GROUPED, int SP, class... T>
 __global__ __launch_bounds__(kTPB) void fused_round_rows(T __restrict__... tabs,
                                                          const int64_t* __restrict__ seg_len,
                                                          const int64_t* __restrict__ tile_off, int nseg,
@@ -333,7 +334,7 @@ __global__ __launch_bounds__(kTPB) void fused_round_rows(T __restrict__... tabs,
                 const int64_t c = gq.col0 + (int64_t)(at % C4 + lane) * 4;
                 const bool vec = Update::vec_of(tb, gq, k);
                 lds[at + lane] = Update::template update<GROUPED>(ln, t, k, c, gq, st, h);
-                Update::template keep<NT>(ln, t, tb, gq, k, c, vec, h);
+                Update::template keep<SP>(ln, t, tb, gq, k, c, vec, h);
             }
         }
     };
@@ -345,7 +346,7 @@ __global__ __launch_bounds__(kTPB) void fused_round_rows(T __restrict__... tabs,
             const F4 self = lds[r * C4 + col];
             if (mixes(r)) fma4(acc, sw[r], self);                    // the self term, last
             else acc = self;                                         // x' as it is
-            Update::template finish<NT>(tb, g, r, g.col0 + (int64_t)col * 4, Update::vec_of(tb, g, r), acc);
+            Update::template finish<SP>(tb, g, r, g.col0 + (int64_t)col * 4, Update::vec_of(tb, g, r), acc);
         };
         int p = 0;
         for (; p + 1 < nmy; p += 2) {            // two items interleaved
@@ -438,9 +439,9 @@ inline int check_runs(const mx_param_runs* runs, const char* who) {
     return MX_OK;
 }
 
-template <class Update, int NS, int TW, bool NT, bool GROUPED, class... T>
+template <class Update, int NS, int TW, bool NT, bool GROUPED, int SP = NT ? mx::kStoreNt : mx::kStorePlain, class... T>
 int launch(const Tune& tune, const Round& r, const typename Update::Hyper& h, const mx_param_runs* runs, T... tabs) {
-    const auto kernel = fused_round_rows<Update, NS, TW, NT, GROUPED, T...>;
+    const auto kernel = fused_round_rows<Update, NS, TW, NT, GROUPED, SP, T...>;
     const int split = pick(r.n_local).tile / TW;
     bool flat = false;
     const int64_t grid = tune.grid_of(NS, r.total_tiles * split, &flat);
@@ -462,22 +463,35 @@ int launch(const Tune& tune, const Round& r, const typename Update::Hyper& h, co
     return MX_OK;
 }
 
-// the instantiation of a checked call: row class x streaming mode x grouped (runs != NULL)
+// the instantiation of a checked call: row class x streaming mode x grouped (runs != NULL), and for the
+// streaming launches of the 8- and 16-row classes the store policy; bytes_per_elem: what the round moves
+// per (row, column)
 template <class Update, class... T>
-int dispatch(const Tune& tune, const Round& r, bool nt, const typename Update::Hyper& h, const mx_param_runs* runs,
-             T... tabs) {
+int dispatch(const Tune& tune, const Round& r, int bytes_per_elem, const typename Update::Hyper& h,
+             const mx_param_runs* runs, T... tabs) {
+    const Cls cls = pick(r.n_local);
+    const bool nt = tune.streaming(r.total_tiles, cls.tile, r.n_local, bytes_per_elem);
+    const int pol = tune.policy(nt, r.total_tiles, cls.tile, r.n_local, bytes_per_elem);
+#define MX_FUSED_POL(N, TW, P)                                                                                \
+    (runs ? launch<Update, N, TW, true, true, P>(tune, r, h, runs, tabs...)                                  \
+          : launch<Update, N, TW, true, false, P>(tune, r, h, runs, tabs...))
+#define MX_FUSED_S(N, TW)                                                                                     \
+    (pol == mx::kStoreSc1 ? MX_FUSED_POL(N, TW, mx::kStoreSc1)                                                \
+                          : pol == mx::kStoreSc1Nt ? MX_FUSED_POL(N, TW, mx::kStoreSc1Nt) : MX_FUSED(N, TW))
 #define MX_FUSED(N, TW)                                                                                       \
     (runs ? (nt ? launch<Update, N, TW, true, true>(tune, r, h, runs, tabs...)                              \
                 : launch<Update, N, TW, false, true>(tune, r, h, runs, tabs...))                             \
           : (nt ? launch<Update, N, TW, true, false>(tune, r, h, runs, tabs...)                             \
                 : launch<Update, N, TW, false, false>(tune, r, h, runs, tabs...)))
-    switch (pick(r.n_local).ns) {
-        case 8: return MX_FUSED(8, 512);
-        case 16: return MX_FUSED(16, 512);
+    switch (cls.ns) {
+        case 8: return MX_FUSED_S(8, 512);
+        case 16: return MX_FUSED_S(16, 512);
         case 32: return MX_FUSED(32, 512);
         default: return MX_FUSED(64, 256);
     }
 #undef MX_FUSED
+#undef MX_FUSED_S
+#undef MX_FUSED_POL
 }
 
 }  // namespace fused

@@ -60,11 +60,18 @@ __device__ __forceinline__ F ld(const float* p) {
     else return *g;
 }
 
-template <bool NT, typename F>
+// SP: the store policy (mx::StorePolicy; a bool NT converts to plain / nt).  The write-through
+// policies exist for 16-byte stores only.
+template <int SP, typename F>
 __device__ __forceinline__ void st(float* p, const F& v) {
-    const GPtr<F> g = (GPtr<F>)(p);
-    if constexpr (NT) __builtin_nontemporal_store(v, g);
-    else *g = v;
+    if constexpr (sizeof(F) == 16) {
+        mx::store16<SP>(reinterpret_cast<F*>(p), v);
+    } else {
+        static_assert(SP <= mx::kStoreNt, "write-through policies are for 16-byte stores");
+        const GPtr<F> g = (GPtr<F>)(p);
+        if constexpr (SP == mx::kStoreNt) __builtin_nontemporal_store(v, g);
+        else *g = v;
+    }
 }
 
 __device__ __forceinline__ float ld1(const float* p) { return *(GPtr<const float>)(p); }
@@ -199,10 +206,10 @@ __device__ __forceinline__ void load_slot(F (&v)[U], const float* row, int64_t g
     }
 }
 
-template <int VEC, bool NT, typename F>
+template <int VEC, int SP, typename F>
 __device__ __forceinline__ void store_one(float* row, int64_t c, int64_t lim, bool full, const F& a) {
     if (full) {
-        st<NT, F>(row + c, a);
+        st<SP, F>(row + c, a);
     } else {
 #pragma unroll
         for (int j = 0; j < VEC; ++j)
@@ -463,7 +470,11 @@ __global__ __launch_bounds__(kTPB) void mix_kernel_reg(float* const* __restrict_
 // PF2: two tiles' loads in flight instead of one (two register sets, the loop unrolled by two) --
 // a persistent workgroup whose tile stages few of its NS slots (a GPU's share of a big topology:
 // few local rows, many received ones) otherwise keeps too little in flight per CU.
-template <int NS, int TW, bool NT, int SPLIT = 1, bool PF2 = false, int TPB = kTPB, bool SPEC = false, bool GL = false>
+//
+// SP: the store policy of the 16-byte row stores (mx::StorePolicy, mx_mix_set "store_policy"); the
+// loads follow NT.
+template <int NS, int TW, bool NT, int SPLIT = 1, bool PF2 = false, int TPB = kTPB, bool SPEC = false, bool GL = false,
+          int SP = NT ? mx::kStoreNt : mx::kStorePlain>
 __global__ __launch_bounds__(TPB) void mix_kernel_rows(float* const* __restrict__ seg_ptrs,
                                                         const int64_t* __restrict__ seg_len,
                                                         const int64_t* __restrict__ tile_off,
@@ -609,7 +620,7 @@ __global__ __launch_bounds__(TPB) void mix_kernel_rows(float* const* __restrict_
 #pragma unroll
             for (int t = 0; t < 4; ++t) acc[t] = __builtin_fmaf(s, xs[t], acc[t]);
             const int64_t c = cur.col0 + (int64_t)col * 4;
-            store_one<4, NT>(cur.ptrs[r], c, cur.lim, al16(cur.ptrs[r]) && c + 4 <= cur.lim, acc);
+            store_one<4, SP>(cur.ptrs[r], c, cur.lim, al16(cur.ptrs[r]) && c + 4 <= cur.lim, acc);
         };
         int p = 0;
         for (; p + 1 < nmy; p += 2) {            // two items interleaved
@@ -1058,7 +1069,8 @@ int launch(float* const* seg_ptrs, const int64_t* seg_len, const int64_t* tile_o
     return MX_OK;
 }
 
-template <int NS, int TW, bool NT, int SPLIT = 1, bool PF2 = false, int TPB = kTPB, bool SPEC = false, bool GL = false>
+template <int NS, int TW, bool NT, int SPLIT = 1, bool PF2 = false, int TPB = kTPB, bool SPEC = false, bool GL = false,
+          int SP = NT ? mx::kStoreNt : mx::kStorePlain>
 int launch_rows(float* const* seg_ptrs, const int64_t* seg_len, const int64_t* tile_off,
                 const uint8_t* seg_vec, int nseg, int n_slots, const int32_t* plan, int64_t iter, const int64_t* iter_dev,
                 int n_local, int M, float alpha, int64_t total_tiles, hipStream_t st) {
@@ -1076,11 +1088,11 @@ int launch_rows(float* const* seg_ptrs, const int64_t* seg_len, const int64_t* t
         static const int stat = [] {                           // static LDS of this instantiation
             hipFuncAttributes fa{};
             return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(
-                       mix_kernel_rows<NS, TW, NT, SPLIT, PF2, TPB, SPEC, GL>)) == hipSuccess ? (int)fa.sharedSizeBytes : 0;
+                       mix_kernel_rows<NS, TW, NT, SPLIT, PF2, TPB, SPEC, GL, SP>)) == hipSuccess ? (int)fa.sharedSizeBytes : 0;
         }();
         pad = mx::lds_cap_pad(stat, g_rows_opt.wg_per_cu);
     }
-    hipLaunchKernelGGL((mix_kernel_rows<NS, TW, NT, SPLIT, PF2, TPB, SPEC, GL>), dim3((unsigned)grid), dim3(TPB),
+    hipLaunchKernelGGL((mix_kernel_rows<NS, TW, NT, SPLIT, PF2, TPB, SPEC, GL, SP>), dim3((unsigned)grid), dim3(TPB),
                        pad, st, seg_ptrs, seg_len, tile_off, seg_vec, nseg, total_tiles, n_slots, plan,
                        iter, iter_dev, n_local, M, alpha, g_rows_opt.hint);
     MX_LAUNCH_CHECK();
@@ -1179,6 +1191,9 @@ extern "C" int mx_mix_set(const char* key, int value) {
     } else if (!strcmp(key, "mean_wgpc")) {
         MX_CHECK(value >= 0 && value <= 32, "mx_mix_set: mean_wgpc %d", value);
         slot = &mx::g_mean_wgpc;
+    } else if (!strcmp(key, "store_policy")) {
+        MX_CHECK(value >= 0 && value <= mx::kStorePolicyMax, "mx_mix_set: store_policy %d", value);
+        slot = &mx::g_store_policy;
     } else if (!strcmp(key, "flat_small")) {
         MX_CHECK(value >= 0 && value <= 4096, "mx_mix_set: flat_small %d", value);
         slot = &g_tune.flat_small;
@@ -1208,6 +1223,7 @@ extern "C" int mx_mix_get(const char* key) {
     if (!strcmp(key, "spec_wgpc")) return g_tune.spec_wgpc;
     if (!strcmp(key, "spec_glds")) return g_tune.spec_glds;
     if (!strcmp(key, "mean_wgpc")) return mx::g_mean_wgpc;
+    if (!strcmp(key, "store_policy")) return mx::g_store_policy;
     if (!strcmp(key, "spec_launches")) return (int)(g_spec_launches.load() & 0x7fffffff);
     if (!strcmp(key, "mid_bpc")) return g_tune.mid_bpc;
     if (!strcmp(key, "mid_tiles")) return g_tune.mid_tiles;
@@ -1412,10 +1428,19 @@ int gossip_mix(float* const* seg_ptrs_dev, const int64_t* seg_len_dev, const int
         const int64_t ws = total_tiles * (int64_t)mx_mix_tile(n_slots) * n_slots * 4;
         const bool nt = g_tune.nontemporal == 2 ? (ws <= ((int64_t)32 << 20) || ws > ((int64_t)320 << 20))
                                                 : g_tune.nontemporal != 0;
-        if (c.ns == 8 && unroll_for(8) == 2)
-            return nt ? launch_rows<8, 2048, true>(MX_ARGS) : launch_rows<8, 2048, false>(MX_ARGS);
-        const int sp = row_split(c.ns, total_tiles);
+        // store policy of the streaming (nt) 8- and 16-slot launches: forced, or auto -- the chosen
+        // policy above 320 MB, nt below (rows that fit the L2s rely on finding their lines again)
+        const int pol = mx::g_store_policy > 0 ? mx::g_store_policy
+                        : ws > mx::kStoreAutoBytes ? mx::kStoreAutoPolicy : mx::kStoreNt;
+#define MX_POL(N, TW, S, SPEC, GL)                                                                                \
+    (pol == mx::kStoreSc1      ? launch_rows<N, TW, true, S, false, kTPB, SPEC, GL, mx::kStoreSc1>(MX_ARGS)       \
+     : pol == mx::kStoreSc1Nt  ? launch_rows<N, TW, true, S, false, kTPB, SPEC, GL, mx::kStoreSc1Nt>(MX_ARGS)     \
+     : pol == mx::kStoreSc0Sc1 ? launch_rows<N, TW, true, S, false, kTPB, SPEC, GL, mx::kStoreSc0Sc1>(MX_ARGS)    \
+                               : launch_rows<N, TW, true, S, false, kTPB, SPEC, GL>(MX_ARGS))
 #define MX_ROWS(N, TW, S) (nt ? launch_rows<N, TW, true, S>(MX_ARGS) : launch_rows<N, TW, false, S>(MX_ARGS))
+#define MX_ROWSS(N, TW, S) (nt ? MX_POL(N, TW, S, false, false) : launch_rows<N, TW, false, S>(MX_ARGS))
+        if (c.ns == 8 && unroll_for(8) == 2) return MX_ROWSS(8, 2048, 1);
+        const int sp = row_split(c.ns, total_tiles);
         if (c.ns == 8) {
             // SPEC (knob "spec"): a round whose local active rows the caller passed (hint, from the
             // host's copy of the flags: mx_gossip_mix_packed) loads their first tile before the plan
@@ -1431,14 +1456,13 @@ int gossip_mix(float* const* seg_ptrs_dev, const int64_t* seg_len_dev, const int
                 g_rows_opt.hint = hint;
                 g_rows_opt.wg_per_cu = g_tune.spec_wgpc;
                 ++g_spec_launches;
-                if (g_tune.spec_glds && sp == 2) return launch_rows<8, 512, true, 2, false, kTPB, true, true>(MX_ARGS);
-                return sp == 4 ? launch_rows<8, 256, true, 4, false, kTPB, true>(MX_ARGS)
-                               : sp == 2 ? launch_rows<8, 512, true, 2, false, kTPB, true>(MX_ARGS)
-                                         : launch_rows<8, 1024, true, 1, false, kTPB, true>(MX_ARGS);
+                if (g_tune.spec_glds && sp == 2) return MX_POL(8, 512, 2, true, true);
+                return sp == 4 ? MX_POL(8, 256, 4, true, false)
+                               : sp == 2 ? MX_POL(8, 512, 2, true, false) : MX_POL(8, 1024, 1, true, false);
             }
-            return sp == 4 ? MX_ROWS(8, 256, 4) : sp == 2 ? MX_ROWS(8, 512, 2) : MX_ROWS(8, 1024, 1);
+            return sp == 4 ? MX_ROWSS(8, 256, 4) : sp == 2 ? MX_ROWSS(8, 512, 2) : MX_ROWSS(8, 1024, 1);
         }
-        if (c.ns == 16) return sp == 4 ? MX_ROWS(16, 256, 4) : sp == 2 ? MX_ROWS(16, 512, 2) : MX_ROWS(16, 1024, 1);
+        if (c.ns == 16) return sp == 4 ? MX_ROWSS(16, 256, 4) : sp == 2 ? MX_ROWSS(16, 512, 2) : MX_ROWSS(16, 1024, 1);
 #define MX_ROWSP(N, TW, S)                                                                                  \
     ((g_tune.rows_pf2 == 1 || (g_tune.rows_pf2 == 2 && 8 * n_slots <= 5 * (N)))                                  \
          ? (nt ? launch_rows<N, TW, true, S, true>(MX_ARGS) : launch_rows<N, TW, false, S, true>(MX_ARGS))     \
@@ -1455,7 +1479,9 @@ int gossip_mix(float* const* seg_ptrs_dev, const int64_t* seg_len_dev, const int
 #undef MX_ROWSW
 #undef MX_ROWST
 #undef MX_ROWSP
+#undef MX_ROWSS
 #undef MX_ROWS
+#undef MX_POL
     }
     if (g_tune.regidx && c.ns == 8) {
         if (unroll_for(8) == 4) { MX_DISPATCH_REG(8, 4) }

@@ -55,6 +55,47 @@ int lds_per_cu();
 size_t lds_cap_pad(int static_bytes, int wg_per_cu);
 extern int g_mean_wgpc;   // mean_tile_kernel's workgroups per CU on large rounds (mx_mix_set "mean_wgpc")
 
+// Store policy of the streaming kernels' 16-byte row stores (mx_mix_set "store_policy"): when a
+// written line leaves the XCD's write-back L2.  nt keeps the line dirty in L2 until it is evicted;
+// the sc1 forms write it through and drop it.  No policy changes a bit: no kernel re-reads what it
+// wrote and the kernel boundary publishes every store.  Only whole 16-byte stores take a policy --
+// element tails and misaligned rows keep their ordinary stores (narrow write-through stores cost
+// several times more per byte).
+enum StorePolicy { kStorePlain = 0, kStoreNt = 1, kStoreSc1 = 2, kStoreSc1Nt = 3, kStoreSc0Sc1 = 4 };
+constexpr int kStorePolicyMax = kStoreSc0Sc1;
+// the policy "store_policy" = 0 (auto) gives rounds of more than kStoreAutoBytes that stream with
+// non-temporal hints; smaller rounds (rows found again in the L2s or the Infinity Cache by the
+// next round) always keep nt.  sc1 nt: the fastest policy of the row kernel and the mean on
+// every streamed shape (8 x 25.6M: 0.2616 -> 0.2565 ms, 8 x 36.5M: 0.3725 -> 0.3673 ms,
+// 8 x 14.8M: 0.1549 -> 0.1533 ms, mean 8 x 25.6M: 0.2629 -> 0.2584 ms; sc1 and sc0 sc1 in
+// between; tools/store_policy_ab.py, profiles/store_policy_ab.json)
+constexpr int kStoreAutoPolicy = kStoreSc1Nt;
+constexpr int64_t kStoreAutoBytes = (int64_t)320 << 20;
+extern int g_store_policy;   // 0 = auto, 1..kStorePolicyMax = that policy at every size
+
+#if defined(__HIPCC__)
+// One 16-byte store to global memory under policy SP.  The write-through forms have no builtin on
+// a plain pointer, so they are inline asm: the compiler does not count such a store on vmcnt (its
+// later waits can only wait longer), and the trailing s_nop keeps its next instruction from
+// overwriting the data registers before the store has read them.
+template <int SP, typename F4>
+__device__ __forceinline__ void store16(F4* p, const F4& v) {
+    static_assert(sizeof(F4) == 16, "store16 takes 16-byte vectors");
+    typedef __attribute__((address_space(1))) F4* G;
+    const G g = (G)(p);
+    if constexpr (SP == kStoreSc1)
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(g), "v"(v) : "memory");
+    else if constexpr (SP == kStoreSc1Nt)
+        asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(g), "v"(v) : "memory");
+    else if constexpr (SP == kStoreSc0Sc1)
+        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(g), "v"(v) : "memory");
+    else if constexpr (SP == kStoreNt)
+        __builtin_nontemporal_store(v, g);
+    else
+        *g = v;
+}
+#endif
+
 // numpy legacy_random_binomial(n=1) parameters, computed on the host with glibc libm exactly
 // as numpy's legacy_random_binomial_inversion does (see flags.hip).
 struct BinomParam {

@@ -66,16 +66,16 @@ struct SgdMix {
                                                 const GroupedIf<Hyper, GROUPED>& h) {
         return sgd_chunk<MOM, GROUPED>(ln.X[t], grad_of(ln.G[t], h, k), ln.Mv[t], c, gq, st, h);
     }
-    template <bool NT>
+    template <int SP>
     static __device__ __forceinline__ void keep(const Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
                                                 bool vec, const Hyper& h) {
-        if constexpr (MOM) store_chunk<NT>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
-        if (h.zero_grads) store_chunk<NT>(tb.g[gq.base + k], c, gq.lim, vec, F4{0.0f, 0.0f, 0.0f, 0.0f});
+        if constexpr (MOM) store_chunk<SP>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
+        if (h.zero_grads) store_chunk<SP>(tb.g[gq.base + k], c, gq.lim, vec, F4{0.0f, 0.0f, 0.0f, 0.0f});
     }
-    template <bool NT>
+    template <int SP>
     static __device__ __forceinline__ void finish(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
                                                   const F4& acc) {
-        store_chunk<NT>(tb.x[gq.base + k], c, gq.lim, vec, acc);
+        store_chunk<SP>(tb.x[gq.base + k], c, gq.lim, vec, acc);
     }
 };
 
@@ -96,11 +96,10 @@ int sgd_mix(const mx_sgd_mix_call* c, const mx_param_runs* runs, const float* gs
     if (c->total_tiles <= 0) return MX_OK;
     const bool mom = c->mom != 0.0f;
     // bytes the round moves: x read + written, g read (+ zeroed), m read + written
-    const bool nt = g_tune.streaming(c->total_tiles, pick(c->n_local).tile, c->n_local,
-                                     4 * (3 + (mom ? 2 : 0) + (c->zero_grads ? 1 : 0)));
+    const int bpe = 4 * (3 + (mom ? 2 : 0) + (c->zero_grads ? 1 : 0));
     const SgdHyper h{lr, c->wd, c->mom, lr_dev, gscale, c->nesterov != 0, c->zero_grads != 0};
-    return mom ? dispatch<SgdMix<true>>(g_tune, r, nt, h, runs, c->x_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev)
-               : dispatch<SgdMix<false>>(g_tune, r, nt, h, runs, c->x_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev);
+    return mom ? dispatch<SgdMix<true>>(g_tune, r, bpe, h, runs, c->x_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev)
+               : dispatch<SgdMix<false>>(g_tune, r, bpe, h, runs, c->x_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev);
 }
 }  // namespace
 

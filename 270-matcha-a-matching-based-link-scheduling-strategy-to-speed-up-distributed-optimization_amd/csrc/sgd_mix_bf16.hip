@@ -81,17 +81,17 @@ struct SgdMixBf16 {
                                                 const GroupedIf<Hyper, GROUPED>& h) {
         return sgd_chunk<MOM, GROUPED>(ln.X[t], grad_of(ln.G[t], h, k), ln.Mv[t], c, gq, st, h);
     }
-    template <bool NT>
+    template <int SP>
     static __device__ __forceinline__ void keep(const Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
                                                 bool vec, const Hyper& h) {
-        if constexpr (MOM) store_chunk<NT>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
-        if (h.zero_grads) store_chunk<NT>(tb.g[gq.base + k], c, gq.lim, vec, U2{0u, 0u});
+        if constexpr (MOM) store_chunk<SP>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
+        if (h.zero_grads) store_chunk<SP>(tb.g[gq.base + k], c, gq.lim, vec, U2{0u, 0u});
     }
-    template <bool NT>
+    template <int SP>
     static __device__ __forceinline__ void finish(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
                                                   const F4& acc) {
-        store_chunk<NT>(tb.w[gq.base + k], c, gq.lim, vec, acc);
-        store_chunk<NT>(tb.p[gq.base + k], c, gq.lim, vec, pack4(acc));         // the model row: bf16 of the stored w
+        store_chunk<SP>(tb.w[gq.base + k], c, gq.lim, vec, acc);
+        store_chunk<SP>(tb.p[gq.base + k], c, gq.lim, vec, pack4(acc));         // the model row: bf16 of the stored w
     }
 };
 
@@ -112,12 +112,11 @@ int sgd_mix_bf16(const mx_sgd_mix_bf16_call* c, const mx_param_runs* runs, const
     if (c->total_tiles <= 0) return MX_OK;
     const bool mom = c->mom != 0.0f;
     // bytes the round moves: w read + written, g read (+ zeroed), p written, m read + written
-    const bool nt = g_tune.streaming(c->total_tiles, pick(c->n_local).tile, c->n_local,
-                                     12 + (mom ? 8 : 0) + (c->zero_grads ? 2 : 0));
+    const int bpe = 12 + (mom ? 8 : 0) + (c->zero_grads ? 2 : 0);
     const SgdHyper h{lr, c->wd, c->mom, lr_dev, gscale, c->nesterov != 0, c->zero_grads != 0};
-    return mom ? dispatch<SgdMixBf16<true>>(g_tune, r, nt, h, runs, c->w_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev,
+    return mom ? dispatch<SgdMixBf16<true>>(g_tune, r, bpe, h, runs, c->w_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev,
                                             c->p_ptrs_dev)
-               : dispatch<SgdMixBf16<false>>(g_tune, r, nt, h, runs, c->w_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev,
+               : dispatch<SgdMixBf16<false>>(g_tune, r, bpe, h, runs, c->w_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev,
                                              c->p_ptrs_dev);
 }
 }  // namespace

@@ -143,6 +143,15 @@ int mx_mix_tile(int n_slots);
  *                  512-column sub-tiles (default 1; headline 0.2627 -> 0.2591 ms)
  *   mean_wgpc      mx_mean_rows_to's tile kernel on rounds moving > 64 MB: workgroups per CU (default
  *                  3; 0 = as many as fit) -- 8 x 25.6M in place 0.2796 -> 0.2590 ms (tools/occ_sweep.py)
+ *   store_policy   cache policy of the 16-byte row stores of the streaming (non-temporal) launches of the
+ *                  row kernel's 8- and 16-slot classes and of mx_mean_rows_to's tile kernel: 1 = nt (the
+ *                  line stays dirty in the write-back L2 until evicted), 2 = sc1, 3 = sc1 nt, 4 = sc0 sc1
+ *                  (written through, the line dropped), forced at every size; 0 = auto (default): sc1 nt
+ *                  for rounds moving > 320 MB, nt below (rows the caches hold are found there by the next
+ *                  round).  Element tails, rows that are not 16-byte aligned, launches without streaming
+ *                  hints and every other kernel keep their stores.  Never changes a bit.  In one process,
+ *                  nt -> sc1 nt: 8 x 25.6M 0.2616 -> 0.2565 ms, 8 x 36.5M 0.3725 -> 0.3673 ms, the mean
+ *                  of 8 x 25.6M 0.2629 -> 0.2584 ms (tools/store_policy_ab.py)
  *   spec_launches  (mx_mix_get only) SPEC launches so far in this process, modulo 2^31
  *   ns48           33-48 slots: 1 = a 48-slot row-kernel class instead of the 64-slot one (default 0)
  *   rows_pf2       row kernel, persistent grids of 32-64 slots: two tiles' loads in flight instead of
@@ -288,8 +297,10 @@ int mx_gossip_mix_bf16_at(uint16_t* const* seg_ptrs_dev, const int64_t* seg_len_
  * mx_sgd_mix_set / _get: "nontemporal" (1 / 0 / 2 = auto as mx_mix_set's, on the bytes the round moves),
  * "wgpc" (8 / 16 rows on the flat grid: workgroups per CU, 0 = as many as fit), "blocks_per_cu"
  * (persistent grids), "flat_small" (8 / 16 rows: one workgroup per 512-column work item up to this many
- * x the persistent grid), "grid" (> 0: exact persistent grid size).  Speed only, never bits; none of
- * them changes the tile. */
+ * x the persistent grid), "grid" (> 0: exact persistent grid size), "store_policy" (the 16-byte stores
+ * of x, m, v and the masters in the streaming launches of the 8- and 16-row classes, as mx_mix_set's:
+ * 1 = nt, 2 = sc1, 3 = sc1 nt forced at every size, 0 = auto; the 8-byte bf16 stores stay nt).  Speed
+ * only, never bits; none of them changes the tile. */
 typedef struct mx_sgd_mix_call {
     float* const* x_ptrs_dev;
     float* const* g_ptrs_dev;
@@ -340,7 +351,7 @@ int mx_sgd_mix_at(const mx_sgd_mix_call* call, const int64_t* iter_dev, int64_t 
  * [1, 32], a momentum table that does not match mom, nesterov without momentum, a null table -- p
  * included) and the launch-side no-ops (a peer-reads plan record; for _at a counter outside
  * [0, n_iters): none of the four arrays is written, the SGD step included) are mx_sgd_mix's.
- * mx_sgd_mix_bf16_set / _get: "nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid", as
+ * mx_sgd_mix_bf16_set / _get: "nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid", "store_policy", as
  * mx_sgd_mix_set's and independent of them.  Speed only, never bits; none of them changes the tile. */
 typedef struct mx_sgd_mix_bf16_call {
     float* const* w_ptrs_dev;
@@ -403,7 +414,7 @@ int mx_sgd_mix_bf16_at(const mx_sgd_mix_bf16_call* call, const int64_t* iter_dev
  * advanced by the caller, e.g. mx_iter_advance).  An iteration counter outside [0, n_iters) or a step
  * below 1 makes the launch a complete no-op: none of x, g, m, v is written.  So does a plan record with
  * the peer-reads bit, in either form.
- * mx_adamw_mix_set / _get: "nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid", as
+ * mx_adamw_mix_set / _get: "nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid", "store_policy", as
  * mx_sgd_mix_set's and independent of them.  Speed only, never bits; none of them changes the tile. */
 typedef struct mx_adamw_mix_call {
     float* const* x_ptrs_dev;
@@ -469,7 +480,7 @@ int mx_adamw_mix_at(const mx_adamw_mix_call* call, const int64_t* iter_dev, int6
  * [1, 32], n_bias < 1, step < 1, a null table -- p included) and the launch-side no-ops (a peer-reads
  * plan record; for _at an iteration counter outside [0, n_iters) or a step counter below 1: none of the
  * five arrays is written) are mx_adamw_mix's.
- * mx_adamw_mix_bf16_set / _get: "nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid", as
+ * mx_adamw_mix_bf16_set / _get: "nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid", "store_policy", as
  * mx_adamw_mix_set's and independent of them.  Speed only, never bits; none of them changes the tile. */
 typedef struct mx_adamw_mix_bf16_call {
     float* const* w_ptrs_dev;
