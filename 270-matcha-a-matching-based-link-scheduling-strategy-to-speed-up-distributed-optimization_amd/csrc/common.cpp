@@ -16,6 +16,25 @@ void set_error(const char* fmt, ...) {
 int g_mean_wgpc = 3;
 int g_store_policy = 0;
 
+int cu_count() {
+    static int v = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return 256;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 256;
+        return n > 0 ? n : 256;
+    }();
+    return v;
+}
+
+int tile_prefix(const char* who, int tile, const int64_t* seg_len_host, int nseg, int64_t* tile_off_host) {
+    tile_off_host[0] = 0;
+    for (int s = 0; s < nseg; ++s) {
+        MX_CHECK(seg_len_host[s] >= 0, "%s: negative length", who);
+        tile_off_host[s + 1] = tile_off_host[s] + (seg_len_host[s] + tile - 1) / tile;
+    }
+    return MX_OK;
+}
+
 int lds_per_cu() {
     static int v = [] {
         int dev = 0, n = 0;

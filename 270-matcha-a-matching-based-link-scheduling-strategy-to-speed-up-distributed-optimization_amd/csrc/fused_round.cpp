@@ -19,12 +19,7 @@ int layout(const char* who, const int64_t* seg_len_host, int nseg, int n_slots, 
     MX_CHECK(seg_len_host && tile_off_host && nseg >= 1, "%s: bad arguments", who);
     const int tile = pick(n_slots).tile;
     MX_CHECK(tile > 0, "%s: n_slots=%d outside [1, 64]", who, n_slots);
-    tile_off_host[0] = 0;
-    for (int s = 0; s < nseg; ++s) {
-        MX_CHECK(seg_len_host[s] >= 0, "%s: negative length", who);
-        tile_off_host[s + 1] = tile_off_host[s] + (seg_len_host[s] + tile - 1) / tile;
-    }
-    return MX_OK;
+    return mx::tile_prefix(who, tile, seg_len_host, nseg, tile_off_host);
 }
 
 int Tune::set(const char* who, const char* key, int value) {
@@ -75,16 +70,6 @@ int Tune::policy(bool nt, int64_t total_tiles, int tile, int n_local, int bytes_
     if (store_policy > 0) return store_policy;
     const int64_t ws = total_tiles * (int64_t)tile * n_local * bytes_per_elem;
     return ws > mx::kStoreAutoBytes ? kAutoPolicy : mx::kStoreNt;
-}
-
-static int cu_count() {
-    static int v = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 256;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 256;
-        return n > 0 ? n : 256;
-    }();
-    return v;
 }
 
 int64_t Tune::grid_of(int ns, int64_t work, bool* flat) const {

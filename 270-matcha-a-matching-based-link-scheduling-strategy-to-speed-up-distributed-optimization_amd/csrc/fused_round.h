@@ -27,29 +27,31 @@
 #pragma once
 #include "fused_host.h"
 #include "mx_common.h"
+#include "row_walk.h"
 
 #include <type_traits>
 
 namespace mx {
 namespace fused {
+// the access helpers and the fp32 chunk the families use too; the kernel names the rest as rows::
+using rows::al16;
+using rows::F4;
+using rows::fma4;
+using rows::GPtr;
+using rows::kMaxM;
+using rows::ld2;
+using rows::st2;
 
 constexpr int kTPB = 256;
-constexpr int kMaxM = 32;
 constexpr int kWV = kTPB / 64;
 // 16-byte chunks of every array a lane has in flight at once: 2 keeps the 8-row SGD kernel at 68 VGPRs
 // (7 waves per SIMD) and measured 3 % faster on the headline shape than 4 (94 VGPRs, 5 waves); for AdamW
 // it is 32 VGPRs of loads in flight (the bf16 families hold g in 2 registers, not 4)
 constexpr int kB = 2;
 
-typedef float F4 __attribute__((ext_vector_type(4)));
 typedef float F2 __attribute__((ext_vector_type(2)));
 typedef __bf16 B2 __attribute__((ext_vector_type(2)));
 typedef uint32_t U2 __attribute__((ext_vector_type(2)));      // 4 bf16: one 8-byte access
-
-// global (not flat) accesses: counted on vmcnt only, so the LDS waits of the partner walk do not
-// drain the HBM stream (see mix.hip)
-template <typename T>
-using GPtr = __attribute__((address_space(1))) T*;
 
 template <bool NT>
 __device__ __forceinline__ F4 ld16(const float* p) {
@@ -76,9 +78,6 @@ __device__ __forceinline__ void st8(uint16_t* p, const U2& v) {
 }
 __device__ __forceinline__ float ld4(const float* p) { return *(GPtr<const float>)(p); }
 __device__ __forceinline__ void st4(float* p, float v) { *(GPtr<float>)(p) = v; }
-__device__ __forceinline__ uint32_t ld2(const uint16_t* p) { return *(GPtr<const uint16_t>)(p); }
-__device__ __forceinline__ void st2(uint16_t* p, uint32_t v) { *(GPtr<uint16_t>)(p) = (uint16_t)v; }
-__device__ __forceinline__ bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 __device__ __forceinline__ bool al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 
 // one lane's chunk of 4 elements at column c of `row`: one wide access on the vector path (`vec`: the
@@ -150,11 +149,6 @@ __device__ __forceinline__ U2 pack4(const F4& a) {
     return v;
 }
 
-__device__ __forceinline__ void fma4(F4& a, float w, const F4& x) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) a[t] = __builtin_fmaf(w, x[t], a[t]);
-}
-
 // the clip factor of the row (mx_*_scaled): g' = fmul(gscale[r], f32(g)), before anything else in the update
 __device__ __forceinline__ F4 scale4(const F4& g, float s) {
     F4 v;
@@ -197,19 +191,6 @@ struct Geo {
     float wd, scale;
 };
 
-template <int NS>
-struct PlanLds {
-    int32_t w[mx::kPlanHeader + 2 * NS + NS * kMaxM];
-};
-
-// The round to run: `iter`, or with iter_dev (graph-replayable launches) the device counter
-// *iter_dev, `iter` then being the schedule length; outside [0, length) the launch is a no-op.
-__device__ __forceinline__ int64_t round_of(int64_t iter, const int64_t* iter_dev) {
-    if (!iter_dev) return iter;
-    const int64_t v = *iter_dev;
-    return (v >= 0 && v < iter) ? v : -1;
-}
-
 // NS rows x TW columns per work item; a layout tile (mx_*_tile) is `split` work items.
 // GROUPED: per-run weight decay and learning-rate scale (see Runs above).  SP: the store policy of the
 // 16-byte stores (mx::StorePolicy; the loads follow NT).  T...: Update::Tabs' members.
@@ -228,7 +209,7 @@ __global__ __launch_bounds__(kTPB) void fused_round_rows(T __restrict__... tabs,
     static_assert(NQ >= 1 && NI <= 64 && NI % kWV == 0 && E % kB == 0 && E * kTPB == NS * C4 && C4 % 64 == 0,
                   "fused row kernel geometry");
     __shared__ F4 lds[NS * C4];
-    __shared__ PlanLds<NS> sp;
+    __shared__ rows::PlanLds<NS> sp;
     __shared__ int32_t wl[kWV][NI / kWV];
     const typename Update::Tabs tb{tabs...};
     const int tid = threadIdx.x;
@@ -283,46 +264,25 @@ __global__ __launch_bounds__(kTPB) void fused_round_rows(T __restrict__... tabs,
     // in every round, so they wait for nothing
     Geo cur = geo(blockIdx.x);
     issue(cur, 0);
-    const int64_t rnd = round_of(iter, iter_dev);
+    const int64_t rnd = rows::round_of(iter, iter_dev);
     if (rnd < 0) return;                     // counter outside the schedule: nothing is written
     typename Update::State st;
     if (Update::no_step(st, h)) return;      // no such optimizer step: nothing is written
-    {
-        const int64_t W = mx::plan_words(n_local, M);
-        const int32_t* rec = plan + rnd * W;
-        for (int i = tid; i < W; i += kTPB) sp.w[i] = rec[i];
-    }
-    __syncthreads();
+    rows::copy_plan<NS, kTPB>(sp, plan, rnd, n_local, M);
     if (sp.w[2] & 2) return;                 // peer-reads record: not this kernel's (nothing is written)
     const bool active = sp.w[0] != 0;
     const bool idle = (sp.w[2] & 1) != 0;
-    const int32_t* deg = sp.w + mx::kPlanHeader;
-    const float* sw = reinterpret_cast<const float*>(deg + n_local);
-    const int32_t* src = deg + 2 * n_local;
+    const rows::Plan pv = rows::view(sp, n_local);
     // rows that get the FMA chain (degree > 0, or every row of an active round in idle mode 1); every
     // other row stores x' as it is
-    auto mixes = [&](int r) { return active && (deg[r] > 0 || idle); };
-    auto degree = [&](int r) { return mixes(r) ? deg[r] : 0; };
+    auto mixes = [&](int r) { return active && (pv.deg[r] > 0 || idle); };
+    auto degree = [&](int r) { return mixes(r) ? pv.deg[r] : 0; };
     Update::setup(st, h);
 
-    // deal the items (row r, pass q) = r * NQ + q to the waves: wave 0 ranks them by weight
-    // (degree + 1), snake order over the waves
-    if (wave == 0) {
-        const int r = lane / NQ;
-        const int w = (lane < NI && r < n_local) ? degree(r) + 1 : 0;
-        int rank = 0;
-        for (int j = 0; j < NI; ++j) {
-            const int wj = __builtin_amdgcn_readlane(w, j);
-            rank += (wj > w) || (wj == w && j < lane);
-        }
-        const int round = rank / kWV, within = rank % kWV;
-        if (lane < NI) wl[(round & 1) ? kWV - 1 - within : within][round] = w > 0 ? lane : -1;
-    }
+    // every row is dealt, by weight degree + 1
+    if (wave == 0) rows::deal<NQ, NI, kWV>(wl, lane, [&](int r) { return r < n_local ? degree(r) + 1 : 0; });
     __syncthreads();
-    // ranks grow along a wave's list, so its unused (-1) entries form a suffix
-    int nmy = 0;
-    while (nmy < NI / kWV && wl[wave][nmy] >= 0) ++nmy;
-    nmy = __builtin_amdgcn_readfirstlane(nmy);
+    const int nmy = rows::count(wl[wave]);
 
     // the update of the chunks in flight: x' parked in LDS, the lane's state (and the zeros over g) stored
     auto park = [&](const Geo& gq, int j0) {
@@ -344,44 +304,11 @@ __global__ __launch_bounds__(kTPB) void fused_round_rows(T __restrict__... tabs,
             const int r = it / NQ;
             const int col = (it % NQ) * 64 + lane;
             const F4 self = lds[r * C4 + col];
-            if (mixes(r)) fma4(acc, sw[r], self);                    // the self term, last
+            if (mixes(r)) fma4(acc, pv.sw[r], self);                    // the self term, last
             else acc = self;                                         // x' as it is
             Update::template finish<SP>(tb, g, r, g.col0 + (int64_t)col * 4, Update::vec_of(tb, g, r), acc);
         };
-        int p = 0;
-        for (; p + 1 < nmy; p += 2) {            // two items interleaved
-            const int ia = __builtin_amdgcn_readfirstlane(wl[wave][p]);
-            const int ib = __builtin_amdgcn_readfirstlane(wl[wave][p + 1]);
-            const int ra = ia / NQ, rb = ib / NQ;
-            const int ca = (ia % NQ) * 64 + lane, cb = (ib % NQ) * 64 + lane;
-            const int da = degree(ra), db = degree(rb);
-            const int dmin = da < db ? da : db;
-            F4 a = {0.0f, 0.0f, 0.0f, 0.0f}, b = {0.0f, 0.0f, 0.0f, 0.0f};
-            int e = 0;
-            for (; e < dmin; ++e) {
-                const int sa = __builtin_amdgcn_readfirstlane(src[ra * M + e]);
-                const int sb = __builtin_amdgcn_readfirstlane(src[rb * M + e]);
-                const F4 xa = lds[sa * C4 + ca];
-                const F4 xb = lds[sb * C4 + cb];
-                fma4(a, alpha, xa);
-                fma4(b, alpha, xb);
-            }
-            for (int ea = e; ea < da; ++ea)
-                fma4(a, alpha, lds[__builtin_amdgcn_readfirstlane(src[ra * M + ea]) * C4 + ca]);
-            for (int eb = e; eb < db; ++eb)
-                fma4(b, alpha, lds[__builtin_amdgcn_readfirstlane(src[rb * M + eb]) * C4 + cb]);
-            finish(ia, a);
-            finish(ib, b);
-        }
-        if (p < nmy) {
-            const int ia = __builtin_amdgcn_readfirstlane(wl[wave][p]);
-            const int ra = ia / NQ, ca = (ia % NQ) * 64 + lane;
-            const int da = degree(ra);
-            F4 a = {0.0f, 0.0f, 0.0f, 0.0f};
-            for (int e = 0; e < da; ++e)
-                fma4(a, alpha, lds[__builtin_amdgcn_readfirstlane(src[ra * M + e]) * C4 + ca]);
-            finish(ia, a);
-        }
+        rows::walk<rows::Fp32, NQ, C4>(lds, wl[wave], nmy, lane, pv.src, M, alpha, degree, finish);
     };
     for (int64_t i = 0; i < niter; ++i) {
         if (i) __syncthreads();              // every wave is done reading the previous tile

@@ -27,21 +27,15 @@
 // elements are in range, per-element loads elsewhere; nothing at or past seg_len enters the sum.  Plain
 // (temporal) loads: the fused launch reads the same gradient right afterwards.
 #include "mx_common.h"
+#include "row_walk.h"
 
 #include <cmath>
 
 namespace {
+using namespace mx::rows;        // GPtr, al16, F4, U4
 constexpr int kTPB = 256;
 constexpr int kWV = kTPB / 64;
 constexpr int kCols = 4096;          // columns per work item = per workspace slot (mx_grad_norm_cols)
-
-typedef float F4 __attribute__((ext_vector_type(4)));
-typedef uint32_t U4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-using GPtr = __attribute__((address_space(1))) T*;
-
-__device__ __forceinline__ bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 __device__ __forceinline__ double sq(double acc, float x) {
     const double d = (double)x;
@@ -168,16 +162,6 @@ struct Tune {
     int grid = 0;            // > 0: exact grid size (tests: few workgroups looping over many work items)
 };
 Tune g_tune;
-
-int cu_count() {
-    static int v = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 256;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 256;
-        return n > 0 ? n : 256;
-    }();
-    return v;
-}
 }  // namespace
 
 extern "C" int mx_grad_norm_cols(void) { return kCols; }
@@ -234,7 +218,7 @@ extern "C" int mx_grad_norm(const mx_grad_norm_call* c, void* stream) {
     hipStream_t st = mx::as_stream(stream);
     const int64_t total = c->chunks * c->n_local;
     if (total > 0) {
-        const int64_t target = g_tune.grid > 0 ? (int64_t)g_tune.grid : (int64_t)cu_count() * g_tune.blocks_per_cu;
+        const int64_t target = g_tune.grid > 0 ? (int64_t)g_tune.grid : (int64_t)mx::cu_count() * g_tune.blocks_per_cu;
         const int64_t grid = total < target ? total : target;
         if (c->elem_size == 4)
             hipLaunchKernelGGL(grad_norm_partials<4>, dim3((unsigned)grid), dim3(kTPB), 0, st, c->g_ptrs_dev,

@@ -27,14 +27,15 @@
 // <= 8 slots (mix_kernel_reg: one register vector per lane indexed through s_set_gpr_idx, no
 // LDS) and the LDS-column kernel (mix_kernel: per-lane columns, every row to the max degree).
 #include "mx_common.h"
+#include "row_walk.h"
 
 #include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
 namespace {
+using namespace mx::rows;
 constexpr int kTPB = 256;
-constexpr int kMaxM = 32;
 
 // VEC-wide float vectors as clang ext vectors (16-byte global_load/store_dwordx4 for VEC = 4;
 // the non-temporal builtins accept them)
@@ -46,12 +47,6 @@ template <>
 struct VT<2> { typedef float type __attribute__((ext_vector_type(2))); };
 template <>
 struct VT<1> { typedef float type __attribute__((ext_vector_type(1))); };
-
-// Row pointers arrive as generic pointers; accessing them through the global address space makes
-// the compiler emit global_load/store (counted on vmcnt only) instead of flat_* (counted on vmcnt
-// AND lgkmcnt, so every LDS or scalar-load wait in the loop would also drain the HBM stream).
-template <typename F>
-using GPtr = __attribute__((address_space(1))) F*;
 
 template <bool NT, typename F>
 __device__ __forceinline__ F ld(const float* p) {
@@ -75,29 +70,7 @@ __device__ __forceinline__ void st(float* p, const F& v) {
 }
 
 __device__ __forceinline__ float ld1(const float* p) { return *(GPtr<const float>)(p); }
-// 16-byte accesses are legal at row + 4i when the row pointer itself is 16-byte aligned: a scalar
-// test of the (wave-uniform) pointer, where the per-segment seg_vec byte would be a vector-memory
-// load -- a full round trip at the head of every workgroup before its first tile load
-__device__ __forceinline__ bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 __device__ __forceinline__ void st1(float* p, float v) { *(GPtr<float>)(p) = v; }
-
-
-// Plan record of this iteration, decoded into LDS (see mx_plan_build); returns the bit mask of
-// slots that must be loaded, or 0 when every flag of the round is 0.  Rows of degree 0 are left
-// untouched unless the record's idle word (mx_plan_set_idle) asks for the reference's
-// `0 + 1.0 * x` (then they are streamed like any other row, with selfweight 1).
-template <int NS>
-struct PlanLds {
-    int32_t w[mx::kPlanHeader + 2 * NS + NS * kMaxM];
-};
-
-// The round to mix: `iter`, or with iter_dev (graph-replayable launches) the device counter
-// *iter_dev, `iter` then being the schedule length; outside [0, length) the launch is a no-op.
-__device__ __forceinline__ int64_t round_of(int64_t iter, const int64_t* iter_dev) {
-    if (!iter_dev) return iter;
-    const int64_t v = *iter_dev;
-    return (v >= 0 && v < iter) ? v : -1;
-}
 
 // Remote-slot load path (PullTransport, plan word [2] bit 1 -- mx_plan_set_peer_reads): the receive
 // slots point at a peer GPU's IPC-mapped snapshot buffer, which this GPU's L2 holds as non-local
@@ -121,22 +94,19 @@ __device__ __forceinline__ void peer_acquire(int32_t mode_word) {
     }
 }
 
+// Plan record of this iteration, decoded into LDS (see mx_plan_build); returns the bit mask of
+// slots that must be loaded, or 0 when every flag of the round is 0.  Rows of degree 0 are left
+// untouched unless the record's idle word (mx_plan_set_idle) asks for the reference's
+// `0 + 1.0 * x` (then they are streamed like any other row, with selfweight 1).
 template <int NS>
 __device__ __forceinline__ uint64_t load_plan(PlanLds<NS>& sp, const int32_t* plan, int64_t iter,
                                               int n_local, int M) {
     if (iter < 0) return 0;                      // block-uniform: no barrier is skipped unevenly
-    const int64_t W = mx::plan_words(n_local, M);
-    const int32_t* rec = plan + iter * W;
-    for (int i = threadIdx.x; i < W; i += blockDim.x) sp.w[i] = rec[i];
-    __syncthreads();
+    copy_plan(sp, plan, iter, n_local, M);
     if (sp.w[0] == 0) return 0;
     peer_acquire(sp.w[2]);
     const int n_remote = sp.w[1];
-    const bool idle = (sp.w[2] & 1) != 0;
-    const int32_t* deg = sp.w + mx::kPlanHeader;
-    uint64_t need = 0;
-    for (int r = 0; r < n_local; ++r)
-        if (deg[r] > 0 || idle) need |= 1ull << r;
+    uint64_t need = local_need(sp, n_local);
     for (int k = 0; k < n_remote; ++k) need |= 1ull << (n_local + k);
     return need;
 }
@@ -570,24 +540,13 @@ __global__ __launch_bounds__(TPB) void mix_kernel_rows(float* const* __restrict_
     }
     const uint64_t need = load_plan<NS>(sp, plan, round_of(iter, iter_dev), n_local, M);
     if (need == 0) return;
-    const int32_t* deg = sp.w + mx::kPlanHeader;
-    const float* sw = reinterpret_cast<const float*>(deg + n_local);
-    const int32_t* src = deg + 2 * n_local;
+    const Plan pv = view(sp, n_local);
     auto stage_to = [&](F (&RR)[E4], const Geo& gq) { stage_mask(RR, gq, need); };
     auto stage = [&](const Geo& gq) { stage_to(R, gq); };
 
-    // deal the items (row r, pass q) = r * NQ + q to the waves: wave 0 ranks them by weight
-    if (wave == 0) {
-        const int r = lane / NQ;
-        const int w = (lane < NI && r < n_local && ((need >> r) & 1ull)) ? deg[r] + 1 : 0;
-        int rank = 0;
-        for (int j = 0; j < NI; ++j) {
-            const int wj = __builtin_amdgcn_readlane(w, j);
-            rank += (wj > w) || (wj == w && j < lane);
-        }
-        const int round = rank / WV, within = rank % WV;
-        if (lane < NI) wl[(round & 1) ? WV - 1 - within : within][round] = w > 0 ? lane : -1;
-    }
+    // the local rows of `need` are dealt, by weight degree + 1
+    if (wave == 0)
+        deal<NQ, NI, WV>(wl, lane, [&](int r) { return (r < n_local && ((need >> r) & 1ull)) ? pv.deg[r] + 1 : 0; });
     if constexpr (SPEC) {
         // received slots, and any local row the hint left out (a wrong hint costs time, never bits)
         const uint64_t rest = need & ~(hint & local_mask);
@@ -605,10 +564,7 @@ __global__ __launch_bounds__(TPB) void mix_kernel_rows(float* const* __restrict_
         }
     }
     __syncthreads();
-    // ranks grow along a wave's list, so its unused (-1) entries form a suffix
-    int nmy = 0;
-    while (nmy < NI / WV && wl[wave][nmy] >= 0) ++nmy;
-    nmy = __builtin_amdgcn_readfirstlane(nmy);
+    const int nmy = count(wl[wave]);
 
     // mix the tile staged in LDS (columns of `cur`) and store the local rows
     auto mix_tile = [&](const Geo& cur) {
@@ -616,57 +572,11 @@ __global__ __launch_bounds__(TPB) void mix_kernel_rows(float* const* __restrict_
             const int r = it / NQ;
             const int col = (it % NQ) * 64 + lane;
             const F xs = lds[r * C4 + col];
-            const float s = sw[r];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = __builtin_fmaf(s, xs[t], acc[t]);
+            fma4(acc, pv.sw[r], xs);                                    // the self term, last
             const int64_t c = cur.col0 + (int64_t)col * 4;
             store_one<4, SP>(cur.ptrs[r], c, cur.lim, al16(cur.ptrs[r]) && c + 4 <= cur.lim, acc);
         };
-        int p = 0;
-        for (; p + 1 < nmy; p += 2) {            // two items interleaved
-            const int ia = __builtin_amdgcn_readfirstlane(wl[wave][p]);
-            const int ib = __builtin_amdgcn_readfirstlane(wl[wave][p + 1]);
-            const int ra = ia / NQ, rb = ib / NQ;
-            const int ca = (ia % NQ) * 64 + lane, cb = (ib % NQ) * 64 + lane;
-            const int da = deg[ra], db = deg[rb];
-            const int dmin = da < db ? da : db;
-            F a = F{0.0f, 0.0f, 0.0f, 0.0f}, b = F{0.0f, 0.0f, 0.0f, 0.0f};
-            int e = 0;
-            for (; e < dmin; ++e) {
-                const int sa = __builtin_amdgcn_readfirstlane(src[ra * M + e]);
-                const int sb = __builtin_amdgcn_readfirstlane(src[rb * M + e]);
-                const F xa = lds[sa * C4 + ca];
-                const F xb = lds[sb * C4 + cb];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    a[t] = __builtin_fmaf(alpha, xa[t], a[t]);
-                    b[t] = __builtin_fmaf(alpha, xb[t], b[t]);
-                }
-            }
-            for (int ea = e; ea < da; ++ea) {
-                const F xa = lds[__builtin_amdgcn_readfirstlane(src[ra * M + ea]) * C4 + ca];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) a[t] = __builtin_fmaf(alpha, xa[t], a[t]);
-            }
-            for (int eb = e; eb < db; ++eb) {
-                const F xb = lds[__builtin_amdgcn_readfirstlane(src[rb * M + eb]) * C4 + cb];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) b[t] = __builtin_fmaf(alpha, xb[t], b[t]);
-            }
-            finish(ia, a);
-            finish(ib, b);
-        }
-        if (p < nmy) {
-            const int ia = __builtin_amdgcn_readfirstlane(wl[wave][p]);
-            const int ra = ia / NQ, ca = (ia % NQ) * 64 + lane;
-            F a = F{0.0f, 0.0f, 0.0f, 0.0f};
-            for (int e = 0; e < deg[ra]; ++e) {
-                const F xa = lds[__builtin_amdgcn_readfirstlane(src[ra * M + e]) * C4 + ca];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) a[t] = __builtin_fmaf(alpha, xa[t], a[t]);
-            }
-            finish(ia, a);
-        }
+        walk<Fp32, NQ, C4>(lds, wl[wave], nmy, lane, pv.src, M, alpha, [&](int r) { return pv.deg[r]; }, finish);
     };
     if constexpr (!PF2) {
         for (int64_t i = 0; i < niter; ++i) {
@@ -999,20 +909,10 @@ int unroll_for(int ns) {
     return g_tune.unroll;
 }
 
-int cu_count() {
-    static int v = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 256;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 256;
-        return n > 0 ? n : 256;
-    }();
-    return v;
-}
-
 // grid: CUs x blocks_per_cu persistent workgroups, never more than there are tiles; a single
 // segment is split into equal contiguous chunks (chunked = 1)
 inline int64_t grid_target() {
-    return g_tune.grid > 0 ? (int64_t)g_tune.grid : (int64_t)cu_count() * g_tune.blocks_per_cu;
+    return g_tune.grid > 0 ? (int64_t)g_tune.grid : (int64_t)mx::cu_count() * g_tune.blocks_per_cu;
 }
 inline int64_t grid_for(int64_t total_tiles) {
     int64_t grid = grid_target();
@@ -1025,7 +925,7 @@ inline int64_t grid_for(int64_t total_tiles) {
 // (graph-replayed rounds, tools/small_cfg.py; equal at 181k, the flat grid 1-3 % ahead from 4M on)
 inline bool rows_mid(int ns, int64_t total_tiles) {
     return ns == 8 && g_tune.mid_bpc > 0 && g_tune.flat_small > 0 && g_tune.grid == 0 &&
-           total_tiles <= (int64_t)g_tune.mid_tiles * cu_count();
+           total_tiles <= (int64_t)g_tune.mid_tiles * mx::cu_count();
 }
 
 // row kernel sub-tiles per layout tile: a sub-tile keeps >= 256 columns (one wave pass), and
@@ -1036,7 +936,7 @@ int row_split(int ns, int64_t total_tiles) {
     if (g_tune.split > 0) return g_tune.split < cap ? g_tune.split : cap;
     int s = 1;
     if (rows_mid(ns, total_tiles)) {
-        while (s < cap && 2 * total_tiles * s < 3 * (int64_t)cu_count() * g_tune.mid_bpc) s *= 2;
+        while (s < cap && 2 * total_tiles * s < 3 * (int64_t)mx::cu_count() * g_tune.mid_bpc) s *= 2;
         return s;
     }
     while (s < cap && 2 * total_tiles * s < 3 * grid_target()) s *= 2;
@@ -1077,7 +977,7 @@ int launch_rows(float* const* seg_ptrs, const int64_t* seg_len, const int64_t* t
     const int64_t work = total_tiles * SPLIT;
     // one workgroup per item only for 8-16 slots: with 32 / 64 slots (narrower tiles, longer partner
     // walks) the persistent grid stays faster (ER(32): 286 vs 350 us, ER(64): 324 vs 426 us)
-    const int64_t mid = rows_mid(NS, total_tiles) ? (int64_t)cu_count() * g_tune.mid_bpc : 0;
+    const int64_t mid = rows_mid(NS, total_tiles) ? (int64_t)mx::cu_count() * g_tune.mid_bpc : 0;
     const int64_t grid = mid ? (work < mid ? work : mid)
                          : (NS <= 16 && g_tune.flat_small > 0 && g_tune.grid == 0 &&
                             work <= (int64_t)g_tune.flat_small * grid_target()) ? work : grid_for(work);
@@ -1253,12 +1153,7 @@ extern "C" int mx_mix_layout(const int64_t* seg_len_host, int nseg, int n_slots,
     MX_CHECK(seg_len_host && tile_off_host && nseg >= 1, "mx_mix_layout: bad arguments");
     const int tile = mx_mix_tile(n_slots);
     MX_CHECK(tile > 0, "mx_mix_layout: n_slots=%d exceeds %d", n_slots, kWideMaxSlots);
-    tile_off_host[0] = 0;
-    for (int s = 0; s < nseg; ++s) {
-        MX_CHECK(seg_len_host[s] >= 0, "mx_mix_layout: negative length");
-        tile_off_host[s + 1] = tile_off_host[s] + (seg_len_host[s] + tile - 1) / tile;
-    }
-    return MX_OK;
+    return mx::tile_prefix("mx_mix_layout", tile, seg_len_host, nseg, tile_off_host);
 }
 
 namespace {
@@ -1362,7 +1257,7 @@ int gossip_mix(float* const* seg_ptrs_dev, const int64_t* seg_len_dev, const int
         int64_t cap = g_tune.wide_per_cu > 0 ? g_tune.wide_per_cu : 4;
         if (cap > 2048 / tpb) cap = 2048 / tpb;  // 32 waves per CU
         per_cu = per_cu > cap ? cap : per_cu < 1 ? 1 : per_cu;
-        int64_t grid = (int64_t)cu_count() * per_cu;
+        int64_t grid = (int64_t)mx::cu_count() * per_cu;
         const int64_t work = total_tiles * (tile_cols / (64 * vec));
         if (grid > work) grid = work;
         const bool nt = g_tune.nontemporal != 0;

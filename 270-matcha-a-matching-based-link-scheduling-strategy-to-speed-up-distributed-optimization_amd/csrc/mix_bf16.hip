@@ -19,23 +19,19 @@
 //
 // No receive slots: n_slots == n_local, the plan's n_remote is 0 and its peer-reads bit is never
 // set (the host entry points refuse anything else).
+#include "fused_host.h"
 #include "mx_common.h"
+#include "row_walk.h"
 
 #include <cstdlib>
 
 namespace {
+using namespace mx::rows;
 constexpr int kTPB = 256;
-constexpr int kMaxM = 32;
 constexpr int kWV = kTPB / 64;
 
-typedef uint32_t U4 __attribute__((ext_vector_type(4)));      // 8 bf16: one 16-byte access
 typedef float F2 __attribute__((ext_vector_type(2)));
 typedef __bf16 B2 __attribute__((ext_vector_type(2)));
-
-// global (not flat) accesses: counted on vmcnt only, so the LDS waits of the partner walk do not
-// drain the HBM stream (see mix.hip)
-template <typename T>
-using GPtr = __attribute__((address_space(1))) T*;
 
 template <bool NT>
 __device__ __forceinline__ U4 ld16(const uint16_t* p) {
@@ -49,9 +45,6 @@ __device__ __forceinline__ void st16(uint16_t* p, const U4& v) {
     if constexpr (NT) __builtin_nontemporal_store(v, g);
     else *g = v;
 }
-__device__ __forceinline__ uint32_t ld2(const uint16_t* p) { return *(GPtr<const uint16_t>)(p); }
-__device__ __forceinline__ void st2(uint16_t* p, uint32_t v) { *(GPtr<uint16_t>)(p) = (uint16_t)v; }
-__device__ __forceinline__ bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // one lane's chunk of 8 elements at column c of `row`: a 16-byte load when the row pointer is
 // 16-byte aligned and the chunk is in range, else 2-byte loads zero-filled from `lim` on
@@ -81,15 +74,6 @@ __device__ __forceinline__ void store_chunk(uint16_t* row, int64_t c, int64_t li
     }
 }
 
-// acc[0..7] = fmaf(w, f32(x[0..7]), acc[0..7]); f32() is the exact widening bits << 16
-__device__ __forceinline__ void fma8(float (&a)[8], float w, const U4& x) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        a[2 * t] = __builtin_fmaf(w, __builtin_bit_cast(float, x[t] << 16), a[2 * t]);
-        a[2 * t + 1] = __builtin_fmaf(w, __builtin_bit_cast(float, x[t] & 0xFFFF0000u), a[2 * t + 1]);
-    }
-}
-
 // the one rounding: fp32 -> bf16, to nearest even (v_cvt_pk_bf16_f32; NaN stays NaN)
 __device__ __forceinline__ U4 pack8(const float (&a)[8]) {
     U4 v;
@@ -101,35 +85,14 @@ __device__ __forceinline__ U4 pack8(const float (&a)[8]) {
     return v;
 }
 
-template <int NS>
-struct PlanLds {
-    int32_t w[mx::kPlanHeader + 2 * NS + NS * kMaxM];
-};
-
-// The round to mix: `iter`, or with iter_dev (graph-replayable launches) the device counter
-// *iter_dev, `iter` then being the schedule length; outside [0, length) the launch is a no-op.
-__device__ __forceinline__ int64_t round_of(int64_t iter, const int64_t* iter_dev) {
-    if (!iter_dev) return iter;
-    const int64_t v = *iter_dev;
-    return (v >= 0 && v < iter) ? v : -1;
-}
-
 // the round's plan record into LDS; returns the mask of rows read and written (degree > 0, or every
 // row of an active round in idle mode 1), 0 when the round has no active matching
 template <int NS>
 __device__ __forceinline__ uint64_t load_plan(PlanLds<NS>& sp, const int32_t* plan, int64_t iter, int n_local, int M) {
     if (iter < 0) return 0;                      // block-uniform
-    const int64_t W = mx::plan_words(n_local, M);
-    const int32_t* rec = plan + iter * W;
-    for (int i = threadIdx.x; i < W; i += blockDim.x) sp.w[i] = rec[i];
-    __syncthreads();
+    copy_plan(sp, plan, iter, n_local, M);
     if (sp.w[0] == 0) return 0;
-    const bool idle = (sp.w[2] & 1) != 0;
-    const int32_t* deg = sp.w + mx::kPlanHeader;
-    uint64_t need = 0;
-    for (int r = 0; r < n_local; ++r)
-        if (deg[r] > 0 || idle) need |= 1ull << r;
-    return need;
+    return local_need(sp, n_local);
 }
 
 // NS slots x TW columns per work item; a layout tile (mx_mix_bf16_tile) is `split` work items.
@@ -192,75 +155,24 @@ __global__ __launch_bounds__(kTPB) void mix_bf16_rows(uint16_t* const* __restric
     stage_mask(cur, hint & local_mask);
     const uint64_t need = load_plan<NS>(sp, plan, round_of(iter, iter_dev), n_local, M);
     if (need == 0) return;                   // all flags zero: no row is written
-    const int32_t* deg = sp.w + mx::kPlanHeader;
-    const float* sw = reinterpret_cast<const float*>(deg + n_local);
-    const int32_t* src = deg + 2 * n_local;
+    const Plan pv = view(sp, n_local);
 
-    // deal the items (row r, pass q) = r * NQ + q to the waves: wave 0 ranks them by weight
-    // (degree + 1), snake order over the waves
-    if (wave == 0) {
-        const int r = lane / NQ;
-        const int w = (lane < NI && r < n_local && ((need >> r) & 1ull)) ? deg[r] + 1 : 0;
-        int rank = 0;
-        for (int j = 0; j < NI; ++j) {
-            const int wj = __builtin_amdgcn_readlane(w, j);
-            rank += (wj > w) || (wj == w && j < lane);
-        }
-        const int round = rank / kWV, within = rank % kWV;
-        if (lane < NI) wl[(round & 1) ? kWV - 1 - within : within][round] = w > 0 ? lane : -1;
-    }
+    // the rows of `need` are dealt, by weight degree + 1
+    if (wave == 0)
+        deal<NQ, NI, kWV>(wl, lane, [&](int r) { return (r < n_local && ((need >> r) & 1ull)) ? pv.deg[r] + 1 : 0; });
     const uint64_t rest = need & ~(hint & local_mask);
     if (rest) stage_mask(cur, rest);
     __syncthreads();
-    // ranks grow along a wave's list, so its unused (-1) entries form a suffix
-    int nmy = 0;
-    while (nmy < NI / kWV && wl[wave][nmy] >= 0) ++nmy;
-    nmy = __builtin_amdgcn_readfirstlane(nmy);
+    const int nmy = count(wl[wave]);
 
     auto mix_tile = [&](const Geo& g) {
         auto finish = [&](int it, float (&acc)[8]) {
             const int r = it / NQ;
             const int col = (it % NQ) * 64 + lane;
-            fma8(acc, sw[r], lds[r * C8 + col]);                    // the self term, last
+            fma8(acc, pv.sw[r], lds[r * C8 + col]);                 // the self term, last
             store_chunk<NT>(g.ptrs[r], g.col0 + (int64_t)col * 8, g.lim, pack8(acc));
         };
-        int p = 0;
-        for (; p + 1 < nmy; p += 2) {            // two items interleaved
-            const int ia = __builtin_amdgcn_readfirstlane(wl[wave][p]);
-            const int ib = __builtin_amdgcn_readfirstlane(wl[wave][p + 1]);
-            const int ra = ia / NQ, rb = ib / NQ;
-            const int ca = (ia % NQ) * 64 + lane, cb = (ib % NQ) * 64 + lane;
-            const int da = deg[ra], db = deg[rb];
-            const int dmin = da < db ? da : db;
-            float a[8], b[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) a[t] = b[t] = 0.0f;
-            int e = 0;
-            for (; e < dmin; ++e) {
-                const int sa = __builtin_amdgcn_readfirstlane(src[ra * M + e]);
-                const int sb = __builtin_amdgcn_readfirstlane(src[rb * M + e]);
-                const U4 xa = lds[sa * C8 + ca];
-                const U4 xb = lds[sb * C8 + cb];
-                fma8(a, alpha, xa);
-                fma8(b, alpha, xb);
-            }
-            for (int ea = e; ea < da; ++ea)
-                fma8(a, alpha, lds[__builtin_amdgcn_readfirstlane(src[ra * M + ea]) * C8 + ca]);
-            for (int eb = e; eb < db; ++eb)
-                fma8(b, alpha, lds[__builtin_amdgcn_readfirstlane(src[rb * M + eb]) * C8 + cb]);
-            finish(ia, a);
-            finish(ib, b);
-        }
-        if (p < nmy) {
-            const int ia = __builtin_amdgcn_readfirstlane(wl[wave][p]);
-            const int ra = ia / NQ, ca = (ia % NQ) * 64 + lane;
-            float a[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) a[t] = 0.0f;
-            for (int e = 0; e < deg[ra]; ++e)
-                fma8(a, alpha, lds[__builtin_amdgcn_readfirstlane(src[ra * M + e]) * C8 + ca]);
-            finish(ia, a);
-        }
+        walk<Bf16, NQ, C8>(lds, wl[wave], nmy, lane, pv.src, M, alpha, [&](int r) { return pv.deg[r]; }, finish);
     };
     for (int64_t i = 0; i < niter; ++i) {
         if (i) __syncthreads();              // every wave is done reading the previous tile
@@ -280,9 +192,7 @@ __global__ __launch_bounds__(kTPB) void mix_bf16_rows(uint16_t* const* __restric
     }
 }
 
-struct Cls {
-    int ns, tile, tw;    // slot class, layout tile (columns), work-item width
-};
+using mx::fused::Cls;    // slot class, layout tile (columns), work-item width
 
 // twice the columns of the fp32 classes in the same LDS bytes; 8 / 16 slots are worked in
 // 1024-column halves of a 2048-column layout tile (16 / 32 KB of LDS per workgroup)
@@ -295,36 +205,17 @@ Cls pick(int n_slots) {
     return {0, 0, 0};
 }
 
-struct Tune {
-    int nontemporal = 2;   // 1 / 0: streaming hints on / off; 2 = auto (off for rounds of 32-320 MB, as mix.hip)
-    int wgpc = 0;          // 8 / 16 slots, flat grid: workgroups per CU cap (dynamic LDS); 0 = as many as fit
-    int blocks_per_cu = 2; // persistent grids (32 / 64 slots, or more work items than flat_small x the grid)
-    int flat_small = 256;  // 8 / 16 slots: one workgroup per work item up to flat_small x CUs x blocks_per_cu items
-    int grid = 0;          // > 0: exact persistent grid size (tests: few workgroups looping over many work items)
-    int split = 0;         // 8 / 16 slots: work items per 2048-column layout tile, 1 / 2 / 4 (0 = the default, 2)
-};
-Tune g_tune;
-
-int cu_count() {
-    static int v = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 256;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 256;
-        return n > 0 ? n : 256;
-    }();
-    return v;
-}
+// the knobs of the fused rounds (fused_host.h) without store_policy, and split: 8 / 16 slots, work items
+// per 2048-column layout tile, 1 / 2 / 4 (0 = the default, 2)
+mx::fused::Tune g_tune;
+int g_split = 0;
 
 template <int NS, int TW, bool NT>
 int launch(uint16_t* const* seg_ptrs, const int64_t* seg_len, const int64_t* tile_off, int nseg, int64_t total_tiles,
            int split, int n_slots, const int32_t* plan, int64_t iter, const int64_t* iter_dev, int n_local, int M,
            float alpha, uint64_t hint, hipStream_t st) {
-    const int64_t work = total_tiles * split;
-    const int64_t target = g_tune.grid > 0 ? (int64_t)g_tune.grid : (int64_t)cu_count() * g_tune.blocks_per_cu;
-    const bool flat = NS <= 16 && g_tune.grid == 0 && g_tune.flat_small > 0 &&
-                      work <= (int64_t)g_tune.flat_small * target;
-    int64_t grid = flat ? work : (work < target ? work : target);
-    if (grid < 1) grid = 1;
+    bool flat = false;
+    const int64_t grid = g_tune.grid_of(NS, total_tiles * split, &flat);
     size_t pad = 0;
     if (flat && g_tune.wgpc > 0) {
         static const int stat = [] {                           // static LDS of this instantiation
@@ -352,11 +243,9 @@ int gossip_mix_bf16(uint16_t* const* seg_ptrs, const int64_t* seg_len, const int
     MX_CHECK(iter >= 0, "mx_gossip_mix_bf16: iter < 0");
     if (total_tiles <= 0) return MX_OK;
     const Cls c = pick(n_slots);
-    const int split = (c.ns <= 16 && g_tune.split > 0) ? g_tune.split : c.tile / c.tw;
+    const int split = (c.ns <= 16 && g_split > 0) ? g_split : c.tile / c.tw;
     hipStream_t st = mx::as_stream(stream);
-    const int64_t ws = total_tiles * (int64_t)c.tile * n_slots * 2;
-    const bool nt = g_tune.nontemporal == 2 ? (ws <= ((int64_t)32 << 20) || ws > ((int64_t)320 << 20))
-                                            : g_tune.nontemporal != 0;
+    const bool nt = g_tune.streaming(total_tiles, c.tile, n_slots, 2);
 #define MX_B16(N, TW)                                                                                             \
     (nt ? launch<N, TW, true>(seg_ptrs, seg_len, tile_off, nseg, total_tiles, split, n_slots, plan, iter, iter_dev, \
                               n_local, M, alpha, hint, st)                                                        \
@@ -378,49 +267,25 @@ extern "C" int mx_mix_bf16_layout(const int64_t* seg_len_host, int nseg, int n_s
     MX_CHECK(seg_len_host && tile_off_host && nseg >= 1, "mx_mix_bf16_layout: bad arguments");
     const int tile = mx_mix_bf16_tile(n_slots);
     MX_CHECK(tile > 0, "mx_mix_bf16_layout: n_slots=%d outside [1, 64]", n_slots);
-    tile_off_host[0] = 0;
-    for (int s = 0; s < nseg; ++s) {
-        MX_CHECK(seg_len_host[s] >= 0, "mx_mix_bf16_layout: negative length");
-        tile_off_host[s + 1] = tile_off_host[s] + (seg_len_host[s] + tile - 1) / tile;
-    }
-    return MX_OK;
+    return mx::tile_prefix("mx_mix_bf16_layout", tile, seg_len_host, nseg, tile_off_host);
 }
 
 extern "C" int mx_mix_bf16_set(const char* key, int value) {
     MX_CHECK(key, "mx_mix_bf16_set: null key");
-    if (!strcmp(key, "nontemporal")) {
-        g_tune.nontemporal = value == 2 ? 2 : (value ? 1 : 0);
-    } else if (!strcmp(key, "wgpc")) {
-        MX_CHECK(value >= 0 && value <= 32, "mx_mix_bf16_set: wgpc %d", value);
-        g_tune.wgpc = value;
-    } else if (!strcmp(key, "blocks_per_cu")) {
-        MX_CHECK(value >= 1 && value <= 64, "mx_mix_bf16_set: blocks_per_cu %d", value);
-        g_tune.blocks_per_cu = value;
-    } else if (!strcmp(key, "flat_small")) {
-        MX_CHECK(value >= 0 && value <= 4096, "mx_mix_bf16_set: flat_small %d", value);
-        g_tune.flat_small = value;
-    } else if (!strcmp(key, "grid")) {
-        MX_CHECK(value >= 0 && value <= 65536, "mx_mix_bf16_set: grid %d", value);
-        g_tune.grid = value;
-    } else if (!strcmp(key, "split")) {
+    if (!strcmp(key, "split")) {
         MX_CHECK(value == 0 || value == 1 || value == 2 || value == 4, "mx_mix_bf16_set: split %d", value);
-        g_tune.split = value;
-    } else {
-        MX_CHECK(false, "mx_mix_bf16_set: unknown key '%s'", key);
+        g_split = value;
+        return MX_OK;
     }
-    return MX_OK;
+    MX_CHECK(strcmp(key, "store_policy"), "mx_mix_bf16_set: unknown key '%s'", key);
+    return g_tune.set("mx_mix_bf16_set", key, value);
 }
 
 extern "C" int mx_mix_bf16_get(const char* key) {
     if (!key) return MX_ERR_INVALID;
-    if (!strcmp(key, "nontemporal")) return g_tune.nontemporal;
-    if (!strcmp(key, "wgpc")) return g_tune.wgpc;
-    if (!strcmp(key, "blocks_per_cu")) return g_tune.blocks_per_cu;
-    if (!strcmp(key, "flat_small")) return g_tune.flat_small;
-    if (!strcmp(key, "split")) return g_tune.split;
-    if (!strcmp(key, "grid")) return g_tune.grid;
-    mx::set_error("mx_mix_bf16_get: unknown key '%s'", key);
-    return MX_ERR_INVALID;
+    if (!strcmp(key, "split")) return g_split;
+    MX_CHECK(strcmp(key, "store_policy"), "mx_mix_bf16_get: unknown key '%s'", key);
+    return g_tune.get("mx_mix_bf16_get", key);
 }
 
 extern "C" int mx_gossip_mix_bf16_packed(const mx_mix_call* c, int64_t iter, void* stream) {

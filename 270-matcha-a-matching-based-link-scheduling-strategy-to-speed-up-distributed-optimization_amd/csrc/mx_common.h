@@ -40,6 +40,13 @@ void set_error(const char* fmt, ...);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// compute units of the current device (256 when it cannot be asked)
+int cu_count();
+
+// mx_*_layout: the prefix of the segments' tile counts, tile_off[s + 1] = tile_off[s] + ceil(len[s] / tile);
+// `who` names the entry point in the error text (the caller has checked the pointers, nseg and tile > 0)
+int tile_prefix(const char* who, int tile, const int64_t* seg_len_host, int nseg, int64_t* tile_off_host);
+
 // Plan record geometry (see include/matcha_gossip.h, mx_plan_build)
 constexpr int kPlanHeader = 4;
 __host__ __device__ inline int64_t plan_words(int n_local, int M) {

@@ -108,4 +108,6 @@ def test_bf16_mix_refuses_before_launching(pkg):
     assert at(fake, fake, fake, fake, 1, 4, 8, fake, None, 10, 8, 5, 0.25, None) == -1
     assert b"counter" in L.mx_last_error()
     assert L.mx_mix_bf16_set(b"nope", 1) == -1 and L.mx_mix_bf16_get(b"nope") == -1
+    # the fused rounds' store_policy is no knob of the bf16 mixing round
+    assert L.mx_mix_bf16_set(b"store_policy", 1) == -1 and L.mx_mix_bf16_get(b"store_policy") == -1
     assert L.mx_mix_bf16_get(b"nontemporal") == 2 and L.mx_mix_bf16_get(b"wgpc") >= 0
