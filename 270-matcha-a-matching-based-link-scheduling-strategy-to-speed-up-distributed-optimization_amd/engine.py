@@ -700,6 +700,26 @@ class AdamwBf16Call(ctypes.Structure):
                 ("decoupled", ctypes.c_int32), ("zero_grads", ctypes.c_int32)]
 
 
+class LionMixCall(ctypes.Structure):
+    """mx_lion_mix_call (include/matcha_gossip.h): the fused Lion + mixing launch's arguments, packed once."""
+    _fields_ = [("x_ptrs_dev", ctypes.c_void_p), ("g_ptrs_dev", ctypes.c_void_p), ("m_ptrs_dev", ctypes.c_void_p),
+                ("seg_len_dev", ctypes.c_void_p), ("tile_off_dev", ctypes.c_void_p), ("plan_dev", ctypes.c_void_p),
+                ("total_tiles", ctypes.c_int64), ("nseg", ctypes.c_int32), ("n_slots", ctypes.c_int32),
+                ("n_local", ctypes.c_int32), ("M", ctypes.c_int32), ("alpha", ctypes.c_float),
+                ("wd", ctypes.c_float), ("omb1", ctypes.c_float), ("omb2", ctypes.c_float),
+                ("zero_grads", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+class LionBf16Call(ctypes.Structure):
+    """mx_lion_mix_bf16_call (include/matcha_gossip.h): the mixed-precision fused Lion launch's arguments."""
+    _fields_ = [("w_ptrs_dev", ctypes.c_void_p), ("g_ptrs_dev", ctypes.c_void_p), ("m_ptrs_dev", ctypes.c_void_p),
+                ("p_ptrs_dev", ctypes.c_void_p), ("seg_len_dev", ctypes.c_void_p), ("tile_off_dev", ctypes.c_void_p),
+                ("plan_dev", ctypes.c_void_p), ("total_tiles", ctypes.c_int64), ("nseg", ctypes.c_int32),
+                ("n_slots", ctypes.c_int32), ("n_local", ctypes.c_int32), ("M", ctypes.c_int32),
+                ("alpha", ctypes.c_float), ("wd", ctypes.c_float), ("omb1", ctypes.c_float),
+                ("omb2", ctypes.c_float), ("zero_grads", ctypes.c_int32), ("m_bf16", ctypes.c_int32)]
+
+
 SGD_TUNE_KEYS = ("nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid")
 
 # the ten entry points of a fused family, as suffixes of its C base name, in FusedFamily's field order
@@ -730,6 +750,9 @@ FAMILIES = {
     ("adamw", False): _family("mx_adamw_mix", AdamwMixCall, "x g m v", None, True, "fused AdamW + mixing"),
     ("adamw", True): _family("mx_adamw_mix_bf16", AdamwBf16Call, "w g m v p", None, True,
                              "mixed-precision fused AdamW + mixing"),
+    ("lion", False): _family("mx_lion_mix", LionMixCall, "x g m", None, False, "fused Lion + mixing"),
+    ("lion", True): _family("mx_lion_mix_bf16", LionBf16Call, "w g m p", None, False,
+                            "mixed-precision fused Lion + mixing"),
 }
 
 
@@ -754,6 +777,8 @@ sgd_mix_tuning, set_sgd_mix_tuning = _tuning_pair(FAMILIES["sgd", False])
 sgd_mix_bf16_tuning, set_sgd_mix_bf16_tuning = _tuning_pair(FAMILIES["sgd", True])
 adamw_mix_tuning, set_adamw_mix_tuning = _tuning_pair(FAMILIES["adamw", False])
 adamw_mix_bf16_tuning, set_adamw_mix_bf16_tuning = _tuning_pair(FAMILIES["adamw", True])
+lion_mix_tuning, set_lion_mix_tuning = _tuning_pair(FAMILIES["lion", False])
+lion_mix_bf16_tuning, set_lion_mix_bf16_tuning = _tuning_pair(FAMILIES["lion", True])
 
 
 def _f32(v):
@@ -773,12 +798,39 @@ def adam_hyper(betas, eps, wd, decoupled, zero_grads):
             int(bool(zero_grads)))
 
 
+def lion_hyper(betas, wd, zero_grads, m_bf16=None):
+    """The Lion records' words after alpha: wd, omb1, omb2, zero_grads, then pad_ (fp32 record) or, with
+    m_bf16 given, m_bf16 (mixed-precision record).  betas are the Python floats: omb1 / omb2 are rounded
+    from the fp64 values 1 - beta, as adam_hyper's."""
+    b1, b2 = float(betas[0]), float(betas[1])
+    return (_f32(wd), _f32(1.0 - b1), _f32(1.0 - b2), int(bool(zero_grads)), 0 if m_bf16 is None else int(bool(m_bf16)))
+
+
+def lion_arguments(betas, weight_decay, momentum_dtype, master_weights):
+    """attach_lion's own argument checks, a pure host function: (betas, weight_decay, m_bf16).  ValueError
+    for betas outside [0, 1), a negative weight decay, a momentum dtype other than float32 / bfloat16, and
+    bfloat16 momentum without master weights."""
+    betas = (float(betas[0]), float(betas[1]))
+    weight_decay = float(weight_decay)
+    if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+        raise ValueError(f"attach_lion: betas {betas} outside [0, 1)")
+    if not weight_decay >= 0.0:
+        raise ValueError("attach_lion: weight_decay must not be negative")
+    if momentum_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"attach_lion: momentum_dtype is torch.float32 or torch.bfloat16, not {momentum_dtype}")
+    m_bf16 = momentum_dtype == torch.bfloat16
+    if m_bf16 and not master_weights:
+        raise ValueError("attach_lion: bfloat16 momentum is the mixed-precision round's (a bfloat16 group with "
+                         "master_weights=True)")
+    return betas, weight_decay, m_bf16
+
+
 def pack_call(fam, tables, seg_len, tile_off, plan, bias, total_tiles, n_bias, nseg, n_slots, n_local, M, alpha32,
               hyper):
     """The call record of family `fam`, a pure function of integers and floats: `tables` are the device
     addresses of its pointer tables in fam.tables order (None: an absent table, NULL), seg_len / tile_off
     / plan / bias device addresses (bias and n_bias count for the Adam families only), `hyper` the words
-    of sgd_hyper / adam_hyper."""
+    of sgd_hyper / adam_hyper / lion_hyper."""
     head = (*tables, seg_len, tile_off, plan)
     if fam.adam:
         return fam.rec(*head, bias, total_tiles, n_bias, nseg, n_slots, n_local, M, alpha32, *hyper)
@@ -786,7 +838,7 @@ def pack_call(fam, tables, seg_len, tile_off, plan, bias, total_tiles, n_bias, n
 
 
 class FusedLayout:
-    """Pointer tables of a fused optimizer + mixing kernel (`family`, set by the four classes below): one
+    """Pointer tables of a fused optimizer + mixing kernel (`family`, set by the six classes below): one
     int64 device table [nseg, n_local] per pointer list -- row r's copy of segment s -- as `<t>_ptrs` for
     t in family.tables, the segment lengths (in elements) and the tile prefix; for the Adam families the
     bias-correction table (adam_bias_table) too.  The tile depends on n_local alone (no knob enters it), so
@@ -879,22 +931,50 @@ class AdamwBf16Layout(FusedLayout):
     call = AdamwLayout.call
 
 
-FUSED_LAYOUTS = {("sgd", False): SgdLayout, ("sgd", True): SgdBf16Layout,          # keyed as FAMILIES
-                 ("adamw", False): AdamwLayout, ("adamw", True): AdamwBf16Layout}
+class LionLayout(FusedLayout):
+    """csrc/lion_mix.hip: row r's copy of segment s, its gradient and its momentum buffer, fp32, lengths in
+    floats."""
+    family = FAMILIES["lion", False]
 
-# what attach_sgd / attach_adamw hold in _sgd / _adamw: the layout, the packed call record and its address,
+    def __init__(self, seg_lens, x_ptrs, g_ptrs, m_ptrs, n_local):
+        super().__init__(seg_lens, (x_ptrs, g_ptrs, m_ptrs), n_local)
+
+    def call(self, engine, betas, wd, zero_grads):
+        """betas are the Python floats (lion_hyper)"""
+        return self._pack(engine, lion_hyper(betas, wd, zero_grads))
+
+
+class LionBf16Layout(FusedLayout):
+    """csrc/lion_mix_bf16.hip: row r's fp32 master of segment s, its bfloat16 gradient, its momentum buffer
+    (fp32, or bfloat16 when the call is packed with m_bf16) and its bfloat16 model row, lengths in elements."""
+    family = FAMILIES["lion", True]
+
+    def __init__(self, seg_lens, w_ptrs, g_ptrs, m_ptrs, p_ptrs, n_local):
+        super().__init__(seg_lens, (w_ptrs, g_ptrs, m_ptrs, p_ptrs), n_local)
+
+    def call(self, engine, betas, wd, zero_grads, m_bf16=False):
+        return self._pack(engine, lion_hyper(betas, wd, zero_grads, m_bf16))
+
+
+FUSED_LAYOUTS = {("sgd", False): SgdLayout, ("sgd", True): SgdBf16Layout,          # keyed as FAMILIES
+                 ("adamw", False): AdamwLayout, ("adamw", True): AdamwBf16Layout,
+                 ("lion", False): LionLayout, ("lion", True): LionBf16Layout}
+
+# what attach_sgd / attach_adamw / attach_lion hold in _sgd / _adamw / _lion: the layout, the packed call record and its address,
 # then the family's own fields side by side, so that a step reads its launch functions in one lookup
 FusedState = collections.namedtuple("FusedState", ("layout", "call", "addr") + FusedFamily._fields)
 
 # optimizer -> its name in messages, the other optimizer, and how attach_* says that bfloat16 rows need masters
+# (the conflict check covers every other entry; the named one is looked at first)
 _OPTIMIZER_WORDS = {
     "sgd": ("SGD", "adamw", "a bfloat16 group needs fp32 master weights for its SGD step"),
     "adamw": ("AdamW", "sgd", "bfloat16 groups need fp32 master weights under AdamW"),
+    "lion": ("Lion", "adamw", "bfloat16 groups need fp32 master weights under Lion"),
 }
 
 
 def _attached(state, opt):
-    """The FusedState in a group's _sgd / _adamw slot, or the error of a group without one."""
+    """The FusedState in a group's _sgd / _adamw / _lion slot, or the error of a group without one."""
     if state is None:
         raise MXError(f"no {_OPTIMIZER_WORDS[opt][0]} state: call attach_{opt}() first")
     return state
@@ -1226,6 +1306,7 @@ class VirtualWorkerGroup:
         self._sgd = None                     # attach_sgd: the fused SGD + mixing launch's state
         self.master_arena = self.master_rows = None   # attach_sgd(master_weights=True): fp32 masters of bf16 rows
         self._adamw = None                   # attach_adamw: the fused AdamW + mixing launch's state
+        self._lion = None                    # attach_lion: the fused Lion + mixing launch's state
         self._clip = None                    # attach_*(clip_grad_norm=...): the norm launch's state (GradNorm)
         self._runs = None                    # attach_*(param_groups=...): the run tables (ParamRuns)
         self.param_runs = None               # ... and the merged run list [(start, end, weight_decay, lr_scale)]
@@ -1465,8 +1546,9 @@ class VirtualWorkerGroup:
         clip = clip_value(clip_grad_norm, who)
         if getattr(self, "_" + opt) is not None:
             raise RuntimeError(f"{who}: already attached")
-        if getattr(self, "_" + other) is not None:
-            raise RuntimeError(f"{who}: the group already carries {_OPTIMIZER_WORDS[other][0]} state (attach_{other})")
+        for o in [other] + [k for k in _OPTIMIZER_WORDS if k not in (opt, other)]:
+            if getattr(self, "_" + o) is not None:
+                raise RuntimeError(f"{who}: the group already carries {_OPTIMIZER_WORDS[o][0]} state (attach_{o})")
         if master_weights and self.dtype != torch.bfloat16:
             raise ValueError(f"{who}: master_weights=True is for bfloat16 groups; fp32 rows are their own masters")
         if self.dtype != torch.float32 and not master_weights:
@@ -1483,8 +1565,8 @@ class VirtualWorkerGroup:
                                       "fused kernel's 64 rows / 32 matchings")
         return who, cls, clip
 
-    def _state_arena(self):
-        return torch.zeros((self.n_local, self.ld), dtype=torch.float32, device="cuda")
+    def _state_arena(self, dtype=torch.float32):
+        return torch.zeros((self.n_local, self.ld), dtype=dtype, device="cuda")
 
     def _attach_fused(self, checked, param_groups, state, bias, hyper, call_args):
         """What attach_sgd / attach_adamw build alike once their own hyperparameters are checked (`checked`
@@ -1740,10 +1822,63 @@ class VirtualWorkerGroup:
         iteration counter, as one launch; returns seconds like communicate()."""
         return self._fused_communicate(self.adamw_step, lr)
 
+    # ------------------------------------------------------------------ fused Lion + mixing
+    def attach_lion(self, betas=(0.9, 0.99), weight_decay=0.0, zero_grads=True, master_weights=False,
+                    momentum_dtype=torch.float32, clip_grad_norm=None, param_groups=None):
+        """Give the group Lion's state (Chen et al. 2023: the weights step by +-lr along the sign of
+        (1 - beta1) g + beta1 m, the momentum follows (1 - beta2) g + beta2 m, the weight decay is
+        decoupled as AdamW's) so that one launch per iteration applies every worker's update and the
+        round's mix (csrc/lion_mix.hip).  Lion keeps ONE state array and has no step counter: it moves
+        the bytes of SGD with momentum.
+
+        Allocates `grad_arena` / `grads` as attach_sgd does (adopted parameters' .grad become views of
+        it; see attach_sgd on zero_grad) and `lion_exp_avg_arena` / `lion_exp_avg_rows` (zeros).  One
+        GPU only.
+
+        master_weights=True is the bfloat16 group's form (csrc/lion_mix_bf16.hip; a ValueError on an
+        fp32 group, and a bfloat16 group refuses to attach without it), as attach_sgd's: `master_arena`
+        / `master_rows` hold an fp32 master of every row, the gradient arena is bfloat16, and the launch
+        updates and mixes the MASTERS and rewrites `rows` as bf16(master).  momentum_dtype=torch.bfloat16
+        (mixed-precision groups only) keeps the momentum in bfloat16 as well: it is widened exactly for
+        the update and rounded to nearest even once at the store, which takes the round from 22 to 18
+        bytes per parameter and the state from 12 to 10 bytes per parameter and worker.  It is a
+        different optimizer from the fp32-momentum one by design: its checkpoints load only into groups
+        of the same momentum dtype.
+
+        clip_grad_norm and param_groups are attach_sgd's (the momentum sees the clipped gradient; a
+        group's "lr_scale" scales the +-lr step, its "weight_decay" the decoupled decay)."""
+        checked = self._fused_family("lion", master_weights, clip_grad_norm)
+        betas, weight_decay, m_bf16 = lion_arguments(betas, weight_decay, momentum_dtype, master_weights)
+        self.lion_exp_avg_arena = self._state_arena(momentum_dtype)
+        self.lion_exp_avg_rows = self.lion_exp_avg_arena[:, :self.numel]
+        self.lion_hyper = {"betas": betas, "weight_decay": weight_decay, "zero_grads": bool(zero_grads),
+                           "momentum_dtype": momentum_dtype}
+        call_args = (betas, weight_decay, zero_grads) + ((m_bf16,) if master_weights else ())
+        self._lion = self._attach_fused(checked, param_groups, {"m": self.lion_exp_avg_arena}, None, self.lion_hyper,
+                                        call_args)
+
+    def lion_step(self, it, lr, stream=None):
+        """Enqueue ONE launch: every local worker's Lion update at learning rate `lr`, then round `it`'s
+        mix of the updated rows.  Always launches -- an all-zero round is the Lion step alone -- and
+        returns whether the round mixed."""
+        return self._fused_step(_attached(self._lion, "lion"), it, lr, stream)
+
+    def lion_device_round(self, stream=None):
+        """Graph-replayable lion_step, as sgd_device_round: the round is read from `self.iter_dev` and the
+        learning rate from `self.lr_dev` when the kernel runs, then the counter is advanced.  A counter
+        outside the schedule makes the launch a no-op: no Lion step either."""
+        self._fused_device_round(_attached(self._lion, "lion"), stream)
+
+    def lion_communicate(self, lr):
+        """optimizer.step() + zero_grad() + communicate() of every worker at the group's own
+        iteration counter, as one launch; returns seconds like communicate()."""
+        return self._fused_communicate(self.lion_step, lr)
+
     def state_dict(self):
         """Checkpoint: the workers' rows and the iteration counter (resume on the same schedule);
         with attach_sgd(momentum != 0) the momentum rows too, with master_weights=True the fp32
-        master rows, and with attach_adamw the exp_avg / exp_avg_sq rows and the step count."""
+        master rows, with attach_adamw the exp_avg / exp_avg_sq rows and the step count, and with
+        attach_lion the lion_exp_avg rows (in the arena's dtype)."""
         state = {"kind": "decen", "iter": int(self.iter), "row_base": int(self.row_base),
                  "workers": list(self.workers), "rows": self.rows.detach().clone()}
         if self._sgd is not None and self.momentum_rows is not None:
@@ -1754,6 +1889,8 @@ class VirtualWorkerGroup:
             state["exp_avg_rows"] = self.exp_avg_rows.detach().clone()
             state["exp_avg_sq_rows"] = self.exp_avg_sq_rows.detach().clone()
             state["opt_step"] = int(self.opt_step)
+        if self._lion is not None:
+            state["lion_exp_avg_rows"] = self.lion_exp_avg_rows.detach().clone()
         return state
 
     def load_state_dict(self, state):
@@ -1773,8 +1910,15 @@ class VirtualWorkerGroup:
         if any(a is not None for a in adam) or state.get("opt_step") is not None:
             if self._adamw is None or any(a is None or tuple(a.shape) != tuple(self.rows.shape) for a in adam):
                 raise ValueError("checkpoint carries Adam state (exp_avg rows): attach_adamw() before loading it")
+        lion = state.get("lion_exp_avg_rows")
+        if lion is not None and (self._lion is None or tuple(lion.shape) != tuple(self.lion_exp_avg_rows.shape)
+                                 or lion.dtype != self.lion_exp_avg_rows.dtype):
+            raise ValueError("checkpoint carries Lion state (lion_exp_avg rows): attach_lion() with the same "
+                             "momentum_dtype before loading it")
         with torch.no_grad():
             self.rows.copy_(state["rows"])
+            if self._lion is not None:           # a checkpoint without them: the buffer starts as zeros
+                self.lion_exp_avg_rows.zero_() if lion is None else self.lion_exp_avg_rows.copy_(lion)
             if self._adamw is not None:          # a checkpoint without them: zero buffers, step 0
                 for rows, a in zip((self.exp_avg_rows, self.exp_avg_sq_rows), adam):
                     rows.zero_() if a is None else rows.copy_(a)

@@ -197,7 +197,8 @@ class VirtualTrainer:
     step for all workers is a handful of batched launches plus the gossip kernel."""
 
     def __init__(self, args, model_fn, n_batches, device="cuda", batched=False, graph=False, fused_sgd=False,
-                 fused_adamw=False, adamw_hyper=None, clip_grad_norm=None, param_groups=None):
+                 fused_adamw=False, adamw_hyper=None, clip_grad_norm=None, param_groups=None, fused_lion=False,
+                 lion_hyper=None):
         """fused_sgd=True (non-batched, uncompressed): the workers' optimizer.step() /
         zero_grad() and the gossip round run as ONE launch (VirtualWorkerGroup.attach_sgd /
         sgd_communicate, csrc/sgd_mix.hip): backward() accumulates into the group's gradient arena,
@@ -214,13 +215,19 @@ class VirtualTrainer:
         decoupled decay, or what adamw_hyper (attach_adamw's keyword arguments) overrides; checkpoints
         save exp_avg / exp_avg_sq rows and the step count.
 
-        clip_grad_norm=X (with fused_sgd or fused_adamw): torch.nn.utils.clip_grad_norm_(model.parameters(),
+        fused_lion=True (same conditions, not together with the other two): the same with the Lion update
+        in the launch (VirtualWorkerGroup.attach_lion / lion_communicate, csrc/lion_mix.hip; all-bfloat16
+        models in mixed precision, csrc/lion_mix_bf16.hip): betas (0.9, 0.99) and the harness's weight decay
+        5e-4 as the decoupled decay, or what lion_hyper (attach_lion's keyword arguments, momentum_dtype
+        among them) overrides; checkpoints save the lion_exp_avg rows.
+
+        clip_grad_norm=X (with fused_sgd, fused_adamw or fused_lion): torch.nn.utils.clip_grad_norm_(model.parameters(),
         X) per worker inside the fused step (attach_sgd / attach_adamw's keyword: one extra read of the
         gradient arena, csrc/grad_norm.hip).  `grad_norm_log` collects every round's pre-clip norms
         (a float32 CPU tensor [size] per round) and the epoch stats carry each worker's last one.  The
         other paths keep torch's optimizers and do not clip: asking for it there is a ValueError.
 
-        param_groups=[{...}, ...] (with fused_sgd or fused_adamw): attach_sgd / attach_adamw's keyword,
+        param_groups=[{...}, ...] (with fused_sgd, fused_adamw or fused_lion): attach_sgd / attach_adamw's keyword,
         per-group weight decay and learning-rate scale inside the fused step (e.g. no decay for biases
         and normalisation scales: [{"params": lambda name, p: p.ndim <= 1, "weight_decay": 0.0}]).
         A ValueError on the other paths, whose torch optimizers are built with one group.
@@ -245,13 +252,21 @@ class VirtualTrainer:
         if self.fused_adamw and (batched or args.compress):
             raise ValueError("fused_adamw needs per-worker (non-batched), uncompressed training: the vmap path's "
                              "gradients are fresh tensors every iteration and ChocoSGD mixes compressed messages")
+        self.fused_lion = bool(fused_lion)
+        if self.fused_lion and (self.fused_sgd or self.fused_adamw):
+            raise ValueError("fused_lion, fused_adamw and fused_sgd are mutually exclusive: the group carries one "
+                             "optimizer")
+        if self.fused_lion and (batched or args.compress):
+            raise ValueError("fused_lion needs per-worker (non-batched), uncompressed training: the vmap path's "
+                             "gradients are fresh tensors every iteration and ChocoSGD mixes compressed messages")
+        self.fused = self.fused_sgd or self.fused_adamw or self.fused_lion
         self.clip_grad_norm = clip_grad_norm
-        if clip_grad_norm is not None and not (self.fused_sgd or self.fused_adamw):
-            raise ValueError("clip_grad_norm is honoured by the fused optimizer steps only (fused_sgd=True or "
-                             "fused_adamw=True): the other paths step torch's optimizers and do not clip")
-        if param_groups is not None and not (self.fused_sgd or self.fused_adamw):
-            raise ValueError("param_groups is honoured by the fused optimizer steps only (fused_sgd=True or "
-                             "fused_adamw=True): the other paths step torch's optimizers with one group")
+        if clip_grad_norm is not None and not self.fused:
+            raise ValueError("clip_grad_norm is honoured by the fused optimizer steps only (fused_sgd=True, "
+                             "fused_adamw=True or fused_lion=True): the other paths step torch's optimizers and do not clip")
+        if param_groups is not None and not self.fused:
+            raise ValueError("param_groups is honoured by the fused optimizer steps only (fused_sgd=True, "
+                             "fused_adamw=True or fused_lion=True): the other paths step torch's optimizers with one group")
         self.grad_norm_log = []
         self.GP = make_topology(args, 0, size, args.epoch * n_batches)
         self.models = []
@@ -266,7 +281,7 @@ class VirtualTrainer:
             dts = {p.dtype for m in self.models for p in m.parameters()}
             self.group = VirtualWorkerGroup(self.GP, self.models,
                                             dtype=torch.bfloat16 if dts == {torch.bfloat16} else torch.float32)
-        mixed = (self.fused_sgd or self.fused_adamw) and self.group.dtype == torch.bfloat16
+        mixed = self.fused and self.group.dtype == torch.bfloat16
         if self.fused_sgd:
             # all-bfloat16 models: fp32 master weights, updated and mixed by the launch (csrc/sgd_mix_bf16.hip)
             self.group.attach_sgd(args.momentum, 5e-4, args.nesterov, master_weights=mixed,
@@ -277,6 +292,12 @@ class VirtualTrainer:
             hyper.update(adamw_hyper or {})
             self.group.attach_adamw(**hyper, master_weights=mixed, clip_grad_norm=clip_grad_norm,
                                     param_groups=param_groups)
+        if self.fused_lion:
+            # all-bfloat16 models: fp32 master weights, as above (csrc/lion_mix_bf16.hip)
+            hyper = {"betas": (0.9, 0.99), "weight_decay": 5e-4}
+            hyper.update(lion_hyper or {})
+            self.group.attach_lion(**hyper, master_weights=mixed, clip_grad_norm=clip_grad_norm,
+                                   param_groups=param_groups)
         sync_rows(self.group.rows)
         if mixed:
             self.group.master_from_rows()                        # the masters of the synchronized rows
@@ -457,7 +478,7 @@ class VirtualTrainer:
                     top1[r].update(acc1[0].item(), data.size(0))
                     loss.backward()
                     lr = update_learning_rate(opt, epoch, args, itr=b, itr_per_epoch=self.n_batches)
-                    if not (self.fused_sgd or self.fused_adamw):   # fused: the update runs inside the gossip launch
+                    if not self.fused:                             # fused: the update runs inside the gossip launch
                         opt.step()
                         opt.zero_grad()
                     comp[r] += time.time() - t0
@@ -467,6 +488,8 @@ class VirtualTrainer:
                 comm_time += self.group.sgd_communicate(lr)
             elif self.fused_adamw:
                 comm_time += self.group.adamw_communicate(lr)
+            elif self.fused_lion:
+                comm_time += self.group.lion_communicate(lr)
             else:
                 comm_time += self.communicate()              # train_mpi.py:142, all workers at once
             self._dev_iter_synced = False

@@ -645,6 +645,114 @@ int mx_adamw_mix_bf16_grouped_at(const mx_adamw_mix_bf16_call* call, const mx_pa
                                  const float* gscale_dev, const int64_t* iter_dev, int64_t n_iters,
                                  const int64_t* step_dev, float lr, const float* lr_dev, void* stream);
 
+/* ---------------------------------------------------------------- the hot path, Lion step fused in
+ * mx_sgd_mix with the Lion update (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms") in
+ * place of SGD's (csrc/lion_mix.hip): fp32 rows, one GPU, every partner local, one launch per training
+ * iteration.  Lion steps every weight by +-lr along the sign of an interpolation of gradient and momentum,
+ * with decoupled weight decay; it keeps ONE state array and needs no sqrt, no division, no bias table and
+ * no step counter.  Per row and column, every line one IEEE fp32 rounding:
+ *   decay = fmaf(-lr, wd, 1)                              once per launch
+ *   x1 = (wd != 0) ? fmul(x, decay) : x                   decoupled decay only, as AdamW's
+ *   dm = fsub(g, m)
+ *   c  = fmaf(omb1, dm, m)                                (1 - beta1) g + beta1 m in lerp form
+ *   x' = c > 0 ? fsub(x1, lr) : c < 0 ? fadd(x1, lr) : c == 0 ? x1 : NaN
+ *   m' = fmaf(omb2, dm, m)                                (1 - beta2) g + beta2 m
+ * and then mx_sgd_mix's round on the x' values (same plan record, alpha, selfweight, ascending matchings,
+ * self term last; a row the record leaves alone, and every row of an all-zero round, keeps x' as it is --
+ * an all-zero round is the Lion step alone, NOT a no-op).  omb1 / omb2 are the fp32 roundings of the fp64
+ * values 1 - beta; lr and wd the fp32 roundings of the Python floats.  c == 0 (either zero) leaves x1 BIT
+ * FOR BIT, an x1 of -0.0 included; a NaN c gives a NaN of any payload.  The momentum buffer starts as
+ * zeros; there is no first-step case.  Traffic: 20 bytes per element (24 with zero_grads), SGD with
+ * momentum's.
+ * mx_lion_mix_call is mx_sgd_mix_call with omb1 / omb2 in place of mom / nesterov: the three tables
+ * (m_ptrs_dev is never NULL), the tile (mx_lion_mix_tile: 1024 / 1024 / 512 / 256 columns, 0 above 64
+ * rows), the layout prefix, the alignment rule (16-byte accesses where x, g and m of a (segment, row) are
+ * all 16-byte aligned and the 4 elements are in range, 4-byte accesses elsewhere; nothing is written at or
+ * past seg_len of a row in any array), the host-side refusals (MX_ERR_INVALID, nothing launched:
+ * n_slots != n_local, more than 64 rows, M outside [1, 32], a null table -- m included) and the
+ * launch-side no-ops (a peer-reads plan record; for _at a counter outside [0, n_iters): x, g and m are not
+ * written, the Lion step included) are mx_sgd_mix's.  _scaled and _grouped are the other families':
+ * g' = fmul(gscale[r], g) before anything else; per run lr_r = fmul(lr, s_r), decay = fmaf(-lr_r, wd_r, 1),
+ * the step +-lr_r, the "wd != 0" test per run, the record's own wd ignored.
+ * mx_lion_mix_set / _get: "nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid", "store_policy", as
+ * mx_sgd_mix_set's and independent of them.  Speed only, never bits; none of them changes the tile. */
+typedef struct mx_lion_mix_call {
+    float* const* x_ptrs_dev;
+    float* const* g_ptrs_dev;
+    float* const* m_ptrs_dev;
+    const int64_t* seg_len_dev;
+    const int64_t* tile_off_dev;
+    const int32_t* plan_dev;
+    int64_t total_tiles;
+    int32_t nseg, n_slots, n_local, M;
+    float alpha, wd, omb1, omb2;
+    int32_t zero_grads, pad_;
+} mx_lion_mix_call;
+int mx_lion_mix_tile(int n_slots);
+int mx_lion_mix_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host);
+int mx_lion_mix_set(const char* key, int value);
+int mx_lion_mix_get(const char* key);
+int mx_lion_mix(const mx_lion_mix_call* call, int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_lion_mix_at(const mx_lion_mix_call* call, const int64_t* iter_dev, int64_t n_iters, float lr,
+                   const float* lr_dev, void* stream);
+int mx_lion_mix_scaled(const mx_lion_mix_call* call, const float* gscale_dev, int64_t iter, float lr,
+                       const float* lr_dev, void* stream);
+int mx_lion_mix_scaled_at(const mx_lion_mix_call* call, const float* gscale_dev, const int64_t* iter_dev,
+                          int64_t n_iters, float lr, const float* lr_dev, void* stream);
+int mx_lion_mix_grouped(const mx_lion_mix_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                        int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_lion_mix_grouped_at(const mx_lion_mix_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                           const int64_t* iter_dev, int64_t n_iters, float lr, const float* lr_dev, void* stream);
+
+/* ---------------------------------------------------------------- the hot path, mixed-precision Lion fused in
+ * mx_lion_mix for models held in bfloat16 (csrc/lion_mix_bf16.hip): the update runs on fp32 MASTER rows,
+ * the master rows are what the round mixes, and the bfloat16 model row is the rounded image of its master,
+ * rewritten by every launch.  Per (segment, row) four arrays, every length in elements:
+ *   w  float*    fp32 master, read and written in place
+ *   g  uint16_t* bfloat16 gradient, read; overwritten with zeros when zero_grads != 0
+ *   m  momentum, read and written: float* when m_bf16 == 0, uint16_t* (bfloat16) when m_bf16 != 0
+ *   p  uint16_t* bfloat16 model row, WRITE ONLY: the kernel never reads it
+ * Arithmetic contract: mx_lion_mix's lines on w with g32 = f32(g) (exact widening, bits << 16) and, for a
+ * bfloat16 momentum, m32 = f32(m) (exact) in place of m and bf16_rne(m') stored -- ONE rounding, to nearest
+ * even, at the store; then mx_lion_mix's round on the w' values and p = bf16_rne(w) of the value stored to w
+ * (NaN stays NaN, payload unspecified, in p and in a bfloat16 m alike).  p is written for every row in
+ * every launch that runs.  Nothing is written at or past seg_len of a row in any of the four arrays.
+ * Traffic: 20 bytes per element (22 with zero_grads) with fp32 momentum, 16 (18) with bfloat16 momentum.
+ * Alignment rule: a lane holds 4 elements; where w of a (segment, row) is 16-byte aligned, m is aligned to
+ * its own access (16 bytes fp32, 8 bytes bfloat16), g and p are 8-byte aligned and the 4 elements are in
+ * range, the accesses are wide; elsewhere they are per element (4 / 2 bytes), zero-filled past the end.
+ * The other fields, the tile, the layout prefix, the host-side refusals (a null table -- m and p included)
+ * and the launch-side no-ops are mx_lion_mix's; the knobs are independent of every other family's. */
+typedef struct mx_lion_mix_bf16_call {
+    float* const* w_ptrs_dev;
+    uint16_t* const* g_ptrs_dev;
+    void* const* m_ptrs_dev;
+    uint16_t* const* p_ptrs_dev;
+    const int64_t* seg_len_dev;
+    const int64_t* tile_off_dev;
+    const int32_t* plan_dev;
+    int64_t total_tiles;
+    int32_t nseg, n_slots, n_local, M;
+    float alpha, wd, omb1, omb2;
+    int32_t zero_grads, m_bf16;
+} mx_lion_mix_bf16_call;
+int mx_lion_mix_bf16_tile(int n_slots);
+int mx_lion_mix_bf16_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host);
+int mx_lion_mix_bf16_set(const char* key, int value);
+int mx_lion_mix_bf16_get(const char* key);
+int mx_lion_mix_bf16(const mx_lion_mix_bf16_call* call, int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_lion_mix_bf16_at(const mx_lion_mix_bf16_call* call, const int64_t* iter_dev, int64_t n_iters, float lr,
+                        const float* lr_dev, void* stream);
+int mx_lion_mix_bf16_scaled(const mx_lion_mix_bf16_call* call, const float* gscale_dev, int64_t iter, float lr,
+                            const float* lr_dev, void* stream);
+int mx_lion_mix_bf16_scaled_at(const mx_lion_mix_bf16_call* call, const float* gscale_dev, const int64_t* iter_dev,
+                               int64_t n_iters, float lr, const float* lr_dev, void* stream);
+int mx_lion_mix_bf16_grouped(const mx_lion_mix_bf16_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                             int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_lion_mix_bf16_grouped_at(const mx_lion_mix_bf16_call* call, const mx_param_runs* runs,
+                                const float* gscale_dev, const int64_t* iter_dev, int64_t n_iters, float lr,
+                                const float* lr_dev, void* stream);
+
 /* ---------------------------------------------------------------- flatten / unflatten
  * mx_gather replaces flatten_tensors (comm_helpers.py:12-30): flat[off[s] + i] = src[s][i].
  * mx_scatter is the copy_ loop of reset_model over unflatten_tensors views

@@ -6,6 +6,8 @@
     python tools/train_gpu.py --momentum 0.9 --fused-sgd --bf16                 # the same, bf16 models + fp32 masters
     python tools/train_gpu.py --lr 1e-3 --no-warmup --fused-adamw --wd 1e-2       # AdamW step fused into the round
     python tools/train_gpu.py --lr 1e-3 --no-warmup --fused-adamw --wd 1e-2 --bf16 # the same, bf16 models + fp32 masters
+    python tools/train_gpu.py --lr 1e-4 --no-warmup --fused-lion --wd 1e-2 --bf16 --lion-bf16-momentum
+                                                                                # Lion fused in, 18 bytes / parameter
     torchrun --nproc-per-node N --master-addr 127.0.0.1 tools/train_gpu.py     # one worker per GPU
 
 Flags follow train_mpi.py:205-231 (same names and defaults where they apply); --workers,
@@ -52,10 +54,14 @@ def main():
                     "workers' optimizer.step() / zero_grad() and the gossip round as ONE launch per iteration")
     ap.add_argument("--fused-adamw", action="store_true", help="as --fused-sgd with AdamW's update in the launch "
                     "(--beta1 --beta2 --eps --wd; --lr is AdamW's, e.g. 1e-3)")
+    ap.add_argument("--fused-lion", action="store_true", help="as --fused-sgd with the Lion update in the launch "
+                    "(--beta1 --beta2 --wd; --lr is Lion's, e.g. 1e-4)")
+    ap.add_argument("--lion-bf16-momentum", action="store_true", help="--fused-lion --bf16: keep the momentum in "
+                    "bfloat16 too (18 instead of 22 bytes per parameter and round)")
     ap.add_argument("--beta1", default=0.9, type=float)
-    ap.add_argument("--beta2", default=0.999, type=float)
+    ap.add_argument("--beta2", default=None, type=float, help="default 0.999 (--fused-adamw) / 0.99 (--fused-lion)")
     ap.add_argument("--eps", default=1e-8, type=float)
-    ap.add_argument("--wd", default=5e-4, type=float, help="--fused-adamw: the decoupled weight decay")
+    ap.add_argument("--wd", default=5e-4, type=float, help="--fused-adamw / --fused-lion: the decoupled weight decay")
     ap.add_argument("--bf16", action="store_true", help="one GPU: the models are cast to bfloat16 (bfloat16 gossip "
                     "rows); with --fused-sgd / --fused-adamw the step runs in mixed precision on fp32 master weights, which the "
                     "round mixes, and the bfloat16 models are their rounded image")
@@ -68,10 +74,15 @@ def main():
                     "parameters with ndim <= 1 (biases, normalisation scales), as a parameter group of the fused "
                     "step; an error on the paths that keep torch's optimizers")
     a = ap.parse_args()
-    if a.no_decay_1d and not (a.fused_sgd or a.fused_adamw):
-        ap.error("--no-decay-1d is honoured by the fused optimizer steps only: add --fused-sgd or --fused-adamw")
-    if a.clip_grad_norm is not None and not (a.fused_sgd or a.fused_adamw):
-        ap.error("--clip-grad-norm is honoured by the fused optimizer steps only: add --fused-sgd or --fused-adamw "
+    fused = a.fused_sgd or a.fused_adamw or a.fused_lion
+    if a.no_decay_1d and not fused:
+        ap.error("--no-decay-1d is honoured by the fused optimizer steps only: add --fused-sgd, --fused-adamw or "
+                 "--fused-lion")
+    if a.lion_bf16_momentum and not (a.fused_lion and a.bf16):
+        ap.error("--lion-bf16-momentum is the mixed-precision Lion step's: add --fused-lion --bf16")
+    if a.clip_grad_norm is not None and not fused:
+        ap.error("--clip-grad-norm is honoured by the fused optimizer steps only: add --fused-sgd, --fused-adamw or "
+                 "--fused-lion "
                  "(the other paths step torch's optimizers and do not clip)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -101,7 +112,11 @@ def main():
     else:
         tr = H.VirtualTrainer(args, model_fn, a.batches, batched=a.batched or a.graph, graph=a.graph,
                               fused_sgd=a.fused_sgd, fused_adamw=a.fused_adamw,
-                              adamw_hyper={"betas": (a.beta1, a.beta2), "eps": a.eps, "weight_decay": a.wd},
+                              adamw_hyper={"betas": (a.beta1, 0.999 if a.beta2 is None else a.beta2), "eps": a.eps,
+                                           "weight_decay": a.wd},
+                              fused_lion=a.fused_lion,
+                              lion_hyper={"betas": (a.beta1, 0.99 if a.beta2 is None else a.beta2), "weight_decay": a.wd,
+                                          "momentum_dtype": torch.bfloat16 if a.lion_bf16_momentum else torch.float32},
                               clip_grad_norm=a.clip_grad_norm,
                               param_groups=[{"params": lambda name, p: p.ndim <= 1, "weight_decay": 0.0}]
                               if a.no_decay_1d else None)
