@@ -44,6 +44,11 @@ SIGNATURES = {
     "mx_grad_norm_set": (c_int, [ctypes.c_char_p, c_int]),
     "mx_grad_norm_get": (c_int, [ctypes.c_char_p]),
     "mx_grad_norm": (c_int, [c_p, c_p]),
+    "mx_consensus_cols": (c_int, []),
+    "mx_consensus_layout": (c_i64, [c_p, c_int, c_int, c_p]),
+    "mx_consensus_set": (c_int, [ctypes.c_char_p, c_int]),
+    "mx_consensus_get": (c_int, [ctypes.c_char_p]),
+    "mx_consensus": (c_int, [c_p, c_p]),
     "mx_param_runs_check": (c_int, [c_p, c_int, c_p, c_p, c_p, c_p]),
     "mx_gather": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p]),
     "mx_scatter": (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p]),

@@ -20,8 +20,8 @@ import numpy as np
 import torch
 
 from ._lib import MXError, check, lib, require_device, stream_ptr
-from .engine import (PULL_HEADER, GossipEngine, PullTransport, ROW_ALIGN, default_comm, owner_table, partition,
-                     wait_round)
+from .engine import (PULL_HEADER, Consensus, GossipEngine, PullTransport, ROW_ALIGN, default_comm, owner_table,
+                     partition, wait_round)
 
 
 def topk_count(P, ratio):
@@ -95,6 +95,9 @@ class ChocoWorkerGroup:
         self.gamma32 = float(np.float32(consensus_lr))
         self.iter_dev = torch.zeros(1, dtype=torch.int64, device="cuda")   # device_round's counter
         self._pull = None
+        self._consensus = None               # consensus_distance(): built on first use
+        self.consensus_dists = self.consensus_stats = None
+        self._one_gpu = nranks == 1 and comm is None
         if isinstance(comm, PullTransport):
             # each rank's snapshot buffer holds two generations of its rows' messages; the gate
             # points the remote entries of the slot table at the round's partners' snapshots
@@ -113,6 +116,19 @@ class ChocoWorkerGroup:
     @property
     def rows(self):
         return self.x[:, :self.numel]
+
+    def consensus_distance(self, stream=None):
+        """VirtualWorkerGroup.consensus_distance over the `x` arena: every worker's distance from the mean
+        row in `consensus_dists` (returned; fp32 CUDA [n_local]) and (consensus distance, norm of the
+        mean) in `consensus_stats`, enqueued without a host synchronisation.  nranks = 1 only."""
+        if not self._one_gpu:
+            raise NotImplementedError("consensus_distance: the mean needs every worker's rows on this GPU "
+                                      "(nranks = 1, no transport); a cross-GPU consensus distance is not built")
+        if self._consensus is None:
+            self._consensus = Consensus([self.numel], [[self.x[r].data_ptr() for r in range(self.n_local)]], 4)
+            self.consensus_dists, self.consensus_stats = self._consensus.dists, self._consensus.stats
+        self._consensus.enqueue(stream_ptr(stream))
+        return self.consensus_dists
 
     @property
     def publish_cols(self):

@@ -77,6 +77,19 @@ def set_grad_norm_tuning(**knobs):
         check(lib.mx_grad_norm_set(k.encode(), int(v)), "mx_grad_norm_set")
 
 
+CONSENSUS_TUNE_KEYS = ("blocks_per_cu", "grid")
+
+
+def consensus_tuning():
+    """Current knobs of the consensus-distance kernel (mx_consensus_set)."""
+    return {k: int(lib.mx_consensus_get(k.encode())) for k in CONSENSUS_TUNE_KEYS}
+
+
+def set_consensus_tuning(**knobs):
+    for k, v in knobs.items():
+        check(lib.mx_consensus_set(k.encode(), int(v)), "mx_consensus_set")
+
+
 def clip_value(clip_grad_norm, who):
     """The clip_grad_norm keyword of attach_sgd / attach_adamw: None (off) or a positive finite float."""
     if clip_grad_norm is None:
@@ -1018,6 +1031,46 @@ class GradNorm:
             check(rc, "mx_grad_norm")
 
 
+class ConsensusCall(ctypes.Structure):
+    """mx_consensus_call (include/matcha_gossip.h): the consensus-distance launches' arguments, packed once."""
+    _fields_ = [("x_ptrs_dev", ctypes.c_void_p), ("seg_len_dev", ctypes.c_void_p), ("work_dev", ctypes.c_void_p),
+                ("dist_dev", ctypes.c_void_p), ("stats_dev", ctypes.c_void_p), ("chunks", ctypes.c_int64),
+                ("nseg", ctypes.c_int32), ("n_local", ctypes.c_int32), ("elem_size", ctypes.c_int32),
+                ("pad_", ctypes.c_int32)]
+
+
+class Consensus:
+    """Every worker's distance from the mean of the rows, the consensus distance and the norm of the mean on
+    the device (csrc/consensus.hip): `dists` (fp32 CUDA [n]), `stats` (fp32 CUDA [2]: the consensus
+    distance, the norm of the mean) and the fp64 workspace, over the rows at `row_ptrs` ([nseg][n] device
+    addresses, segment s of seg_lens[s] elements).  elem_size 4 = fp32 rows, 2 = bfloat16.  `dists` /
+    `stats`: output tensors to write instead of new ones (a group's sources share one pair)."""
+
+    def __init__(self, seg_lens, row_ptrs, elem_size, dists=None, stats=None):
+        seg_len = np.asarray(seg_lens, dtype=np.int64)
+        ptrs = np.ascontiguousarray(row_ptrs, dtype=np.int64).reshape(len(seg_len), -1)
+        n = ptrs.shape[1]
+        chunks = ctypes.c_int64(0)
+        nbytes = int(lib.mx_consensus_layout(seg_len.ctypes.data, len(seg_len), n, ctypes.byref(chunks)))
+        if nbytes < 0:
+            check(nbytes, "mx_consensus_layout")
+        self.x_ptrs = torch.from_numpy(ptrs).cuda()
+        self.seg_len = torch.from_numpy(seg_len).cuda()
+        self.work = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device="cuda")
+        self.dists = torch.zeros(n, dtype=torch.float32, device="cuda") if dists is None else dists
+        self.stats = torch.zeros(2, dtype=torch.float32, device="cuda") if stats is None else stats
+        self.call = ConsensusCall(self.x_ptrs.data_ptr(), self.seg_len.data_ptr(), self.work.data_ptr(),
+                                  self.dists.data_ptr(), self.stats.data_ptr(), chunks.value, len(seg_len), n,
+                                  int(elem_size), 0)
+        self._addr = ctypes.addressof(self.call)
+
+    def enqueue(self, s):
+        """The two launches on raw stream `s`: no host synchronisation, graph-capturable."""
+        rc = lib.mx_consensus(self._addr, s)
+        if rc:
+            check(rc, "mx_consensus")
+
+
 IDLE_MODES = {"skip": 0, "canonical": 1}
 
 
@@ -1314,6 +1367,9 @@ class VirtualWorkerGroup:
         self.clip_grad_norm = None
         self.grad_norms = self.grad_scales = None
         self._round_ctrs = {}                # device_rounds(K): per-round counters, one tensor per K
+        self._consensus = {}                 # consensus_distance(): source -> (arena address, Consensus)
+        self.consensus_dists = self.consensus_stats = None
+        self._one_gpu = nranks == 1 and comm is None
         if models is not None:
             if len(models) != self.n_local:
                 raise ValueError(f"{len(models)} models for {self.n_local} local workers")
@@ -1537,6 +1593,36 @@ class VirtualWorkerGroup:
             raise MXError("grad_norm: no clipping state: attach_sgd / attach_adamw with clip_grad_norm=...")
         self._clip.enqueue(stream_ptr(stream))
         return self.grad_norms
+
+    def consensus_distance(self, stream=None, of=None):
+        """Enqueue the consensus-distance launches (csrc/consensus.hip: one read of the rows, no host
+        synchronisation, graph-capturable) and return `consensus_dists`: every worker's distance from the
+        mean of the rows, fp32 CUDA [n_local], valid once the stream reaches it.  `consensus_stats`
+        (fp32 CUDA [2]) then holds the consensus distance sqrt(mean_r dist[r]^2) and the norm of the mean
+        row.  of=None measures the fp32 masters where master weights are attached and the group's rows
+        (fp32 or bfloat16) otherwise; of="rows" the model rows; of="masters" the masters (MXError
+        without them).  The state is built on first use, per source; every source writes the same two
+        output tensors.  One GPU only: the mean needs every worker's rows on this GPU."""
+        if not self._one_gpu:
+            raise NotImplementedError("consensus_distance: the mean needs every worker's rows on this GPU "
+                                      "(nranks = 1, no transport); a cross-GPU consensus distance is not built")
+        if of not in (None, "rows", "masters"):
+            raise ValueError(f"consensus_distance: of is None, 'rows' or 'masters', not {of!r}")
+        if of == "masters" and self.master_arena is None:
+            raise MXError("consensus_distance: no master weights: attach_sgd / attach_adamw / attach_lion with "
+                          "master_weights=True")
+        masters = of == "masters" or (of is None and self.master_arena is not None)
+        arena = self.master_arena if masters else self.arena
+        if self.consensus_dists is None:
+            self.consensus_dists = torch.zeros(self.n_local, dtype=torch.float32, device="cuda")
+            self.consensus_stats = torch.zeros(2, dtype=torch.float32, device="cuda")
+        held = self._consensus.get(masters)
+        if held is None or held[0] != arena.data_ptr():
+            state = Consensus([self.numel], [[arena[r].data_ptr() for r in range(self.n_local)]],
+                              arena.element_size(), dists=self.consensus_dists, stats=self.consensus_stats)
+            held = self._consensus[masters] = (arena.data_ptr(), state)
+        held[1].enqueue(stream_ptr(stream))
+        return self.consensus_dists
 
     def _fused_family(self, opt, master_weights, clip_grad_norm):
         """What attach_sgd / attach_adamw refuse alike, before anything is allocated; returns the layout

@@ -198,7 +198,7 @@ class VirtualTrainer:
 
     def __init__(self, args, model_fn, n_batches, device="cuda", batched=False, graph=False, fused_sgd=False,
                  fused_adamw=False, adamw_hyper=None, clip_grad_norm=None, param_groups=None, fused_lion=False,
-                 lion_hyper=None):
+                 lion_hyper=None, consensus_every=None):
         """fused_sgd=True (non-batched, uncompressed): the workers' optimizer.step() /
         zero_grad() and the gossip round run as ONE launch (VirtualWorkerGroup.attach_sgd /
         sgd_communicate, csrc/sgd_mix.hip): backward() accumulates into the group's gradient arena,
@@ -231,6 +231,14 @@ class VirtualTrainer:
         per-group weight decay and learning-rate scale inside the fused step (e.g. no decay for biases
         and normalisation scales: [{"params": lambda name, p: p.ndim <= 1, "weight_decay": 0.0}]).
         A ValueError on the other paths, whose torch optimizers are built with one group.
+
+        consensus_every=K (default None: nothing is measured): after the round of every K-th iteration,
+        counted over the whole run, the group's consensus_distance() is enqueued (csrc/consensus.hip: one
+        read of the rows) and its figures are copied into a preallocated device log, in every mode -- between
+        replays in graph mode.  The log is read once per epoch, so no round gains a host synchronisation.
+        `consensus_log` collects a float32 CPU tensor [size + 2] per measurement (every worker's distance
+        from the mean row, the consensus distance, the norm of the mean) and the epoch stats carry
+        "consensus" (the last consensus distance) and "consensus_dist" (that worker's own distance).
 
         graph=True (with batched=True, decentralized gossip, one GPU): once the learning rate
         is constant within an epoch, the whole training iteration -- vmap'd forward / backward,
@@ -268,6 +276,11 @@ class VirtualTrainer:
             raise ValueError("param_groups is honoured by the fused optimizer steps only (fused_sgd=True, "
                              "fused_adamw=True or fused_lion=True): the other paths step torch's optimizers with one group")
         self.grad_norm_log = []
+        if consensus_every is not None and (int(consensus_every) != consensus_every or consensus_every < 1):
+            raise ValueError(f"consensus_every must be None or a positive integer, not {consensus_every!r}")
+        self.consensus_every = None if consensus_every is None else int(consensus_every)
+        self.consensus_log = []
+        self._rounds_done = 0                                    # iterations over the whole run
         self.GP = make_topology(args, 0, size, args.epoch * n_batches)
         self.models = []
         for r in range(size):
@@ -310,6 +323,10 @@ class VirtualTrainer:
         if self.group.rows.dtype == torch.bfloat16:              # inputs in the models' element type
             self.data = [[(x.to(torch.bfloat16), y) for x, y in batches] for batches in self.data]
         self.n_batches = n_batches
+        if self.consensus_every is not None:                     # an epoch's measurements, read at its end
+            self._cons_dev = torch.zeros((n_batches // self.consensus_every + 1, size + 2), dtype=torch.float32,
+                                         device=device)
+            self._cons_n = 0
         self.recorders = [Recorder(args, r) for r in range(size)] if args.save else None
         self.epoch = 0
         self.batched = bool(batched)
@@ -423,6 +440,18 @@ class VirtualTrainer:
         self.group.iter += 1
         return loss, acc
 
+    def _consensus_tick(self):
+        """after an iteration's round: every consensus_every-th one enqueues the measurement and two small
+        device copies into the epoch's log (no host synchronisation)"""
+        self._rounds_done += 1
+        if self.consensus_every is None or self._rounds_done % self.consensus_every:
+            return
+        dists = self.group.consensus_distance()
+        row = self._cons_dev[self._cons_n]
+        row[:-2].copy_(dists)
+        row[-2:].copy_(self.group.consensus_stats)
+        self._cons_n += 1
+
     def train_epoch(self, on_round=None):
         """One epoch of train_mpi.py:109-168 for every worker; returns per-worker stats."""
         args = self.args
@@ -444,6 +473,7 @@ class VirtualTrainer:
             for b in range(self.n_batches):
                 lr = update_learning_rate(self.optimizers[0], epoch, args, itr=b, itr_per_epoch=self.n_batches)
                 loss_b, acc_b = self._graph_iteration(b, lr)
+                self._consensus_tick()
                 stat[b, 0].copy_(loss_b)
                 stat[b, 1].copy_(acc_b)
             st = stat.cpu().numpy()                            # one host sync per epoch
@@ -495,8 +525,12 @@ class VirtualTrainer:
             self._dev_iter_synced = False
             if self.clip_grad_norm is not None:              # the round is complete (wait_round): a plain read
                 self.grad_norm_log.append(self.group.grad_norms.cpu())
+            self._consensus_tick()
             if on_round is not None:
                 on_round("after", self)
+        if self.consensus_every is not None and self._cons_n:    # the epoch's one read of the log
+            self.consensus_log.extend(self._cons_dev[:self._cons_n].cpu().unbind(0))
+            self._cons_n = 0
         record_time = time.time() - tic
         stats = []
         for r in range(size):
@@ -505,6 +539,9 @@ class VirtualTrainer:
                           "comp_time": comp[r], "comm_time": comm_time})
             if self.clip_grad_norm is not None and self.grad_norm_log:
                 stats[-1]["grad_norm"] = float(self.grad_norm_log[-1][r])
+            if self.consensus_log:
+                stats[-1]["consensus"] = float(self.consensus_log[-1][-2])
+                stats[-1]["consensus_dist"] = float(self.consensus_log[-1][r])
             if self.recorders is not None:
                 self.recorders[r].add_new(record_time, comp[r], comm_time, comp[r] + comm_time, top1[r].avg,
                                           losses[r].avg, test_acc)

@@ -587,6 +587,59 @@ int mx_adamw_mix_bf16_scaled_at(const mx_adamw_mix_bf16_call* call, const float*
                                 const int64_t* iter_dev, int64_t n_iters, const int64_t* step_dev, float lr,
                                 const float* lr_dev, void* stream);
 
+/* ---------------------------------------------------------------- consensus distance
+ * How far apart the workers are (csrc/consensus.hip): every worker's distance from the mean of the n =
+ * n_local rows, the consensus distance and the norm of the mean row, from ONE read of the rows, on the
+ * device.  Per column c, rows fp32 or bfloat16 bit patterns (widened exactly, bits << 16):
+ *   s_c      = ((f64(x_0c) + f64(x_1c)) + f64(x_2c)) + ...     fp64 adds in ROW ORDER
+ *   m_c      = s_c / f64(n)                                    one IEEE fp64 division (a multiplication by
+ *                                                              1/n only where n is a power of two: same bits)
+ *   d_rc     = f64(x_rc) - m_c                                 one fp64 subtraction
+ *   D_r      = sum_c d_rc^2       M = sum_c m_c^2              fp64 over every segment, in a fixed order
+ *   dist[r]  = f32(sqrt(D_r))                                  worker r's ||x_r - mean||
+ *   stats[0] = f32(sqrt((D_0 + D_1 + ... in row order) / n))   the consensus distance
+ *   stats[1] = f32(sqrt(M))                                    ||mean||, for the relative figure
+ * The column arithmetic is pinned because x - m cancels: near consensus another order of the mean changes
+ * d by far more than an fp64 rounding.  With it pinned every d_rc is the same in every conforming
+ * implementation and the sums of the non-negative squares are within P * 2^-53 of exact in any order, so
+ * every output is within 1 fp32 ulp of the specification for P <= 2^26 columns.  Identical rows give
+ * exactly 0.0 for every n <= 64 (n = 1 included).  A NaN or Inf anywhere in a column makes its mean
+ * non-finite, and with it EVERY dist and both stats.  fp32 denormals count; +-3.4e38 does not overflow.
+ * Unlike mx_grad_norm's rows, a row's distance depends on every row (the mean does).  The bits are the
+ * same on every launch and under every knob; no floating-point atomics.
+ * mx_consensus_call, built once and kept alive by the caller (sizeof == 64):
+ *   x_ptrs_dev   [nseg][n_local] device table of row pointers and seg_len_dev int64 [nseg] elements per
+ *                segment, read only.  Nothing at or past seg_len of a row is read.
+ *   elem_size    4 (fp32) or 2 (bfloat16 bit patterns)
+ *   work_dev     fp64 workspace of mx_consensus_layout(seg_len_host, nseg, n_local, &chunks) BYTES (the
+ *                return value, 8 * (n_local + 1) * chunks; negative on bad arguments); `chunks` is what
+ *                that call stored: one slot per row, and one for the mean, per mx_consensus_cols() = 4096
+ *                columns of a segment.  Every slot is rewritten by every call: no zeroing.
+ *   dist_dev     float [n_local];  stats_dev  float [2], on the device
+ * mx_consensus(call, stream) enqueues two launches -- per-work-item partials of all rows into their own
+ * workspace slots, then one workgroup adding them in a fixed order -- with no host synchronisation and no
+ * host read, so it can be captured in a graph.  Vector loads (16 bytes a lane up to 16 rows, 8 up to 32, 4
+ * up to 64; non-temporal) where a row pointer is 16-byte aligned and the elements are in range, per-element
+ * loads elsewhere.
+ * MX_ERR_INVALID, nothing launched: a null call record, table, output or workspace; elem_size other than
+ * 2 or 4; n_local outside [1, 64]; nseg < 1 or chunks < 0; in mx_consensus_layout a negative length.
+ * mx_consensus_set / _get: "blocks_per_cu" (persistent workgroups per CU of the partial pass, default 8),
+ * "grid" (> 0: exact grid size), as mx_grad_norm_set: which workgroup computes a work item, never how. */
+typedef struct mx_consensus_call {
+    const void* const* x_ptrs_dev;
+    const int64_t* seg_len_dev;
+    double* work_dev;
+    float* dist_dev;
+    float* stats_dev;
+    int64_t chunks;
+    int32_t nseg, n_local, elem_size, pad_;
+} mx_consensus_call;
+int mx_consensus_cols(void);
+int64_t mx_consensus_layout(const int64_t* seg_len_host, int nseg, int n_local, int64_t* chunks_out);
+int mx_consensus_set(const char* key, int value);
+int mx_consensus_get(const char* key);
+int mx_consensus(const mx_consensus_call* call, void* stream);
+
 /* ---------------------------------------------------------------- per-parameter-group hyperparameters
  * torch.optim's param_groups with their own weight_decay and their own learning-rate multiplier, for the
  * four fused launches above.  The columns [0, seg_len) of every segment are cut into RUNS, half-open

@@ -73,8 +73,13 @@ def main():
     ap.add_argument("--no-decay-1d", action="store_true", help="--fused-sgd / --fused-adamw: weight decay 0 for "
                     "parameters with ndim <= 1 (biases, normalisation scales), as a parameter group of the fused "
                     "step; an error on the paths that keep torch's optimizers")
+    ap.add_argument("--consensus-every", default=None, type=int, metavar="K", help="one GPU: measure how far apart "
+                    "the workers are after every K-th iteration's round (one read of the rows, no host wait per "
+                    "round) and print the consensus distance and its ratio to the norm of the mean per epoch")
     a = ap.parse_args()
     fused = a.fused_sgd or a.fused_adamw or a.fused_lion
+    if a.consensus_every is not None and a.consensus_every < 1:
+        ap.error("--consensus-every: a positive number of iterations")
     if a.no_decay_1d and not fused:
         ap.error("--no-decay-1d is honoured by the fused optimizer steps only: add --fused-sgd, --fused-adamw or "
                  "--fused-lion")
@@ -91,6 +96,8 @@ def main():
                  "does not clip")
     if a.no_decay_1d and world > 1:
         ap.error("--no-decay-1d: one process per GPU trains with torch's optimizers (no fused step yet)")
+    if a.consensus_every is not None and world > 1:
+        ap.error("--consensus-every: the mean needs every worker's rows on one GPU (one process)")
     args = H.HarnessArgs(name=a.name, description=a.description, model=a.model, lr=a.lr, momentum=a.momentum,
                          epoch=a.epoch, bs=a.bs, warmup=a.warmup, nesterov=a.nesterov, matcha=a.matcha,
                          budget=a.budget, graphid=a.graphid, savePath=a.savePath, save=a.save,
@@ -119,7 +126,7 @@ def main():
                                           "momentum_dtype": torch.bfloat16 if a.lion_bf16_momentum else torch.float32},
                               clip_grad_norm=a.clip_grad_norm,
                               param_groups=[{"params": lambda name, p: p.ndim <= 1, "weight_decay": 0.0}]
-                              if a.no_decay_1d else None)
+                              if a.no_decay_1d else None, consensus_every=a.consensus_every)
         if a.resume:
             tr.load(a.resume)
     import time
@@ -131,8 +138,12 @@ def main():
         if rank == 0:
             norms = "" if "grad_norm" not in stats[0] else \
                 ", grad_norm: " + " ".join(f"{s['grad_norm']:.3g}" for s in stats)
+            cons = ""
+            if "consensus" in stats[0]:
+                xi, mean_norm = (float(v) for v in tr.consensus_log[-1][-2:])
+                cons = f", consensus: {xi:.4g} (relative {xi / mean_norm if mean_norm else float('nan'):.3g})"
             print(H.epoch_summary(stats, tr.epoch - 1) + f", wall: {time.time() - t:.3f} s "
-                  f"({a.batches / (time.time() - t):.1f} iterations/s)" + norms, flush=True)
+                  f"({a.batches / (time.time() - t):.1f} iterations/s)" + norms + cons, flush=True)
     tr.finish()
     if a.checkpoint and world == 1:
         tr.save(a.checkpoint)
