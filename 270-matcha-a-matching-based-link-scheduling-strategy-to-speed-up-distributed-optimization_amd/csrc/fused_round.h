@@ -16,8 +16,14 @@
 //     keep<SP>(...)         stores the state the lane owns and, with zero_grads, the zeros over g
 //     finish<SP>(...)       stores a mixed chunk (and, bf16 families, its rounded image)
 // (SP: the store policy, mx::StorePolicy -- its 16-byte stores; the 8-byte bf16 stores are plain or nt)
+// One optional hook, for an optimizer whose state follows the MIXED row (quasi-global momentum, qgm_mix.hip):
+//     kAfterMix = true      a static constexpr flag of the policy; the kernel then calls
+//     after_mix<G, SP>(tb, geo, r, c, vec, acc, st, h)   in place of finish: the mixed chunk together with the
+//                           launch state and the (grouped) argument block; the work item's own Geo resolves
+//                           the run, as sgd_chunk does
 // Everything a policy decides is decided at compile time; the kernel has no run-time branch on the family.
-// A new optimizer is a new policy type plus its entry points: nothing in this file changes.
+// A new optimizer whose state is settled before the round is a new policy type plus its entry points:
+// nothing in this file changes.  Policies without the flag compile to exactly what they did without the hook.
 //
 // In place: a tile's x' of every row is parked in LDS (barrier) before any x row of it is stored, and
 // different work items never share a column.  State arrays are read and written by the same lane only, so
@@ -181,6 +187,12 @@ using GroupedIf = std::conditional_t<GROUPED, Grouped<Hyper>, Hyper>;
 template <class Update, bool GROUPED>
 using HyperOf = GroupedIf<typename Update::Hyper, GROUPED>;
 
+// the optional hook: a policy that declares `static constexpr bool kAfterMix = true` gets after_mix, not finish
+template <class Update, class = void>
+struct AfterMix : std::false_type {};
+template <class Update>
+struct AfterMix<Update, std::void_t<decltype(Update::kAfterMix)>> : std::bool_constant<Update::kAfterMix> {};
+
 // where a work item lies
 struct Geo {
     int64_t base, col0, lim;             // base: the segment's row of the pointer tables
@@ -306,7 +318,11 @@ __global__ __launch_bounds__(kTPB) void fused_round_rows(T __restrict__... tabs,
             const F4 self = lds[r * C4 + col];
             if (mixes(r)) fma4(acc, pv.sw[r], self);                    // the self term, last
             else acc = self;                                         // x' as it is
-            Update::template finish<SP>(tb, g, r, g.col0 + (int64_t)col * 4, Update::vec_of(tb, g, r), acc);
+            if constexpr (AfterMix<Update>::value)
+                Update::template after_mix<GROUPED, SP>(tb, g, r, g.col0 + (int64_t)col * 4, Update::vec_of(tb, g, r),
+                                                        acc, st, h);
+            else
+                Update::template finish<SP>(tb, g, r, g.col0 + (int64_t)col * 4, Update::vec_of(tb, g, r), acc);
         };
         rows::walk<rows::Fp32, NQ, C4>(lds, wl[wave], nmy, lane, pv.src, M, alpha, degree, finish);
     };

@@ -733,7 +733,29 @@ class LionBf16Call(ctypes.Structure):
                 ("omb2", ctypes.c_float), ("zero_grads", ctypes.c_int32), ("m_bf16", ctypes.c_int32)]
 
 
+class QgmMixCall(ctypes.Structure):
+    """mx_qgm_mix_call (include/matcha_gossip.h): the fused quasi-global-momentum launch's arguments, packed once."""
+    _fields_ = [("x_ptrs_dev", ctypes.c_void_p), ("g_ptrs_dev", ctypes.c_void_p), ("m_ptrs_dev", ctypes.c_void_p),
+                ("seg_len_dev", ctypes.c_void_p), ("tile_off_dev", ctypes.c_void_p), ("plan_dev", ctypes.c_void_p),
+                ("total_tiles", ctypes.c_int64), ("nseg", ctypes.c_int32), ("n_slots", ctypes.c_int32),
+                ("n_local", ctypes.c_int32), ("M", ctypes.c_int32), ("alpha", ctypes.c_float),
+                ("wd", ctypes.c_float), ("beta", ctypes.c_float), ("omu", ctypes.c_float),
+                ("nesterov", ctypes.c_int32), ("zero_grads", ctypes.c_int32)]
+
+
+class QgmBf16Call(ctypes.Structure):
+    """mx_qgm_mix_bf16_call (include/matcha_gossip.h): the mixed-precision fused QG-momentum launch's arguments."""
+    _fields_ = [("w_ptrs_dev", ctypes.c_void_p), ("g_ptrs_dev", ctypes.c_void_p), ("m_ptrs_dev", ctypes.c_void_p),
+                ("p_ptrs_dev", ctypes.c_void_p), ("seg_len_dev", ctypes.c_void_p), ("tile_off_dev", ctypes.c_void_p),
+                ("plan_dev", ctypes.c_void_p), ("total_tiles", ctypes.c_int64), ("nseg", ctypes.c_int32),
+                ("n_slots", ctypes.c_int32), ("n_local", ctypes.c_int32), ("M", ctypes.c_int32),
+                ("alpha", ctypes.c_float), ("wd", ctypes.c_float), ("beta", ctypes.c_float),
+                ("omu", ctypes.c_float), ("nesterov", ctypes.c_int32), ("zero_grads", ctypes.c_int32)]
+
+
 SGD_TUNE_KEYS = ("nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid")
+# the QG-momentum families' own knob on top: x and mh staged with plain loads (include/matcha_gossip.h)
+QGM_TUNE_KEYS = SGD_TUNE_KEYS + ("stage_plain",)
 
 # the ten entry points of a fused family, as suffixes of its C base name, in FusedFamily's field order
 _FUSED_ENTRIES = ("_tile", "_layout", "_set", "_get", "", "_at", "_scaled", "_scaled_at", "_grouped", "_grouped_at")
@@ -766,14 +788,17 @@ FAMILIES = {
     ("lion", False): _family("mx_lion_mix", LionMixCall, "x g m", None, False, "fused Lion + mixing"),
     ("lion", True): _family("mx_lion_mix_bf16", LionBf16Call, "w g m p", None, False,
                             "mixed-precision fused Lion + mixing"),
+    ("qgm", False): _family("mx_qgm_mix", QgmMixCall, "x g m", None, False, "fused quasi-global momentum + mixing"),
+    ("qgm", True): _family("mx_qgm_mix_bf16", QgmBf16Call, "w g m p", None, False,
+                           "mixed-precision fused quasi-global momentum + mixing"),
 }
 
 
-def _tuning_pair(fam):
+def _tuning_pair(fam, keys=SGD_TUNE_KEYS):
     """(<family>_tuning, set_<family>_tuning) of a fused family.  None of the knobs changes the tile
     (include/matcha_gossip.h), so a set invalidates no layout."""
     def tuning():
-        return {k: int(fam.get(k.encode())) for k in SGD_TUNE_KEYS}
+        return {k: int(fam.get(k.encode())) for k in keys}
 
     def set_tuning(**knobs):
         for k, v in knobs.items():
@@ -792,6 +817,8 @@ adamw_mix_tuning, set_adamw_mix_tuning = _tuning_pair(FAMILIES["adamw", False])
 adamw_mix_bf16_tuning, set_adamw_mix_bf16_tuning = _tuning_pair(FAMILIES["adamw", True])
 lion_mix_tuning, set_lion_mix_tuning = _tuning_pair(FAMILIES["lion", False])
 lion_mix_bf16_tuning, set_lion_mix_bf16_tuning = _tuning_pair(FAMILIES["lion", True])
+qgm_mix_tuning, set_qgm_mix_tuning = _tuning_pair(FAMILIES["qgm", False], QGM_TUNE_KEYS)
+qgm_mix_bf16_tuning, set_qgm_mix_bf16_tuning = _tuning_pair(FAMILIES["qgm", True], QGM_TUNE_KEYS)
 
 
 def _f32(v):
@@ -836,6 +863,28 @@ def lion_arguments(betas, weight_decay, momentum_dtype, master_weights):
         raise ValueError("attach_lion: bfloat16 momentum is the mixed-precision round's (a bfloat16 group with "
                          "master_weights=True)")
     return betas, weight_decay, m_bf16
+
+
+def qgm_hyper(beta, mu, wd, nesterov, zero_grads):
+    """The QG-momentum records' words after alpha: wd, beta, omu, nesterov, zero_grads.  beta and mu are the
+    Python floats: omu is rounded from the fp64 value 1 - mu, as adam_hyper's omb1."""
+    return _f32(wd), _f32(beta), _f32(1.0 - float(mu)), int(bool(nesterov)), int(bool(zero_grads))
+
+
+def qgm_arguments(momentum, mu, weight_decay):
+    """attach_qgm's own argument checks, a pure host function: (momentum, mu, weight_decay) with mu = momentum
+    when None (the paper's setting).  ValueError for a momentum or mu outside [0, 1) and a negative weight
+    decay."""
+    momentum = float(momentum)
+    mu = momentum if mu is None else float(mu)
+    weight_decay = float(weight_decay)
+    if not 0.0 <= momentum < 1.0:
+        raise ValueError(f"attach_qgm: momentum {momentum} outside [0, 1)")
+    if not 0.0 <= mu < 1.0:
+        raise ValueError(f"attach_qgm: mu {mu} outside [0, 1)")
+    if not weight_decay >= 0.0:
+        raise ValueError("attach_qgm: weight_decay must not be negative")
+    return momentum, mu, weight_decay
 
 
 def pack_call(fam, tables, seg_len, tile_off, plan, bias, total_tiles, n_bias, nseg, n_slots, n_local, M, alpha32,
@@ -969,9 +1018,34 @@ class LionBf16Layout(FusedLayout):
         return self._pack(engine, lion_hyper(betas, wd, zero_grads, m_bf16))
 
 
+class QgmLayout(FusedLayout):
+    """csrc/qgm_mix.hip: row r's copy of segment s, its gradient and its quasi-global momentum buffer (the
+    `m` table), fp32, lengths in floats."""
+    family = FAMILIES["qgm", False]
+
+    def __init__(self, seg_lens, x_ptrs, g_ptrs, m_ptrs, n_local):
+        super().__init__(seg_lens, (x_ptrs, g_ptrs, m_ptrs), n_local)
+
+    def call(self, engine, beta, mu, wd, nesterov, zero_grads):
+        """beta and mu are the Python floats (qgm_hyper)"""
+        return self._pack(engine, qgm_hyper(beta, mu, wd, nesterov, zero_grads))
+
+
+class QgmBf16Layout(FusedLayout):
+    """csrc/qgm_mix_bf16.hip: row r's fp32 master of segment s, its bfloat16 gradient, its fp32 quasi-global
+    momentum buffer and its bfloat16 model row, lengths in elements."""
+    family = FAMILIES["qgm", True]
+
+    def __init__(self, seg_lens, w_ptrs, g_ptrs, m_ptrs, p_ptrs, n_local):
+        super().__init__(seg_lens, (w_ptrs, g_ptrs, m_ptrs, p_ptrs), n_local)
+
+    call = QgmLayout.call
+
+
 FUSED_LAYOUTS = {("sgd", False): SgdLayout, ("sgd", True): SgdBf16Layout,          # keyed as FAMILIES
                  ("adamw", False): AdamwLayout, ("adamw", True): AdamwBf16Layout,
-                 ("lion", False): LionLayout, ("lion", True): LionBf16Layout}
+                 ("lion", False): LionLayout, ("lion", True): LionBf16Layout,
+                 ("qgm", False): QgmLayout, ("qgm", True): QgmBf16Layout}
 
 # what attach_sgd / attach_adamw / attach_lion hold in _sgd / _adamw / _lion: the layout, the packed call record and its address,
 # then the family's own fields side by side, so that a step reads its launch functions in one lookup
@@ -984,12 +1058,16 @@ _OPTIMIZER_WORDS = {
     "adamw": ("AdamW", "sgd", "bfloat16 groups need fp32 master weights under AdamW"),
     "lion": ("Lion", "adamw", "bfloat16 groups need fp32 master weights under Lion"),
 }
+# every slot a group has (_sgd / _adamw / _lion / _qgm): the three above, then quasi-global momentum, which
+# comes last in every other optimizer's conflict check
+_FUSED_WORDS = {**_OPTIMIZER_WORDS,
+                "qgm": ("QGM", "sgd", "bfloat16 groups need fp32 master weights under quasi-global momentum")}
 
 
 def _attached(state, opt):
-    """The FusedState in a group's _sgd / _adamw / _lion slot, or the error of a group without one."""
+    """The FusedState in a group's _sgd / _adamw / _lion / _qgm slot, or the error of a group without one."""
     if state is None:
-        raise MXError(f"no {_OPTIMIZER_WORDS[opt][0]} state: call attach_{opt}() first")
+        raise MXError(f"no {_FUSED_WORDS[opt][0]} state: call attach_{opt}() first")
     return state
 
 
@@ -1360,6 +1438,7 @@ class VirtualWorkerGroup:
         self.master_arena = self.master_rows = None   # attach_sgd(master_weights=True): fp32 masters of bf16 rows
         self._adamw = None                   # attach_adamw: the fused AdamW + mixing launch's state
         self._lion = None                    # attach_lion: the fused Lion + mixing launch's state
+        self._qgm = None                     # attach_qgm: the fused quasi-global-momentum launch's state
         self._clip = None                    # attach_*(clip_grad_norm=...): the norm launch's state (GradNorm)
         self._runs = None                    # attach_*(param_groups=...): the run tables (ParamRuns)
         self.param_runs = None               # ... and the merged run list [(start, end, weight_decay, lr_scale)]
@@ -1628,13 +1707,13 @@ class VirtualWorkerGroup:
         """What attach_sgd / attach_adamw refuse alike, before anything is allocated; returns the layout
         class of (opt, mixed precision) and the checked clip norm."""
         who = "attach_" + opt
-        name, other, needs_master = _OPTIMIZER_WORDS[opt]
+        name, other, needs_master = _FUSED_WORDS[opt]
         clip = clip_value(clip_grad_norm, who)
         if getattr(self, "_" + opt) is not None:
             raise RuntimeError(f"{who}: already attached")
-        for o in [other] + [k for k in _OPTIMIZER_WORDS if k not in (opt, other)]:
+        for o in [other] + [k for k in _FUSED_WORDS if k not in (opt, other)]:
             if getattr(self, "_" + o) is not None:
-                raise RuntimeError(f"{who}: the group already carries {_OPTIMIZER_WORDS[o][0]} state (attach_{o})")
+                raise RuntimeError(f"{who}: the group already carries {_FUSED_WORDS[o][0]} state (attach_{o})")
         if master_weights and self.dtype != torch.bfloat16:
             raise ValueError(f"{who}: master_weights=True is for bfloat16 groups; fp32 rows are their own masters")
         if self.dtype != torch.float32 and not master_weights:
@@ -1960,11 +2039,62 @@ class VirtualWorkerGroup:
         iteration counter, as one launch; returns seconds like communicate()."""
         return self._fused_communicate(self.lion_step, lr)
 
+    # ------------------------------------------------------------------ fused quasi-global momentum + mixing
+    def attach_qgm(self, momentum=0.9, mu=None, weight_decay=0.0, nesterov=False, zero_grads=True,
+                   master_weights=False, clip_grad_norm=None, param_groups=None):
+        """Give the group quasi-global momentum (QG-DSGDm: Lin et al., ICML 2021): SGD with momentum whose
+        buffer is fed by the displacement of the worker's row AFTER the gossip round, (x_t - x_{t+1}) / lr,
+        not by its own gradient, so that it follows the direction the neighbourhood actually moved and
+        heterogeneous shards stop pulling the workers apart between rounds.  One launch per iteration
+        applies every worker's local step (momentum `momentum`, optionally Nesterov, L2 weight decay as
+        SGD's), the round's mix and the buffer update mh' = mu * mh + (1 - mu) * (x_t - x_{t+1}) / lr
+        (csrc/qgm_mix.hip); mu=None is mu = momentum, the paper's setting.  It moves the bytes of SGD with
+        momentum and needs no extra communication.
+
+        Allocates `grad_arena` / `grads` as attach_sgd does (adopted parameters' .grad become views of it;
+        see attach_sgd on zero_grad) and `qgm_buffer_arena` / `qgm_buffer_rows` (fp32 zeros).  A step at
+        lr = 0, and a parameter group of lr_scale 0, leave the buffer as it is.  One GPU only.
+
+        master_weights=True is the bfloat16 group's form (csrc/qgm_mix_bf16.hip; a ValueError on an fp32
+        group, and a bfloat16 group refuses to attach without it), as attach_sgd's: `master_arena` /
+        `master_rows` hold an fp32 master of every row, the gradient arena is bfloat16, the buffer stays
+        fp32, and the launch updates and mixes the MASTERS, takes the displacement from them and rewrites
+        `rows` as bf16(master).
+
+        clip_grad_norm and param_groups are attach_sgd's (the local momentum sees the clipped gradient; a
+        group's "lr_scale" scales the step and the 1 / lr of the buffer update alike, its "weight_decay"
+        the L2 term)."""
+        checked = self._fused_family("qgm", master_weights, clip_grad_norm)
+        momentum, mu, weight_decay = qgm_arguments(momentum, mu, weight_decay)
+        self.qgm_buffer_arena = self._state_arena()
+        self.qgm_buffer_rows = self.qgm_buffer_arena[:, :self.numel]
+        self.qgm_hyper = {"momentum": momentum, "mu": mu, "weight_decay": weight_decay, "nesterov": bool(nesterov),
+                          "zero_grads": bool(zero_grads)}
+        self._qgm = self._attach_fused(checked, param_groups, {"m": self.qgm_buffer_arena}, None, self.qgm_hyper,
+                                       (momentum, mu, weight_decay, nesterov, zero_grads))
+
+    def qgm_step(self, it, lr, stream=None):
+        """Enqueue ONE launch: every local worker's step at learning rate `lr`, round `it`'s mix of the
+        updated rows and the buffer update from the rows' displacement.  Always launches -- an all-zero
+        round is the local step plus the buffer update -- and returns whether the round mixed."""
+        return self._fused_step(_attached(self._qgm, "qgm"), it, lr, stream)
+
+    def qgm_device_round(self, stream=None):
+        """Graph-replayable qgm_step, as sgd_device_round: the round is read from `self.iter_dev` and the
+        learning rate from `self.lr_dev` when the kernel runs, then the counter is advanced.  A counter
+        outside the schedule makes the launch a no-op: no step, and the buffer is not written."""
+        self._fused_device_round(_attached(self._qgm, "qgm"), stream)
+
+    def qgm_communicate(self, lr):
+        """optimizer.step() + zero_grad() + communicate() of every worker at the group's own
+        iteration counter, as one launch; returns seconds like communicate()."""
+        return self._fused_communicate(self.qgm_step, lr)
+
     def state_dict(self):
         """Checkpoint: the workers' rows and the iteration counter (resume on the same schedule);
         with attach_sgd(momentum != 0) the momentum rows too, with master_weights=True the fp32
         master rows, with attach_adamw the exp_avg / exp_avg_sq rows and the step count, and with
-        attach_lion the lion_exp_avg rows (in the arena's dtype)."""
+        attach_lion the lion_exp_avg rows (in the arena's dtype), with attach_qgm the qgm_buffer rows."""
         state = {"kind": "decen", "iter": int(self.iter), "row_base": int(self.row_base),
                  "workers": list(self.workers), "rows": self.rows.detach().clone()}
         if self._sgd is not None and self.momentum_rows is not None:
@@ -1977,6 +2107,8 @@ class VirtualWorkerGroup:
             state["opt_step"] = int(self.opt_step)
         if self._lion is not None:
             state["lion_exp_avg_rows"] = self.lion_exp_avg_rows.detach().clone()
+        if self._qgm is not None:
+            state["qgm_buffer_rows"] = self.qgm_buffer_rows.detach().clone()
         return state
 
     def load_state_dict(self, state):
@@ -2001,8 +2133,14 @@ class VirtualWorkerGroup:
                                  or lion.dtype != self.lion_exp_avg_rows.dtype):
             raise ValueError("checkpoint carries Lion state (lion_exp_avg rows): attach_lion() with the same "
                              "momentum_dtype before loading it")
+        qgm = state.get("qgm_buffer_rows")
+        if qgm is not None and (self._qgm is None or tuple(qgm.shape) != tuple(self.qgm_buffer_rows.shape)):
+            raise ValueError("checkpoint carries quasi-global momentum state (qgm_buffer rows): attach_qgm() on a "
+                             "group of the same shape before loading it")
         with torch.no_grad():
             self.rows.copy_(state["rows"])
+            if self._qgm is not None:            # a checkpoint without them: the buffer starts as zeros
+                self.qgm_buffer_rows.zero_() if qgm is None else self.qgm_buffer_rows.copy_(qgm)
             if self._lion is not None:           # a checkpoint without them: the buffer starts as zeros
                 self.lion_exp_avg_rows.zero_() if lion is None else self.lion_exp_avg_rows.copy_(lion)
             if self._adamw is not None:          # a checkpoint without them: zero buffers, step 0

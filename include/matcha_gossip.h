@@ -806,6 +806,119 @@ int mx_lion_mix_bf16_grouped_at(const mx_lion_mix_bf16_call* call, const mx_para
                                 const float* gscale_dev, const int64_t* iter_dev, int64_t n_iters, float lr,
                                 const float* lr_dev, void* stream);
 
+/* ---------------------------------------------------------------- the hot path, quasi-global momentum fused in
+ * mx_sgd_mix with quasi-global momentum (QG-DSGDm: Lin et al., ICML 2021, "Quasi-Global Momentum:
+ * Accelerating Decentralized Deep Learning on Heterogeneous Data") in place of SGD's local momentum
+ * (csrc/qgm_mix.hip): fp32 rows, one GPU, every partner local, one launch per training iteration.  The
+ * momentum buffer mh is fed by the displacement of the worker's row AFTER the gossip round, (x_t - x_{t+1}) /
+ * lr, so it follows the direction the neighbourhood actually moved, at no extra communication.  Per row and
+ * column, every line one IEEE fp32 rounding (the library is built with -ffp-contract=off and every fma is
+ * explicit); g is widened and clip-scaled as in every fused family (g' = fmul(gscale[r], f32(g))); beta is
+ * the fp32 rounding of the Python float, omu the fp32 rounding of the fp64 value 1 - mu; (wd_r, scale_r) are
+ * the run's pair, the launch's wd and 1.0 when ungrouped:
+ *   lr_r = fmul(lr, scale_r)
+ *   d    = (wd_r != 0) ? fmaf(wd_r, x, g) : g
+ *   m    = fadd(fmul(beta, mh), d)                       mh: the quasi-global buffer, read only here
+ *   s    = nesterov ? fmaf(beta, m, d) : m
+ *   x'   = fmaf(-lr_r, s, x)
+ *   y    = mx_sgd_mix's round on the x' values           rows the record leaves alone, and every row of an
+ *                                                        all-zero round: y = x'
+ *   rl   = fdiv(1.0f, lr_r)                              once per launch, or per run when grouped
+ *   q    = fmul(fsub(x, y), rl)                          x: the value the row held BEFORE this launch
+ *   mh'  = (lr_r != 0) ? fmaf(omu, fsub(q, mh), mh) : mh
+ *   x    = y        (mixed precision: w = y, p = bf16_rne(y))
+ * mu = beta is the paper's setting.  An all-zero round is the local step plus the buffer update, NOT a
+ * no-op.  lr_r == 0 (lr = 0, or a run of scale 0) leaves mh BIT FOR BIT while x is still mixed.  q amplifies
+ * the rounding of x by 1 / lr; that is inherent to the algorithm in fp32.  The buffer starts as zeros.
+ * Traffic: 20 bytes per element (24 with zero_grads), SGD with momentum's.
+ * mx_qgm_mix_call is mx_sgd_mix_call with beta / omu in place of mom: the three tables (m_ptrs_dev, the
+ * buffer's, is never NULL), the tile (mx_qgm_mix_tile: 1024 / 1024 / 512 / 256 columns, 0 above 64 rows),
+ * the layout prefix, the alignment rule (16-byte accesses where x, g and mh of a (segment, row) are all
+ * 16-byte aligned and the 4 elements are in range, 4-byte accesses elsewhere, for the loads and stores
+ * before the round and for the reload and stores after it alike; nothing is read or written at or past
+ * seg_len of a row in any array), the host-side refusals (MX_ERR_INVALID, nothing launched: n_slots !=
+ * n_local, more than 64 rows, M outside [1, 32], a null table -- the buffer's included) and the launch-side
+ * no-ops (a peer-reads plan record; for _at a counter outside [0, n_iters): x, g and mh are not written) are
+ * mx_sgd_mix's.  _scaled and _grouped are the other families'; the record's own wd is ignored when grouped.
+ * mx_qgm_mix_set / _get: "nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid", "store_policy", as
+ * mx_sgd_mix_set's and independent of them, and "stage_plain" (0 / 1, default 1): 1 loads x and mh with
+ * plain loads before the round where the launch streams, so that their reload after the round finds more
+ * of the lines cached; 0 loads them with the streaming hint, as g.  Speed only, never bits; none of them changes the tile. */
+typedef struct mx_qgm_mix_call {
+    float* const* x_ptrs_dev;
+    float* const* g_ptrs_dev;
+    float* const* m_ptrs_dev;
+    const int64_t* seg_len_dev;
+    const int64_t* tile_off_dev;
+    const int32_t* plan_dev;
+    int64_t total_tiles;
+    int32_t nseg, n_slots, n_local, M;
+    float alpha, wd, beta, omu;
+    int32_t nesterov, zero_grads;
+} mx_qgm_mix_call;
+int mx_qgm_mix_tile(int n_slots);
+int mx_qgm_mix_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host);
+int mx_qgm_mix_set(const char* key, int value);
+int mx_qgm_mix_get(const char* key);
+int mx_qgm_mix(const mx_qgm_mix_call* call, int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_qgm_mix_at(const mx_qgm_mix_call* call, const int64_t* iter_dev, int64_t n_iters, float lr,
+                  const float* lr_dev, void* stream);
+int mx_qgm_mix_scaled(const mx_qgm_mix_call* call, const float* gscale_dev, int64_t iter, float lr,
+                      const float* lr_dev, void* stream);
+int mx_qgm_mix_scaled_at(const mx_qgm_mix_call* call, const float* gscale_dev, const int64_t* iter_dev,
+                         int64_t n_iters, float lr, const float* lr_dev, void* stream);
+int mx_qgm_mix_grouped(const mx_qgm_mix_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                       int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_qgm_mix_grouped_at(const mx_qgm_mix_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                          const int64_t* iter_dev, int64_t n_iters, float lr, const float* lr_dev, void* stream);
+
+/* ---------------------------------------------------------------- the hot path, mixed-precision QG momentum fused in
+ * mx_qgm_mix for models held in bfloat16 (csrc/qgm_mix_bf16.hip): the update runs on fp32 MASTER rows, the
+ * master rows are what the round mixes and what the buffer's displacement is taken from, and the bfloat16
+ * model row is the rounded image of its master, rewritten by every launch.  Per (segment, row) four arrays:
+ *   w  float*    fp32 master, read and written in place
+ *   g  uint16_t* bfloat16 gradient, read; overwritten with zeros when zero_grads != 0
+ *   m  float*    the fp32 quasi-global buffer mh, read, and written after the round
+ *   p  uint16_t* bfloat16 model row, WRITE ONLY: the kernel never reads it
+ * Arithmetic contract: mx_qgm_mix's lines on w with g32 = f32(g) (exact widening, bits << 16), then w = y
+ * and p = bf16_rne(y) of the value stored to w (ONE rounding, to nearest even; NaN stays NaN, payload
+ * unspecified).  p is written for every row in every launch that runs.  Traffic: 20 bytes per element (22
+ * with zero_grads), mixed-precision SGD with momentum's.  Alignment rule: a lane holds 4 elements; where w
+ * and mh of a (segment, row) are 16-byte aligned, g and p are 8-byte aligned and the 4 elements are in
+ * range, the accesses are wide; elsewhere they are per element (4 / 2 bytes), zero-filled past the end --
+ * before and after the round alike.  The other fields, the tile, the layout prefix, the host-side refusals
+ * (a null table -- the buffer's and p included) and the launch-side no-ops are mx_qgm_mix's; the knobs are
+ * its own, independent of every other family's. */
+typedef struct mx_qgm_mix_bf16_call {
+    float* const* w_ptrs_dev;
+    uint16_t* const* g_ptrs_dev;
+    float* const* m_ptrs_dev;
+    uint16_t* const* p_ptrs_dev;
+    const int64_t* seg_len_dev;
+    const int64_t* tile_off_dev;
+    const int32_t* plan_dev;
+    int64_t total_tiles;
+    int32_t nseg, n_slots, n_local, M;
+    float alpha, wd, beta, omu;
+    int32_t nesterov, zero_grads;
+} mx_qgm_mix_bf16_call;
+int mx_qgm_mix_bf16_tile(int n_slots);
+int mx_qgm_mix_bf16_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host);
+int mx_qgm_mix_bf16_set(const char* key, int value);
+int mx_qgm_mix_bf16_get(const char* key);
+int mx_qgm_mix_bf16(const mx_qgm_mix_bf16_call* call, int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_qgm_mix_bf16_at(const mx_qgm_mix_bf16_call* call, const int64_t* iter_dev, int64_t n_iters, float lr,
+                       const float* lr_dev, void* stream);
+int mx_qgm_mix_bf16_scaled(const mx_qgm_mix_bf16_call* call, const float* gscale_dev, int64_t iter, float lr,
+                           const float* lr_dev, void* stream);
+int mx_qgm_mix_bf16_scaled_at(const mx_qgm_mix_bf16_call* call, const float* gscale_dev, const int64_t* iter_dev,
+                              int64_t n_iters, float lr, const float* lr_dev, void* stream);
+int mx_qgm_mix_bf16_grouped(const mx_qgm_mix_bf16_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                            int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_qgm_mix_bf16_grouped_at(const mx_qgm_mix_bf16_call* call, const mx_param_runs* runs,
+                               const float* gscale_dev, const int64_t* iter_dev, int64_t n_iters, float lr,
+                               const float* lr_dev, void* stream);
+
 /* ---------------------------------------------------------------- flatten / unflatten
  * mx_gather replaces flatten_tensors (comm_helpers.py:12-30): flat[off[s] + i] = src[s][i].
  * mx_scatter is the copy_ loop of reset_model over unflatten_tensors views
