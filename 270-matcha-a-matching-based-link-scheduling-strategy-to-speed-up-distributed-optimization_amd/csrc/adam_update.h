@@ -1,6 +1,8 @@
 // adam_update.h -- torch.optim.AdamW's / Adam's single-tensor update on fp32 values, as adamw_mix.hip and
 // adamw_mix_bf16.hip apply it on the way into LDS: the same functions in both precisions, only load,
 // widen, store and pack differ.  The contract is at the head of those files.
+// After the arithmetic: the one policy template of both families over a storage form (fused_round.h) and
+// their one host function template.
 #pragma once
 #include "fused_round.h"
 
@@ -150,6 +152,84 @@ __device__ __forceinline__ F4 adam_chunk(const F4& x, const F4& g, F4& m, F4& v,
     } else {
         return adam4(x, g, m, v, s.st, h);
     }
+}
+
+// the policy of both families: x (the fp32 row, or the master), g, m and v; wide accesses only where x, m
+// and v of the (segment, row) are 16-byte aligned and the form's arrays to its own accesses
+template <class F>
+struct AdamRows {
+    using Form = F;
+    using Hyper = AdamHyper;
+    using State = AdamState;
+    struct Tabs {
+        float* const* x;
+        typename Form::GT* const* g;
+        float* const* m;
+        float* const* v;
+        typename Form::PTab p;
+    };
+    struct Lane {
+        F4 X[kB], Mv[kB], Vv[kB];
+        typename Form::GC G[kB];
+    };
+    static __device__ __forceinline__ bool vec_of(const Tabs& tb, const Geo& gq, int k) {
+        return al16(tb.x[gq.base + k]) && al16(tb.m[gq.base + k]) && al16(tb.v[gq.base + k]) && Form::al(tb, gq, k);
+    }
+    template <bool NT>
+    static __device__ __forceinline__ void load(Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
+                                                bool vec) {
+        ln.X[t] = load_chunk<NT>(tb.x[gq.base + k], c, gq.lim, vec);
+        ln.G[t] = load_chunk<NT>(tb.g[gq.base + k], c, gq.lim, vec);
+        ln.Mv[t] = load_chunk<NT>(tb.m[gq.base + k], c, gq.lim, vec);
+        ln.Vv[t] = load_chunk<NT>(tb.v[gq.base + k], c, gq.lim, vec);
+    }
+    static __device__ __forceinline__ bool no_step(State& st, const Hyper& h) { return adam_no_step(st, h); }
+    static __device__ __forceinline__ void setup(State& st, const Hyper& h) { adam_setup(st, h); }
+    template <bool GROUPED>
+    static __device__ __forceinline__ void begin_item(State& st, const Geo& cur, const Hyper& h) {
+        adam_begin_item<GROUPED>(st, cur, h);
+    }
+    template <bool GROUPED>
+    static __device__ __forceinline__ F4 update(Lane& ln, int t, int k, int64_t c, const Geo& gq, const State& st,
+                                                const GroupedIf<Hyper, GROUPED>& h) {
+        return adam_chunk<GROUPED>(ln.X[t], grad_of(ln.G[t], h, k), ln.Mv[t], ln.Vv[t], c, gq, st, h);
+    }
+    template <int SP>
+    static __device__ __forceinline__ void keep(const Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
+                                                bool vec, const Hyper& h) {
+        store_chunk<SP>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
+        store_chunk<SP>(tb.v[gq.base + k], c, gq.lim, vec, ln.Vv[t]);
+        if (h.zero_grads) store_chunk<SP>(tb.g[gq.base + k], c, gq.lim, vec, Form::zero());
+    }
+    template <int SP>
+    static __device__ __forceinline__ void finish(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
+                                                  const F4& acc) {
+        Form::template store<SP>(tb, gq, k, c, vec, acc);
+    }
+};
+
+// the host side of both families: Mix is the family's named policy, Call its call record
+template <class Mix, class Call>
+int adamw_round(const Tune& tune, const Call* c, const mx_param_runs* runs, const float* gscale, int64_t iter,
+                const int64_t* iter_dev, int64_t step, const int64_t* step_dev, float lr, const float* lr_dev,
+                void* stream, const char* who) {
+    using Form = typename Mix::Form;
+    MX_CHECK(c, "%s: null call record", who);
+    MX_CHECK(Form::tables(c) && c->m_ptrs_dev && c->v_ptrs_dev && c->seg_len_dev && c->tile_off_dev && c->plan_dev &&
+                 c->bias_dev,
+             "%s: null pointer", who);
+    Round r;
+    if (const int rc = check_round(c, iter, iter_dev, stream, who, &r)) return rc;
+    MX_CHECK(c->n_bias >= 1, "%s: n_bias=%lld < 1", who, (long long)c->n_bias);
+    MX_CHECK(iter >= 0, "%s: iter < 0", who);
+    MX_CHECK(step_dev || step >= 1, "%s: optimizer step %lld < 1", who, (long long)step);
+    if (const int rc = check_runs(runs, who)) return rc;
+    if (c->total_tiles <= 0) return MX_OK;
+    // bytes the round moves: the form's, m and v read + written, g zeroed
+    const int bpe = Form::kBytes + 16 + (c->zero_grads ? (int)sizeof(typename Form::GT) : 0);
+    const AdamHyper h{lr, c->wd, c->omb1, c->beta2, c->omb2, c->eps, lr_dev, gscale, c->bias_dev, c->n_bias, step, step_dev,
+                      c->decoupled != 0, c->zero_grads != 0};
+    return Form::template run<Mix>(tune, r, bpe, h, runs, c, c->m_ptrs_dev, c->v_ptrs_dev);
 }
 
 }  // namespace fused

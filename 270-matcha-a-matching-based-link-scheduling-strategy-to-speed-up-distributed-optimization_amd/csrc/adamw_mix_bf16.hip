@@ -52,138 +52,16 @@
 // every round, the first loads are issued before the plan record is looked at.  No receive slots:
 // n_slots == n_local.
 //
-// The row kernel, its mixing walk and the host side are fused_round.h's; this file is the policy that
-// kernel is instantiated with (kernel traces show it as fused_round_rows<AdamwMixBf16, ...>).
+// The row kernel, its mixing walk and the host side are fused_round.h's and the policy is adam_update.h's
+// AdamRows over a storage form; this file names the policy the kernel is instantiated with (kernel traces show
+// it as fused_round_rows<AdamwMixBf16, ...>) and defines the family's entry points.
 #include "adam_update.h"
 
 namespace {
 using namespace mx::fused;
-
 // w, m and v as fp32, g and p as bf16; wide accesses only where the (segment, row)'s w, m and v are
 // 16-byte and g and p 8-byte aligned
-struct AdamwMixBf16 {
-    using Hyper = AdamHyper;
-    using State = AdamState;
-    struct Tabs {
-        float* const* w;
-        uint16_t* const* g;
-        float* const* m;
-        float* const* v;
-        uint16_t* const* p;
-    };
-    struct Lane {
-        F4 X[kB], Mv[kB], Vv[kB];
-        U2 G[kB];
-    };
-    static __device__ __forceinline__ bool vec_of(const Tabs& tb, const Geo& gq, int k) {
-        return al16(tb.w[gq.base + k]) && al16(tb.m[gq.base + k]) && al16(tb.v[gq.base + k]) && al8(tb.g[gq.base + k]) && al8(tb.p[gq.base + k]);
-    }
-    template <bool NT>
-    static __device__ __forceinline__ void load(Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
-                                                bool vec) {
-        ln.X[t] = load_chunk<NT>(tb.w[gq.base + k], c, gq.lim, vec);
-        ln.G[t] = load_chunk<NT>(tb.g[gq.base + k], c, gq.lim, vec);
-        ln.Mv[t] = load_chunk<NT>(tb.m[gq.base + k], c, gq.lim, vec);
-        ln.Vv[t] = load_chunk<NT>(tb.v[gq.base + k], c, gq.lim, vec);
-    }
-    static __device__ __forceinline__ bool no_step(State& st, const Hyper& h) { return adam_no_step(st, h); }
-    static __device__ __forceinline__ void setup(State& st, const Hyper& h) { adam_setup(st, h); }
-    template <bool GROUPED>
-    static __device__ __forceinline__ void begin_item(State& st, const Geo& cur, const Hyper& h) {
-        adam_begin_item<GROUPED>(st, cur, h);
-    }
-    template <bool GROUPED>
-    static __device__ __forceinline__ F4 update(Lane& ln, int t, int k, int64_t c, const Geo& gq, const State& st,
-                                                const GroupedIf<Hyper, GROUPED>& h) {
-        return adam_chunk<GROUPED>(ln.X[t], grad_of(ln.G[t], h, k), ln.Mv[t], ln.Vv[t], c, gq, st, h);
-    }
-    template <int SP>
-    static __device__ __forceinline__ void keep(const Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
-                                                bool vec, const Hyper& h) {
-        store_chunk<SP>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
-        store_chunk<SP>(tb.v[gq.base + k], c, gq.lim, vec, ln.Vv[t]);
-        if (h.zero_grads) store_chunk<SP>(tb.g[gq.base + k], c, gq.lim, vec, U2{0u, 0u});
-    }
-    template <int SP>
-    static __device__ __forceinline__ void finish(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
-                                                  const F4& acc) {
-        store_chunk<SP>(tb.w[gq.base + k], c, gq.lim, vec, acc);
-        store_chunk<SP>(tb.p[gq.base + k], c, gq.lim, vec, pack4(acc));         // the model row: bf16 of the stored w
-    }
-};
-
-Tune g_tune;
-
-int adamw_mix_bf16(const mx_adamw_mix_bf16_call* c, const mx_param_runs* runs, const float* gscale, int64_t iter,
-                   const int64_t* iter_dev, int64_t step, const int64_t* step_dev, float lr, const float* lr_dev,
-                   void* stream, const char* who) {
-    MX_CHECK(c, "%s: null call record", who);
-    MX_CHECK(c->w_ptrs_dev && c->g_ptrs_dev && c->m_ptrs_dev && c->v_ptrs_dev && c->p_ptrs_dev && c->seg_len_dev &&
-                 c->tile_off_dev && c->plan_dev && c->bias_dev,
-             "%s: null pointer", who);
-    Round r;
-    if (const int rc = check_round(c, iter, iter_dev, stream, who, &r)) return rc;
-    MX_CHECK(c->n_bias >= 1, "%s: n_bias=%lld < 1", who, (long long)c->n_bias);
-    MX_CHECK(iter >= 0, "%s: iter < 0", who);
-    MX_CHECK(step_dev || step >= 1, "%s: optimizer step %lld < 1", who, (long long)step);
-    if (const int rc = check_runs(runs, who)) return rc;
-    if (c->total_tiles <= 0) return MX_OK;
-    // bytes the round moves: w, m, v read + written, g read (+ zeroed), p written
-    const int bpe = 28 + (c->zero_grads ? 2 : 0);
-    const AdamHyper h{lr, c->wd, c->omb1, c->beta2, c->omb2, c->eps, lr_dev, gscale, c->bias_dev, c->n_bias, step, step_dev,
-                      c->decoupled != 0, c->zero_grads != 0};
-    return dispatch<AdamwMixBf16>(g_tune, r, bpe, h, runs, c->w_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev, c->v_ptrs_dev,
-                                  c->p_ptrs_dev);
-}
+struct AdamwMixBf16 : AdamRows<Bf16Form> {};
 }  // namespace
 
-extern "C" int mx_adamw_mix_bf16_tile(int n_slots) { return pick(n_slots).tile; }
-
-extern "C" int mx_adamw_mix_bf16_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host) {
-    return layout("mx_adamw_mix_bf16_layout", seg_len_host, nseg, n_slots, tile_off_host);
-}
-
-extern "C" int mx_adamw_mix_bf16_set(const char* key, int value) {
-    return g_tune.set("mx_adamw_mix_bf16_set", key, value);
-}
-
-extern "C" int mx_adamw_mix_bf16_get(const char* key) { return g_tune.get("mx_adamw_mix_bf16_get", key); }
-
-extern "C" int mx_adamw_mix_bf16(const mx_adamw_mix_bf16_call* c, int64_t iter, int64_t step, float lr,
-                                 const float* lr_dev, void* stream) {
-    return adamw_mix_bf16(c, nullptr, nullptr, iter, nullptr, step, nullptr, lr, lr_dev, stream, "mx_adamw_mix_bf16");
-}
-
-extern "C" int mx_adamw_mix_bf16_scaled(const mx_adamw_mix_bf16_call* c, const float* gscale_dev, int64_t iter,
-                                        int64_t step, float lr, const float* lr_dev, void* stream) {
-    return adamw_mix_bf16(c, nullptr, gscale_dev, iter, nullptr, step, nullptr, lr, lr_dev, stream, "mx_adamw_mix_bf16_scaled");
-}
-
-extern "C" int mx_adamw_mix_bf16_at(const mx_adamw_mix_bf16_call* c, const int64_t* iter_dev, int64_t n_iters,
-                                    const int64_t* step_dev, float lr, const float* lr_dev, void* stream) {
-    MX_CHECK(iter_dev && step_dev, "mx_adamw_mix_bf16_at: null iteration or step counter");
-    return adamw_mix_bf16(c, nullptr, nullptr, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream, "mx_adamw_mix_bf16_at");
-}
-
-extern "C" int mx_adamw_mix_bf16_scaled_at(const mx_adamw_mix_bf16_call* c, const float* gscale_dev,
-                                           const int64_t* iter_dev, int64_t n_iters, const int64_t* step_dev,
-                                           float lr, const float* lr_dev, void* stream) {
-    MX_CHECK(iter_dev && step_dev, "mx_adamw_mix_bf16_scaled_at: null iteration or step counter");
-    return adamw_mix_bf16(c, nullptr, gscale_dev, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream,
-                          "mx_adamw_mix_bf16_scaled_at");
-}
-
-extern "C" int mx_adamw_mix_bf16_grouped(const mx_adamw_mix_bf16_call* c, const mx_param_runs* runs,
-                                         const float* gscale_dev, int64_t iter, int64_t step, float lr,
-                                         const float* lr_dev, void* stream) {
-    return adamw_mix_bf16(c, runs, gscale_dev, iter, nullptr, step, nullptr, lr, lr_dev, stream,
-                          "mx_adamw_mix_bf16_grouped");
-}
-
-extern "C" int mx_adamw_mix_bf16_grouped_at(const mx_adamw_mix_bf16_call* c, const mx_param_runs* runs,
-                                            const float* gscale_dev, const int64_t* iter_dev, int64_t n_iters,
-                                            const int64_t* step_dev, float lr, const float* lr_dev, void* stream) {
-    MX_CHECK(iter_dev && step_dev, "mx_adamw_mix_bf16_grouped_at: null iteration or step counter");
-    return adamw_mix_bf16(c, runs, gscale_dev, n_iters, iter_dev, 0, step_dev, lr, lr_dev, stream,
-                          "mx_adamw_mix_bf16_grouped_at");
-}
+MX_FUSED_FAMILY(adamw_mix_bf16, Tune, MX_WITH_STEP, adamw_round<AdamwMixBf16>)

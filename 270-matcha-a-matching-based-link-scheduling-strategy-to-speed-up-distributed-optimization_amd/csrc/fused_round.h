@@ -1,6 +1,7 @@
-// fused_round.h -- the scaffold the fused optimizer rounds share (sgd_mix.hip, sgd_mix_bf16.hip,
-// adamw_mix.hip, adamw_mix_bf16.hip): one row kernel that stages a work item's updated rows in LDS and
-// runs the mixing round on them, and the host side that picks its class, grid and streaming mode.
+// fused_round.h -- the scaffold the fused optimizer rounds share (sgd_mix.hip, adamw_mix.hip, lion_mix.hip,
+// qgm_mix.hip and the _bf16 file of each): one row kernel that stages a work item's updated rows in LDS and
+// runs the mixing round on them, the host side that picks its class, grid and streaming mode, the two
+// storage forms and the definition of a family's entry points.
 //
 // A family supplies a compile-time policy type `Update` and nothing else:
 //     Hyper                 the launch's argument block (fields lr, lr_dev, gscale, zero_grads and its own)
@@ -22,8 +23,25 @@
 //                           launch state and the (grouped) argument block; the work item's own Geo resolves
 //                           the run, as sgd_chunk does
 // Everything a policy decides is decided at compile time; the kernel has no run-time branch on the family.
-// A new optimizer whose state is settled before the round is a new policy type plus its entry points:
-// nothing in this file changes.  Policies without the flag compile to exactly what they did without the hook.
+// Policies without the flag compile to exactly what they did without the hook.
+//
+// An optimizer's two families (fp32 rows; bf16 rows over fp32 masters) differ only in storage, so each
+// optimizer writes ONE policy template over a storage form (Fp32Form, Bf16Form: at the end of this file) in
+// its *_update.h, beside its arithmetic and its one host function template.  A form supplies
+//     GT, GC                the gradient's element and chunk type (float / F4, uint16_t / U2)
+//     PTab                  the type of the last member `p` of every Tabs: the bf16 model rows' table (fp32: empty)
+//     zero()                the chunk stored over g
+//     al(tb, gq, k)         its share of the alignment rule: g (and p) of the (segment, row)
+//     store<SP>(...)        the store of a mixed chunk: x, or the master and p = pack4(acc)
+//     kBytes                the bytes per element the round moves on x, g (and p)
+//     tables(c), run<U>(..) which fields of the call record are its tables, and dispatch with them in
+//                           kernel-argument order: x, g, the optimizer's state tables (, p)
+// A policy's Tabs names the mixed fp32 row `x` in both forms (the master `w` of a bf16 call record).  The
+// kernel is instantiated with NAMED policies, one line each in the family's .hip file
+// (template <bool MOM> struct SgdMixBf16 : SgdRows<Bf16Form, MOM> {};), so kernel traces and resource tables
+// show the family.  MX_FUSED_FAMILY, also at the end, defines a family's knobs and its ten entry points.
+// A new optimizer is one policy template, two named policies and two MX_FUSED_FAMILY lines: nothing in this
+// file changes.
 //
 // In place: a tile's x' of every row is parked in LDS (barrier) before any x row of it is stored, and
 // different work items never share a column.  State arrays are read and written by the same lane only, so
@@ -437,5 +455,122 @@ int dispatch(const Tune& tune, const Round& r, int bytes_per_elem, const typenam
 #undef MX_FUSED_POL
 }
 
+// ---------------------------------------------------------------- the storage forms
+
+// The helpers index the tables as the policies do, tb.g[gq.base + k] at every use: with the index computed
+// once by the caller the bf16 kernels came out different (profiles/fused_forms_refactor.md).
+
+// fp32 rows: x, g and the optimizer's state all fp32, 16-byte accesses
+struct NoTable {};
+struct Fp32Form {
+    using GT = float;
+    using GC = F4;
+    using PTab = NoTable;
+    static constexpr int kBytes = 12;      // x read + written, g read
+    static __device__ __forceinline__ GC zero() { return F4{0.0f, 0.0f, 0.0f, 0.0f}; }
+    template <class Tabs>
+    static __device__ __forceinline__ bool al(const Tabs& tb, const Geo& gq, int k) {
+        return al16(tb.g[gq.base + k]);
+    }
+    template <int SP, class Tabs>
+    static __device__ __forceinline__ void store(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
+                                                 const F4& acc) {
+        store_chunk<SP>(tb.x[gq.base + k], c, gq.lim, vec, acc);
+    }
+    template <class Call>
+    static bool tables(const Call* c) {
+        return c->x_ptrs_dev && c->g_ptrs_dev;
+    }
+    template <class Update, class Call, class... S>
+    static int run(const Tune& tune, const Round& r, int bpe, const typename Update::Hyper& h, const mx_param_runs* runs,
+                   const Call* c, S... state) {
+        return dispatch<Update>(tune, r, bpe, h, runs, c->x_ptrs_dev, c->g_ptrs_dev, state...);
+    }
+};
+
+// bf16 rows over fp32 masters: the master w (a policy's `x`) and the state fp32, the gradient g and the
+// model row p bf16 in 8-byte accesses; p is write only, the rounded image of every master chunk stored
+struct Bf16Form {
+    using GT = uint16_t;
+    using GC = U2;
+    using PTab = uint16_t* const*;
+    static constexpr int kBytes = 12;      // w read + written, g read, p written
+    static __device__ __forceinline__ GC zero() { return U2{0u, 0u}; }
+    template <class Tabs>
+    static __device__ __forceinline__ bool al(const Tabs& tb, const Geo& gq, int k) {
+        return al8(tb.g[gq.base + k]) && al8(tb.p[gq.base + k]);
+    }
+    template <int SP, class Tabs>
+    static __device__ __forceinline__ void store(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
+                                                 const F4& acc) {
+        store_chunk<SP>(tb.x[gq.base + k], c, gq.lim, vec, acc);
+        store_chunk<SP>(tb.p[gq.base + k], c, gq.lim, vec, pack4(acc));         // the model row: bf16 of the stored w
+    }
+    template <class Call>
+    static bool tables(const Call* c) {
+        return c->w_ptrs_dev && c->g_ptrs_dev && c->p_ptrs_dev;
+    }
+    template <class Update, class Call, class... S>
+    static int run(const Tune& tune, const Round& r, int bpe, const typename Update::Hyper& h, const mx_param_runs* runs,
+                   const Call* c, S... state) {
+        return dispatch<Update>(tune, r, bpe, h, runs, c->w_ptrs_dev, c->g_ptrs_dev, state..., c->p_ptrs_dev);
+    }
+};
+
 }  // namespace fused
 }  // namespace mx
+
+// ---------------------------------------------------------------- a family's entry points
+
+// MX_FUSED_FAMILY(name, TUNE, S, round): the knobs of family `name` (its own TUNE instance: mx::fused::Tune,
+// or a type derived from it whose set / get know further keys) and its ten entry points, as
+// include/matcha_gossip.h declares them.  `round` is the optimizer's host function template instantiated
+// with the family's named policy: round(tune, c, runs, gscale, iter, iter_dev, [step, step_dev,] lr, lr_dev,
+// stream, who).  S is MX_WITH_STEP for an optimizer with a step counter (AdamW), else MX_NO_STEP.
+#define MX_NO_STEP(...)
+#define MX_WITH_STEP(...) __VA_ARGS__
+#define MX_FUSED_FAMILY(name, TUNE, S, ...)                                                                            \
+    namespace {                                                                                                        \
+    TUNE g_tune;                                                                                                       \
+    }                                                                                                                  \
+    extern "C" int mx_##name##_tile(int n_slots) { return mx::fused::pick(n_slots).tile; }                             \
+    extern "C" int mx_##name##_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host) {    \
+        return mx::fused::layout("mx_" #name "_layout", seg_len_host, nseg, n_slots, tile_off_host);                   \
+    }                                                                                                                  \
+    extern "C" int mx_##name##_set(const char* key, int value) { return g_tune.set("mx_" #name "_set", key, value); }  \
+    extern "C" int mx_##name##_get(const char* key) { return g_tune.get("mx_" #name "_get", key); }                    \
+    extern "C" int mx_##name(const mx_##name##_call* c, int64_t iter, S(int64_t step, ) float lr, const float* lr_dev, \
+                             void* stream) {                                                                           \
+        return __VA_ARGS__(g_tune, c, nullptr, nullptr, iter, nullptr, S(step, nullptr, ) lr, lr_dev, stream,          \
+                           "mx_" #name);                                                                               \
+    }                                                                                                                  \
+    extern "C" int mx_##name##_scaled(const mx_##name##_call* c, const float* gscale_dev, int64_t iter,                \
+                                      S(int64_t step, ) float lr, const float* lr_dev, void* stream) {                 \
+        return __VA_ARGS__(g_tune, c, nullptr, gscale_dev, iter, nullptr, S(step, nullptr, ) lr, lr_dev, stream,       \
+                           "mx_" #name "_scaled");                                                                     \
+    }                                                                                                                  \
+    extern "C" int mx_##name##_grouped(const mx_##name##_call* c, const mx_param_runs* runs, const float* gscale_dev,  \
+                                       int64_t iter, S(int64_t step, ) float lr, const float* lr_dev, void* stream) {  \
+        return __VA_ARGS__(g_tune, c, runs, gscale_dev, iter, nullptr, S(step, nullptr, ) lr, lr_dev, stream,          \
+                           "mx_" #name "_grouped");                                                                    \
+    }                                                                                                                  \
+    extern "C" int mx_##name##_at(const mx_##name##_call* c, const int64_t* iter_dev, int64_t n_iters,                 \
+                                  S(const int64_t* step_dev, ) float lr, const float* lr_dev, void* stream) {          \
+        MX_CHECK(iter_dev S(&& step_dev), "mx_" #name "_at: null iteration" S(" or step") " counter");                 \
+        return __VA_ARGS__(g_tune, c, nullptr, nullptr, n_iters, iter_dev, S(0, step_dev, ) lr, lr_dev, stream,        \
+                           "mx_" #name "_at");                                                                         \
+    }                                                                                                                  \
+    extern "C" int mx_##name##_scaled_at(const mx_##name##_call* c, const float* gscale_dev, const int64_t* iter_dev,  \
+                                         int64_t n_iters, S(const int64_t* step_dev, ) float lr, const float* lr_dev,  \
+                                         void* stream) {                                                               \
+        MX_CHECK(iter_dev S(&& step_dev), "mx_" #name "_scaled_at: null iteration" S(" or step") " counter");          \
+        return __VA_ARGS__(g_tune, c, nullptr, gscale_dev, n_iters, iter_dev, S(0, step_dev, ) lr, lr_dev, stream,     \
+                           "mx_" #name "_scaled_at");                                                                  \
+    }                                                                                                                  \
+    extern "C" int mx_##name##_grouped_at(const mx_##name##_call* c, const mx_param_runs* runs,                        \
+                                          const float* gscale_dev, const int64_t* iter_dev, int64_t n_iters,           \
+                                          S(const int64_t* step_dev, ) float lr, const float* lr_dev, void* stream) {  \
+        MX_CHECK(iter_dev S(&& step_dev), "mx_" #name "_grouped_at: null iteration" S(" or step") " counter");         \
+        return __VA_ARGS__(g_tune, c, runs, gscale_dev, n_iters, iter_dev, S(0, step_dev, ) lr, lr_dev, stream,        \
+                           "mx_" #name "_grouped_at");                                                                 \
+    }

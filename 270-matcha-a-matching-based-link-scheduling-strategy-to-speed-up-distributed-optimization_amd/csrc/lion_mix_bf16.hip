@@ -36,144 +36,16 @@
 // to its own access (16 bytes fp32, 8 bytes bf16), g and p are 8-byte aligned and the 4 elements are in
 // range; everything else goes element by element (4-byte / 2-byte accesses), zero-filled past the end.
 //
-// The row kernel, its mixing walk and the host side are fused_round.h's; this file is the policy that
-// kernel is instantiated with (kernel traces show it as fused_round_rows<LionMixBf16<MB16>, ...>).
+// The row kernel, its mixing walk and the host side are fused_round.h's and the policy is lion_update.h's
+// LionRows over a storage form; this file names the policy the kernel is instantiated with (kernel traces show
+// it as fused_round_rows<LionMixBf16<MB16>, ...>) and defines the family's entry points.
 #include "lion_update.h"
 
 namespace {
 using namespace mx::fused;
-
-// w as fp32, g and p as bf16, m as fp32 (MB16 = false) or bf16 (MB16 = true: held in flight as its 8
-// bytes, widened for the update and rounded once on the way back)
+// w as fp32, g and p as bf16, m as fp32 (MB16 = false) or bf16 (MB16 = true)
 template <bool MB16>
-struct LionMixBf16 {
-    using Hyper = LionHyper;
-    using State = LionState;
-    using MT = std::conditional_t<MB16, uint16_t, float>;
-    using MC = std::conditional_t<MB16, U2, F4>;
-    struct Tabs {
-        float* const* w;
-        uint16_t* const* g;
-        MT* const* m;
-        uint16_t* const* p;
-    };
-    struct Lane {
-        F4 X[kB];
-        MC Mv[kB];
-        U2 G[kB];
-    };
-    static __device__ __forceinline__ bool vec_of(const Tabs& tb, const Geo& gq, int k) {
-        const bool v = al16(tb.w[gq.base + k]) && al8(tb.g[gq.base + k]) && al8(tb.p[gq.base + k]);
-        if constexpr (MB16) return v && al8(tb.m[gq.base + k]);
-        else return v && al16(tb.m[gq.base + k]);
-    }
-    template <bool NT>
-    static __device__ __forceinline__ void load(Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
-                                                bool vec) {
-        ln.X[t] = load_chunk<NT>(tb.w[gq.base + k], c, gq.lim, vec);
-        ln.G[t] = load_chunk<NT>(tb.g[gq.base + k], c, gq.lim, vec);
-        ln.Mv[t] = load_chunk<NT>(tb.m[gq.base + k], c, gq.lim, vec);
-    }
-    static __device__ __forceinline__ bool no_step(State& st, const Hyper& h) { return lion_no_step(st, h); }
-    static __device__ __forceinline__ void setup(State& st, const Hyper& h) { lion_setup(st, h); }
-    template <bool GROUPED>
-    static __device__ __forceinline__ void begin_item(State& st, const Geo& cur, const Hyper& h) {
-        lion_begin_item<GROUPED>(st, cur, h);
-    }
-    template <bool GROUPED>
-    static __device__ __forceinline__ F4 update(Lane& ln, int t, int k, int64_t c, const Geo& gq, const State& st,
-                                                const GroupedIf<Hyper, GROUPED>& h) {
-        if constexpr (MB16) {
-            F4 m32 = widen4(ln.Mv[t]);
-            const F4 out = lion_chunk<GROUPED>(ln.X[t], grad_of(ln.G[t], h, k), m32, c, gq, st, h);
-            ln.Mv[t] = pack4(m32);                                                  // the one rounding of m'
-            return out;
-        } else {
-            return lion_chunk<GROUPED>(ln.X[t], grad_of(ln.G[t], h, k), ln.Mv[t], c, gq, st, h);
-        }
-    }
-    template <int SP>
-    static __device__ __forceinline__ void keep(const Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
-                                                bool vec, const Hyper& h) {
-        store_chunk<SP>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
-        if (h.zero_grads) store_chunk<SP>(tb.g[gq.base + k], c, gq.lim, vec, U2{0u, 0u});
-    }
-    template <int SP>
-    static __device__ __forceinline__ void finish(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
-                                                  const F4& acc) {
-        store_chunk<SP>(tb.w[gq.base + k], c, gq.lim, vec, acc);
-        store_chunk<SP>(tb.p[gq.base + k], c, gq.lim, vec, pack4(acc));         // the model row: bf16 of the stored w
-    }
-};
-
-Tune g_tune;
-
-int lion_mix_bf16(const mx_lion_mix_bf16_call* c, const mx_param_runs* runs, const float* gscale, int64_t iter,
-                  const int64_t* iter_dev, float lr, const float* lr_dev, void* stream, const char* who) {
-    MX_CHECK(c, "%s: null call record", who);
-    MX_CHECK(c->w_ptrs_dev && c->g_ptrs_dev && c->p_ptrs_dev && c->seg_len_dev && c->tile_off_dev && c->plan_dev,
-             "%s: null pointer", who);
-    Round r;
-    if (const int rc = check_round(c, iter, iter_dev, stream, who, &r)) return rc;
-    MX_CHECK(iter >= 0, "%s: iter < 0", who);
-    MX_CHECK(c->m_ptrs_dev, "%s: null momentum table (Lion always carries momentum)", who);
-    if (const int rc = check_runs(runs, who)) return rc;
-    if (c->total_tiles <= 0) return MX_OK;
-    const bool mb16 = c->m_bf16 != 0;
-    // bytes the round moves: w read + written, g read (+ zeroed), p written, m read + written
-    const int bpe = 12 + (mb16 ? 4 : 8) + (c->zero_grads ? 2 : 0);
-    const LionHyper h{lr, c->wd, c->omb1, c->omb2, lr_dev, gscale, c->zero_grads != 0};
-    return mb16 ? dispatch<LionMixBf16<true>>(g_tune, r, bpe, h, runs, c->w_ptrs_dev, c->g_ptrs_dev,
-                                              reinterpret_cast<uint16_t* const*>(c->m_ptrs_dev), c->p_ptrs_dev)
-                : dispatch<LionMixBf16<false>>(g_tune, r, bpe, h, runs, c->w_ptrs_dev, c->g_ptrs_dev,
-                                               reinterpret_cast<float* const*>(c->m_ptrs_dev), c->p_ptrs_dev);
-}
+struct LionMixBf16 : LionRows<Bf16Form, MB16> {};
 }  // namespace
 
-extern "C" int mx_lion_mix_bf16_tile(int n_slots) { return pick(n_slots).tile; }
-
-extern "C" int mx_lion_mix_bf16_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host) {
-    return layout("mx_lion_mix_bf16_layout", seg_len_host, nseg, n_slots, tile_off_host);
-}
-
-extern "C" int mx_lion_mix_bf16_set(const char* key, int value) {
-    return g_tune.set("mx_lion_mix_bf16_set", key, value);
-}
-
-extern "C" int mx_lion_mix_bf16_get(const char* key) { return g_tune.get("mx_lion_mix_bf16_get", key); }
-
-extern "C" int mx_lion_mix_bf16(const mx_lion_mix_bf16_call* c, int64_t iter, float lr, const float* lr_dev,
-                                void* stream) {
-    return lion_mix_bf16(c, nullptr, nullptr, iter, nullptr, lr, lr_dev, stream, "mx_lion_mix_bf16");
-}
-
-extern "C" int mx_lion_mix_bf16_scaled(const mx_lion_mix_bf16_call* c, const float* gscale_dev, int64_t iter, float lr,
-                                       const float* lr_dev, void* stream) {
-    return lion_mix_bf16(c, nullptr, gscale_dev, iter, nullptr, lr, lr_dev, stream, "mx_lion_mix_bf16_scaled");
-}
-
-extern "C" int mx_lion_mix_bf16_at(const mx_lion_mix_bf16_call* c, const int64_t* iter_dev, int64_t n_iters, float lr,
-                                   const float* lr_dev, void* stream) {
-    MX_CHECK(iter_dev, "mx_lion_mix_bf16_at: null iteration counter");
-    return lion_mix_bf16(c, nullptr, nullptr, n_iters, iter_dev, lr, lr_dev, stream, "mx_lion_mix_bf16_at");
-}
-
-extern "C" int mx_lion_mix_bf16_scaled_at(const mx_lion_mix_bf16_call* c, const float* gscale_dev,
-                                          const int64_t* iter_dev, int64_t n_iters, float lr, const float* lr_dev,
-                                          void* stream) {
-    MX_CHECK(iter_dev, "mx_lion_mix_bf16_scaled_at: null iteration counter");
-    return lion_mix_bf16(c, nullptr, gscale_dev, n_iters, iter_dev, lr, lr_dev, stream, "mx_lion_mix_bf16_scaled_at");
-}
-
-extern "C" int mx_lion_mix_bf16_grouped(const mx_lion_mix_bf16_call* c, const mx_param_runs* runs,
-                                        const float* gscale_dev, int64_t iter, float lr, const float* lr_dev,
-                                        void* stream) {
-    return lion_mix_bf16(c, runs, gscale_dev, iter, nullptr, lr, lr_dev, stream, "mx_lion_mix_bf16_grouped");
-}
-
-extern "C" int mx_lion_mix_bf16_grouped_at(const mx_lion_mix_bf16_call* c, const mx_param_runs* runs,
-                                           const float* gscale_dev, const int64_t* iter_dev, int64_t n_iters, float lr,
-                                           const float* lr_dev, void* stream) {
-    MX_CHECK(iter_dev, "mx_lion_mix_bf16_grouped_at: null iteration counter");
-    return lion_mix_bf16(c, runs, gscale_dev, n_iters, iter_dev, lr, lr_dev, stream, "mx_lion_mix_bf16_grouped_at");
-}
+MX_FUSED_FAMILY(lion_mix_bf16, Tune, MX_NO_STEP, lion_round<LionMixBf16<false>, LionMixBf16<true>>)

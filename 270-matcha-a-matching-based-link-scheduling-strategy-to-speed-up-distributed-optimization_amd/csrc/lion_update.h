@@ -2,6 +2,8 @@
 // the sign of an interpolated momentum, decoupled weight decay) on fp32 values, as lion_mix.hip and
 // lion_mix_bf16.hip apply it on the way into LDS: the same functions in both precisions, only load,
 // widen, store and pack differ.  The contract is at the head of those files.
+// After the arithmetic: the one policy template of both families over a storage form (fused_round.h) and
+// their one host function template.
 #pragma once
 #include "fused_round.h"
 
@@ -106,6 +108,98 @@ __device__ __forceinline__ F4 lion_chunk(const F4& x, const F4& g, F4& m, int64_
     } else {
         return lion4(x, g, m, s.rn, h);
     }
+}
+
+// the policy of both families: x (the fp32 row, or the master), g and m.  m is fp32 (MB16 = false) or, in
+// the bf16 family alone, bf16 (MB16 = true: held in flight as its 8 bytes, widened for the update and
+// rounded once on the way back).  Wide accesses only where x of the (segment, row) is 16-byte aligned and m
+// and the form's arrays to their own accesses
+template <class F, bool MB16>
+struct LionRows {
+    using Form = F;
+    using Hyper = LionHyper;
+    using State = LionState;
+    using MT = std::conditional_t<MB16, uint16_t, float>;
+    using MC = std::conditional_t<MB16, U2, F4>;
+    struct Tabs {
+        float* const* x;
+        typename Form::GT* const* g;
+        MT* const* m;
+        typename Form::PTab p;
+    };
+    struct Lane {
+        F4 X[kB];
+        MC Mv[kB];
+        typename Form::GC G[kB];
+    };
+    static __device__ __forceinline__ bool vec_of(const Tabs& tb, const Geo& gq, int k) {
+        const bool v = al16(tb.x[gq.base + k]) && Form::al(tb, gq, k);
+        if constexpr (MB16) return v && al8(tb.m[gq.base + k]);
+        else return v && al16(tb.m[gq.base + k]);
+    }
+    template <bool NT>
+    static __device__ __forceinline__ void load(Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
+                                                bool vec) {
+        ln.X[t] = load_chunk<NT>(tb.x[gq.base + k], c, gq.lim, vec);
+        ln.G[t] = load_chunk<NT>(tb.g[gq.base + k], c, gq.lim, vec);
+        ln.Mv[t] = load_chunk<NT>(tb.m[gq.base + k], c, gq.lim, vec);
+    }
+    static __device__ __forceinline__ bool no_step(State& st, const Hyper& h) { return lion_no_step(st, h); }
+    static __device__ __forceinline__ void setup(State& st, const Hyper& h) { lion_setup(st, h); }
+    template <bool GROUPED>
+    static __device__ __forceinline__ void begin_item(State& st, const Geo& cur, const Hyper& h) {
+        lion_begin_item<GROUPED>(st, cur, h);
+    }
+    template <bool GROUPED>
+    static __device__ __forceinline__ F4 update(Lane& ln, int t, int k, int64_t c, const Geo& gq, const State& st,
+                                                const GroupedIf<Hyper, GROUPED>& h) {
+        if constexpr (MB16) {
+            F4 m32 = widen4(ln.Mv[t]);
+            const F4 out = lion_chunk<GROUPED>(ln.X[t], grad_of(ln.G[t], h, k), m32, c, gq, st, h);
+            ln.Mv[t] = pack4(m32);                                                  // the one rounding of m'
+            return out;
+        } else {
+            return lion_chunk<GROUPED>(ln.X[t], grad_of(ln.G[t], h, k), ln.Mv[t], c, gq, st, h);
+        }
+    }
+    template <int SP>
+    static __device__ __forceinline__ void keep(const Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
+                                                bool vec, const Hyper& h) {
+        store_chunk<SP>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
+        if (h.zero_grads) store_chunk<SP>(tb.g[gq.base + k], c, gq.lim, vec, Form::zero());
+    }
+    template <int SP>
+    static __device__ __forceinline__ void finish(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
+                                                  const F4& acc) {
+        Form::template store<SP>(tb, gq, k, c, vec, acc);
+    }
+};
+
+// the host side of both families: Mix is the family's named policy with an fp32 momentum, MixB16 the one
+// with a bf16 momentum (the bf16 family's call record says which; the fp32 family names Mix twice), Call
+// the call record
+template <class Mix, class MixB16, class Call>
+int lion_round(const Tune& tune, const Call* c, const mx_param_runs* runs, const float* gscale, int64_t iter,
+               const int64_t* iter_dev, float lr, const float* lr_dev, void* stream, const char* who) {
+    using Form = typename Mix::Form;
+    MX_CHECK(c, "%s: null call record", who);
+    MX_CHECK(Form::tables(c) && c->seg_len_dev && c->tile_off_dev && c->plan_dev, "%s: null pointer", who);
+    Round r;
+    if (const int rc = check_round(c, iter, iter_dev, stream, who, &r)) return rc;
+    MX_CHECK(iter >= 0, "%s: iter < 0", who);
+    MX_CHECK(c->m_ptrs_dev, "%s: null momentum table (Lion always carries momentum)", who);
+    if (const int rc = check_runs(runs, who)) return rc;
+    if (c->total_tiles <= 0) return MX_OK;
+    // bytes the round moves: the form's, m read + written, g zeroed
+    const int zero = c->zero_grads ? (int)sizeof(typename Form::GT) : 0;
+    const LionHyper h{lr, c->wd, c->omb1, c->omb2, lr_dev, gscale, c->zero_grads != 0};
+    if constexpr (!std::is_same_v<Mix, MixB16>) {
+        if (c->m_bf16)
+            return Form::template run<MixB16>(tune, r, Form::kBytes + 4 + zero, h, runs, c,
+                                              reinterpret_cast<uint16_t* const*>(c->m_ptrs_dev));
+    }
+    return Form::template run<Mix>(tune, r, Form::kBytes + 8 + zero, h, runs, c,
+                                   reinterpret_cast<float* const*>(c->m_ptrs_dev));
 }
 
 }  // namespace fused

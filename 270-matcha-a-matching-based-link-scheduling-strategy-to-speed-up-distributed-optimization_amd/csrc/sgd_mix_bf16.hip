@@ -37,133 +37,17 @@
 // stored when its chunk is staged; so are the zeros over g.  Because every row is read in every round,
 // the first loads are issued before the plan record is looked at.  No receive slots: n_slots == n_local.
 //
-// The row kernel, its mixing walk and the host side are fused_round.h's; this file is the policy that
-// kernel is instantiated with (kernel traces show it as fused_round_rows<SgdMixBf16<MOM>, ...>).
+// The row kernel, its mixing walk and the host side are fused_round.h's and the policy is sgd_update.h's
+// SgdRows over a storage form; this file names the policy the kernel is instantiated with (kernel traces show
+// it as fused_round_rows<SgdMixBf16<MOM>, ...>) and defines the family's entry points.
 #include "sgd_update.h"
 
 namespace {
 using namespace mx::fused;
-
 // w and m as fp32, g and p as bf16; wide accesses only where the (segment, row)'s w and m are 16-byte and
 // g and p 8-byte aligned
 template <bool MOM>
-struct SgdMixBf16 {
-    using Hyper = SgdHyper;
-    using State = SgdState;
-    struct Tabs {
-        float* const* w;
-        uint16_t* const* g;
-        float* const* m;
-        uint16_t* const* p;
-    };
-    struct Lane {
-        F4 X[kB], Mv[kB];
-        U2 G[kB];
-    };
-    static __device__ __forceinline__ bool vec_of(const Tabs& tb, const Geo& gq, int k) {
-        bool v = al16(tb.w[gq.base + k]) && al8(tb.g[gq.base + k]) && al8(tb.p[gq.base + k]);
-        if constexpr (MOM) v = v && al16(tb.m[gq.base + k]);
-        return v;
-    }
-    template <bool NT>
-    static __device__ __forceinline__ void load(Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
-                                                bool vec) {
-        ln.X[t] = load_chunk<NT>(tb.w[gq.base + k], c, gq.lim, vec);
-        ln.G[t] = load_chunk<NT>(tb.g[gq.base + k], c, gq.lim, vec);
-        if constexpr (MOM) ln.Mv[t] = load_chunk<NT>(tb.m[gq.base + k], c, gq.lim, vec);
-    }
-    static __device__ __forceinline__ bool no_step(State& st, const Hyper& h) { return sgd_no_step(st, h); }
-    static __device__ __forceinline__ void setup(State& st, const Hyper& h) { sgd_setup(st, h); }
-    template <bool GROUPED>
-    static __device__ __forceinline__ void begin_item(State&, const Geo&, const Hyper&) {}
-    template <bool GROUPED>
-    static __device__ __forceinline__ F4 update(Lane& ln, int t, int k, int64_t c, const Geo& gq, const State& st,
-                                                const GroupedIf<Hyper, GROUPED>& h) {
-        return sgd_chunk<MOM, GROUPED>(ln.X[t], grad_of(ln.G[t], h, k), ln.Mv[t], c, gq, st, h);
-    }
-    template <int SP>
-    static __device__ __forceinline__ void keep(const Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
-                                                bool vec, const Hyper& h) {
-        if constexpr (MOM) store_chunk<SP>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
-        if (h.zero_grads) store_chunk<SP>(tb.g[gq.base + k], c, gq.lim, vec, U2{0u, 0u});
-    }
-    template <int SP>
-    static __device__ __forceinline__ void finish(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
-                                                  const F4& acc) {
-        store_chunk<SP>(tb.w[gq.base + k], c, gq.lim, vec, acc);
-        store_chunk<SP>(tb.p[gq.base + k], c, gq.lim, vec, pack4(acc));         // the model row: bf16 of the stored w
-    }
-};
-
-Tune g_tune;
-
-int sgd_mix_bf16(const mx_sgd_mix_bf16_call* c, const mx_param_runs* runs, const float* gscale, int64_t iter,
-                 const int64_t* iter_dev, float lr, const float* lr_dev, void* stream, const char* who) {
-    MX_CHECK(c, "%s: null call record", who);
-    MX_CHECK(c->w_ptrs_dev && c->g_ptrs_dev && c->p_ptrs_dev && c->seg_len_dev && c->tile_off_dev && c->plan_dev,
-             "%s: null pointer", who);
-    Round r;
-    if (const int rc = check_round(c, iter, iter_dev, stream, who, &r)) return rc;
-    MX_CHECK(iter >= 0, "%s: iter < 0", who);
-    MX_CHECK((c->mom != 0.0f) == (c->m_ptrs_dev != nullptr), "%s: the momentum table is given exactly when mom != 0",
-             who);
-    MX_CHECK(c->mom != 0.0f || !c->nesterov, "%s: nesterov needs momentum", who);
-    if (const int rc = check_runs(runs, who)) return rc;
-    if (c->total_tiles <= 0) return MX_OK;
-    const bool mom = c->mom != 0.0f;
-    // bytes the round moves: w read + written, g read (+ zeroed), p written, m read + written
-    const int bpe = 12 + (mom ? 8 : 0) + (c->zero_grads ? 2 : 0);
-    const SgdHyper h{lr, c->wd, c->mom, lr_dev, gscale, c->nesterov != 0, c->zero_grads != 0};
-    return mom ? dispatch<SgdMixBf16<true>>(g_tune, r, bpe, h, runs, c->w_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev,
-                                            c->p_ptrs_dev)
-               : dispatch<SgdMixBf16<false>>(g_tune, r, bpe, h, runs, c->w_ptrs_dev, c->g_ptrs_dev, c->m_ptrs_dev,
-                                             c->p_ptrs_dev);
-}
+struct SgdMixBf16 : SgdRows<Bf16Form, MOM> {};
 }  // namespace
 
-extern "C" int mx_sgd_mix_bf16_tile(int n_slots) { return pick(n_slots).tile; }
-
-extern "C" int mx_sgd_mix_bf16_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host) {
-    return layout("mx_sgd_mix_bf16_layout", seg_len_host, nseg, n_slots, tile_off_host);
-}
-
-extern "C" int mx_sgd_mix_bf16_set(const char* key, int value) {
-    return g_tune.set("mx_sgd_mix_bf16_set", key, value);
-}
-
-extern "C" int mx_sgd_mix_bf16_get(const char* key) { return g_tune.get("mx_sgd_mix_bf16_get", key); }
-
-extern "C" int mx_sgd_mix_bf16(const mx_sgd_mix_bf16_call* c, int64_t iter, float lr, const float* lr_dev,
-                               void* stream) {
-    return sgd_mix_bf16(c, nullptr, nullptr, iter, nullptr, lr, lr_dev, stream, "mx_sgd_mix_bf16");
-}
-
-extern "C" int mx_sgd_mix_bf16_scaled(const mx_sgd_mix_bf16_call* c, const float* gscale_dev, int64_t iter, float lr,
-                                      const float* lr_dev, void* stream) {
-    return sgd_mix_bf16(c, nullptr, gscale_dev, iter, nullptr, lr, lr_dev, stream, "mx_sgd_mix_bf16_scaled");
-}
-
-extern "C" int mx_sgd_mix_bf16_at(const mx_sgd_mix_bf16_call* c, const int64_t* iter_dev, int64_t n_iters, float lr,
-                                  const float* lr_dev, void* stream) {
-    MX_CHECK(iter_dev, "mx_sgd_mix_bf16_at: null iteration counter");
-    return sgd_mix_bf16(c, nullptr, nullptr, n_iters, iter_dev, lr, lr_dev, stream, "mx_sgd_mix_bf16_at");
-}
-
-extern "C" int mx_sgd_mix_bf16_scaled_at(const mx_sgd_mix_bf16_call* c, const float* gscale_dev,
-                                         const int64_t* iter_dev, int64_t n_iters, float lr, const float* lr_dev,
-                                         void* stream) {
-    MX_CHECK(iter_dev, "mx_sgd_mix_bf16_scaled_at: null iteration counter");
-    return sgd_mix_bf16(c, nullptr, gscale_dev, n_iters, iter_dev, lr, lr_dev, stream, "mx_sgd_mix_bf16_scaled_at");
-}
-
-extern "C" int mx_sgd_mix_bf16_grouped(const mx_sgd_mix_bf16_call* c, const mx_param_runs* runs, const float* gscale_dev,
-                                       int64_t iter, float lr, const float* lr_dev, void* stream) {
-    return sgd_mix_bf16(c, runs, gscale_dev, iter, nullptr, lr, lr_dev, stream, "mx_sgd_mix_bf16_grouped");
-}
-
-extern "C" int mx_sgd_mix_bf16_grouped_at(const mx_sgd_mix_bf16_call* c, const mx_param_runs* runs,
-                                          const float* gscale_dev, const int64_t* iter_dev, int64_t n_iters, float lr,
-                                          const float* lr_dev, void* stream) {
-    MX_CHECK(iter_dev, "mx_sgd_mix_bf16_grouped_at: null iteration counter");
-    return sgd_mix_bf16(c, runs, gscale_dev, n_iters, iter_dev, lr, lr_dev, stream, "mx_sgd_mix_bf16_grouped_at");
-}
+MX_FUSED_FAMILY(sgd_mix_bf16, Tune, MX_NO_STEP, sgd_round<SgdMixBf16>)

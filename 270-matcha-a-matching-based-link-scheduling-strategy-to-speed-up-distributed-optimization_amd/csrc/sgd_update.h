@@ -1,6 +1,8 @@
 // sgd_update.h -- torch.optim.SGD's update (dampening 0) on fp32 values, as sgd_mix.hip and
 // sgd_mix_bf16.hip apply it on the way into LDS: the same functions in both precisions, only load, widen,
 // store and pack differ.  The contract is at the head of those files.
+// After the arithmetic: the one policy template of both families over a storage form (fused_round.h) and
+// their one host function template.
 #pragma once
 #include "fused_round.h"
 
@@ -98,6 +100,80 @@ __device__ __forceinline__ F4 sgd_chunk(const F4& x, const F4& g, F4& m, int64_t
     } else {
         return sgd4<MOM>(x, g, m, st.nlr, h);
     }
+}
+
+// the policy of both families: x (the fp32 row, or the master), g and m; wide accesses only where x and m
+// of the (segment, row) are 16-byte aligned and the form's arrays to its own accesses
+template <class F, bool MOM>
+struct SgdRows {
+    using Form = F;
+    using Hyper = SgdHyper;
+    using State = SgdState;
+    struct Tabs {
+        float* const* x;
+        typename Form::GT* const* g;
+        float* const* m;
+        typename Form::PTab p;
+    };
+    struct Lane {
+        F4 X[kB], Mv[kB];
+        typename Form::GC G[kB];
+    };
+    static __device__ __forceinline__ bool vec_of(const Tabs& tb, const Geo& gq, int k) {
+        bool v = al16(tb.x[gq.base + k]) && Form::al(tb, gq, k);
+        if constexpr (MOM) v = v && al16(tb.m[gq.base + k]);
+        return v;
+    }
+    template <bool NT>
+    static __device__ __forceinline__ void load(Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
+                                                bool vec) {
+        ln.X[t] = load_chunk<NT>(tb.x[gq.base + k], c, gq.lim, vec);
+        ln.G[t] = load_chunk<NT>(tb.g[gq.base + k], c, gq.lim, vec);
+        if constexpr (MOM) ln.Mv[t] = load_chunk<NT>(tb.m[gq.base + k], c, gq.lim, vec);
+    }
+    static __device__ __forceinline__ bool no_step(State& st, const Hyper& h) { return sgd_no_step(st, h); }
+    static __device__ __forceinline__ void setup(State& st, const Hyper& h) { sgd_setup(st, h); }
+    template <bool GROUPED>
+    static __device__ __forceinline__ void begin_item(State&, const Geo&, const Hyper&) {}
+    template <bool GROUPED>
+    static __device__ __forceinline__ F4 update(Lane& ln, int t, int k, int64_t c, const Geo& gq, const State& st,
+                                                const GroupedIf<Hyper, GROUPED>& h) {
+        return sgd_chunk<MOM, GROUPED>(ln.X[t], grad_of(ln.G[t], h, k), ln.Mv[t], c, gq, st, h);
+    }
+    template <int SP>
+    static __device__ __forceinline__ void keep(const Lane& ln, int t, const Tabs& tb, const Geo& gq, int k, int64_t c,
+                                                bool vec, const Hyper& h) {
+        if constexpr (MOM) store_chunk<SP>(tb.m[gq.base + k], c, gq.lim, vec, ln.Mv[t]);
+        if (h.zero_grads) store_chunk<SP>(tb.g[gq.base + k], c, gq.lim, vec, Form::zero());
+    }
+    template <int SP>
+    static __device__ __forceinline__ void finish(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
+                                                  const F4& acc) {
+        Form::template store<SP>(tb, gq, k, c, vec, acc);
+    }
+};
+
+// the host side of both families: Mix<MOM> is the family's named policy, Call its call record
+template <template <bool> class Mix, class Call>
+int sgd_round(const Tune& tune, const Call* c, const mx_param_runs* runs, const float* gscale, int64_t iter,
+              const int64_t* iter_dev, float lr, const float* lr_dev, void* stream, const char* who) {
+    using Form = typename Mix<true>::Form;
+    MX_CHECK(c, "%s: null call record", who);
+    MX_CHECK(Form::tables(c) && c->seg_len_dev && c->tile_off_dev && c->plan_dev, "%s: null pointer", who);
+    Round r;
+    if (const int rc = check_round(c, iter, iter_dev, stream, who, &r)) return rc;
+    MX_CHECK(iter >= 0, "%s: iter < 0", who);
+    MX_CHECK((c->mom != 0.0f) == (c->m_ptrs_dev != nullptr), "%s: the momentum table is given exactly when mom != 0",
+             who);
+    MX_CHECK(c->mom != 0.0f || !c->nesterov, "%s: nesterov needs momentum", who);
+    if (const int rc = check_runs(runs, who)) return rc;
+    if (c->total_tiles <= 0) return MX_OK;
+    const bool mom = c->mom != 0.0f;
+    // bytes the round moves: the form's, m read + written, g zeroed
+    const int bpe = Form::kBytes + (mom ? 8 : 0) + (c->zero_grads ? (int)sizeof(typename Form::GT) : 0);
+    const SgdHyper h{lr, c->wd, c->mom, lr_dev, gscale, c->nesterov != 0, c->zero_grads != 0};
+    return mom ? Form::template run<Mix<true>>(tune, r, bpe, h, runs, c, c->m_ptrs_dev)
+               : Form::template run<Mix<false>>(tune, r, bpe, h, runs, c, c->m_ptrs_dev);
 }
 
 }  // namespace fused
