@@ -52,6 +52,32 @@ size_t lds_cap_pad(int static_bytes, int wg_per_cu) {
     const int want = (cap / (wg_per_cu + 1) + cap / wg_per_cu) / 2 / 256 * 256;
     return want > static_bytes ? (size_t)(want - static_bytes) : 0;
 }
+
+static const Knob* knob_find(const Knob* table, int n, const char* key) {
+    for (int i = 0; i < n; ++i)
+        if (!strcmp(table[i].key, key)) return table + i;
+    return nullptr;
+}
+
+int knob_set(const char* who, const Knob* table, int n, const char* key, int value) {
+    MX_CHECK(key, "%s: null key", who);
+    const Knob* k = knob_find(table, n, key);
+    MX_CHECK(k && !k->read_only, "%s: unknown key '%s'", who, key);
+    bool ok = true;
+    if (k->kind == Knob::kRange) ok = value >= k->v[0] && value <= k->v[1];
+    else if (k->kind == Knob::kOneOf) ok = value == k->v[0] || value == k->v[1] || value == k->v[2] || value == k->v[3];
+    else value = (k->kind == Knob::kTri && value == 2) ? 2 : (value ? 1 : 0);
+    MX_CHECK(ok, "%s: %s %d", who, key, value);
+    *k->slot = value;
+    return MX_OK;
+}
+
+int knob_get(const char* who, const Knob* table, int n, const char* key) {
+    if (!key) return MX_ERR_INVALID;
+    const Knob* k = knob_find(table, n, key);
+    MX_CHECK(k, "%s: unknown key '%s'", who, key);
+    return *k->slot;
+}
 }  // namespace mx
 
 extern "C" const char* mx_version(void) { return "matcha-gossip gfx950 0.1"; }

@@ -586,8 +586,7 @@ extern "C" int mx_mean_rows_to(const float* rows, int nrows, int64_t ld, int64_t
             const size_t pad = (int64_t)nrows * count * 4 > ((int64_t)64 << 20)
                                    ? mx::lds_cap_pad(8 * 128 * (int)sizeof(f4v), mx::g_mean_wgpc) : 0;
             // store policy: forced, or auto -- the chosen policy above 320 MB of rows, nt below
-            const int pol = mx::g_store_policy > 0 ? mx::g_store_policy
-                            : (int64_t)nrows * count * 4 > mx::kStoreAutoBytes ? mx::kStoreAutoPolicy : mx::kStoreNt;
+            const int pol = mx::store_policy_of(mx::g_store_policy, (int64_t)nrows * count * 4, mx::kStoreAutoPolicy);
 #define MX_MEAN_TILE(T, P)                                                                                    \
     hipLaunchKernelGGL((mean_tile_kernel<T, P>), dim3((unsigned)nt), dim3(256), pad, st, r4, nrows, ld / 4, d, d4, \
                        ndst, dst_ld / 4)

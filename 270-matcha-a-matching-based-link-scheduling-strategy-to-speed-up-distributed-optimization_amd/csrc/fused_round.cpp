@@ -22,54 +22,40 @@ int layout(const char* who, const int64_t* seg_len_host, int nseg, int n_slots, 
     return mx::tile_prefix(who, tile, seg_len_host, nseg, tile_off_host);
 }
 
+// the six knobs of one family's instance
+static void knobs_of(Tune& t, Knob (&k)[6]) {
+    k[0] = knob_tri("nontemporal", &t.nontemporal);
+    k[1] = knob_range("wgpc", &t.wgpc, 0, 32);
+    k[2] = knob_range("blocks_per_cu", &t.blocks_per_cu, 1, 64);
+    k[3] = knob_range("flat_small", &t.flat_small, 0, 4096);
+    k[4] = knob_range("grid", &t.grid, 0, 65536);
+    k[5] = knob_range("store_policy", &t.store_policy, 0, mx::kStoreSc1Nt);
+}
+
 int Tune::set(const char* who, const char* key, int value) {
-    MX_CHECK(key, "%s: null key", who);
-    if (!strcmp(key, "nontemporal")) {
-        nontemporal = value == 2 ? 2 : (value ? 1 : 0);
-    } else if (!strcmp(key, "wgpc")) {
-        MX_CHECK(value >= 0 && value <= 32, "%s: wgpc %d", who, value);
-        wgpc = value;
-    } else if (!strcmp(key, "blocks_per_cu")) {
-        MX_CHECK(value >= 1 && value <= 64, "%s: blocks_per_cu %d", who, value);
-        blocks_per_cu = value;
-    } else if (!strcmp(key, "flat_small")) {
-        MX_CHECK(value >= 0 && value <= 4096, "%s: flat_small %d", who, value);
-        flat_small = value;
-    } else if (!strcmp(key, "grid")) {
-        MX_CHECK(value >= 0 && value <= 65536, "%s: grid %d", who, value);
-        grid = value;
-    } else if (!strcmp(key, "store_policy")) {
-        MX_CHECK(value >= 0 && value <= mx::kStoreSc1Nt, "%s: store_policy %d", who, value);
-        store_policy = value;
-    } else {
-        MX_CHECK(false, "%s: unknown key '%s'", who, key);
-    }
-    return MX_OK;
+    Knob k[6];
+    knobs_of(*this, k);
+    return knob_set(who, k, 6, key, value);
 }
 
 int Tune::get(const char* who, const char* key) const {
-    if (!key) return MX_ERR_INVALID;
-    if (!strcmp(key, "nontemporal")) return nontemporal;
-    if (!strcmp(key, "wgpc")) return wgpc;
-    if (!strcmp(key, "blocks_per_cu")) return blocks_per_cu;
-    if (!strcmp(key, "flat_small")) return flat_small;
-    if (!strcmp(key, "grid")) return grid;
-    if (!strcmp(key, "store_policy")) return store_policy;
-    mx::set_error("%s: unknown key '%s'", who, key);
-    return MX_ERR_INVALID;
+    Knob k[6];
+    knobs_of(const_cast<Tune&>(*this), k);
+    return knob_get(who, k, 6, key);
+}
+
+// bytes the round moves
+static int64_t moved(int64_t total_tiles, int tile, int n_local, int bytes_per_elem) {
+    return total_tiles * (int64_t)tile * n_local * bytes_per_elem;
 }
 
 bool Tune::streaming(int64_t total_tiles, int tile, int n_local, int bytes_per_elem) const {
-    if (nontemporal != 2) return nontemporal != 0;
-    const int64_t ws = total_tiles * (int64_t)tile * n_local * bytes_per_elem;   // bytes the round moves
-    return ws <= ((int64_t)32 << 20) || ws > ((int64_t)320 << 20);
+    return nontemporal == 2 ? mx::streams(moved(total_tiles, tile, n_local, bytes_per_elem)) : nontemporal != 0;
 }
 
 int Tune::policy(bool nt, int64_t total_tiles, int tile, int n_local, int bytes_per_elem) const {
     if (!nt) return mx::kStorePlain;
-    if (store_policy > 0) return store_policy;
-    const int64_t ws = total_tiles * (int64_t)tile * n_local * bytes_per_elem;
-    return ws > mx::kStoreAutoBytes ? kAutoPolicy : mx::kStoreNt;
+    return mx::store_policy_of(store_policy, moved(total_tiles, tile, n_local, bytes_per_elem), kAutoPolicy);
 }
 
 int64_t Tune::grid_of(int ns, int64_t work, bool* flat) const {

@@ -183,27 +183,12 @@ extern "C" int64_t mx_grad_norm_layout(const int64_t* seg_len_host, int nseg, in
     return chunks * n_local * (int64_t)sizeof(double);
 }
 
-extern "C" int mx_grad_norm_set(const char* key, int value) {
-    MX_CHECK(key, "mx_grad_norm_set: null key");
-    if (!strcmp(key, "blocks_per_cu")) {
-        MX_CHECK(value >= 1 && value <= 64, "mx_grad_norm_set: blocks_per_cu %d", value);
-        g_tune.blocks_per_cu = value;
-    } else if (!strcmp(key, "grid")) {
-        MX_CHECK(value >= 0 && value <= 65536, "mx_grad_norm_set: grid %d", value);
-        g_tune.grid = value;
-    } else {
-        MX_CHECK(false, "mx_grad_norm_set: unknown key '%s'", key);
-    }
-    return MX_OK;
-}
+const mx::Knob kKnobs[] = {mx::knob_range("blocks_per_cu", &g_tune.blocks_per_cu, 1, 64),
+                           mx::knob_range("grid", &g_tune.grid, 0, 65536)};
 
-extern "C" int mx_grad_norm_get(const char* key) {
-    if (!key) return MX_ERR_INVALID;
-    if (!strcmp(key, "blocks_per_cu")) return g_tune.blocks_per_cu;
-    if (!strcmp(key, "grid")) return g_tune.grid;
-    mx::set_error("mx_grad_norm_get: unknown key '%s'", key);
-    return MX_ERR_INVALID;
-}
+extern "C" int mx_grad_norm_set(const char* key, int value) { return mx::knob_set("mx_grad_norm_set", kKnobs, 2, key, value); }
+
+extern "C" int mx_grad_norm_get(const char* key) { return mx::knob_get("mx_grad_norm_get", kKnobs, 2, key); }
 
 extern "C" int mx_grad_norm(const mx_grad_norm_call* c, void* stream) {
     MX_CHECK(c, "mx_grad_norm: null call record");

@@ -29,8 +29,11 @@
 #include "mx_common.h"
 #include "row_walk.h"
 
+#include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstdlib>
+#include <utility>
 #include <type_traits>
 
 namespace {
@@ -841,22 +844,6 @@ __global__ __launch_bounds__(TPB) void mix_kernel_wide(float* const* __restrict_
     }
 }
 
-struct Cfg {
-    int vec, ns;
-};
-
-int g_ns48 = 0;      // 33-48 slots: a 48-slot row-kernel class (48 KB tiles) instead of the 64-slot one
-
-Cfg pick(int n_slots) {
-    if (n_slots <= 8) return {4, 8};
-    if (n_slots <= 16) return {4, 16};
-    if (n_slots <= 32) return {2, 32};
-    if (n_slots <= 48 && g_ns48) return {1, 48};
-    if (n_slots <= 64) return {1, 64};
-    if (n_slots <= kWideMaxSlots) return {1, 0};    // wide kernel only (256-column layout tiles)
-    return {0, 0};
-}
-
 // tuning state (mx_mix_set / mx_mix_get); defaults from tools/mixtune.py sweeps on MI355X
 // (8 x 25.6M graph-0 rounds): register-indexed + non-temporal + tile stride; with global (not
 // flat) loads 2 WGs/CU beat 3 / 4 by 5-9 % (fewer concurrent DRAM streams, latency still hidden)
@@ -877,6 +864,7 @@ struct Tune {
                          // 1 = 9-64 slots only (<= 8: register-indexed / LDS-column), 0 = never
     int split = 0;       // row kernel sub-tiles per layout tile: 0 = auto (enough work items for
                          // the persistent grid), 1 / 2 / 4 = forced (capped by the geometry)
+    int ns48 = 0;        // 33-48 slots: a 48-slot row-kernel class (48 KB tiles) instead of the 64-slot one
     int wide_lds_kb = 158;  // wide kernel (65-156 slots): LDS per piece (KB); more -> wider pieces, fewer WGs per CU
     int rows_tpb = 256;     // row kernel, 32-64 slots (unsplit tiles): workgroup size 256 / 512 / 1024
     int wide_tpb = 1024;    // wide kernel: workgroup size (256 / 512 / 1024)
@@ -899,268 +887,413 @@ struct Tune {
     int spec_glds = 1;     // ... staging those tiles with LDS-DMA (global_load_lds) instead of registers
                            // (512-column sub-tiles: headline 0.2627 -> 0.2591 ms, WRN-28-10 rows
                            // 0.3792 -> 0.3712 ms; profiles/r06t_glds_ab.json)
+    const int* store_policy = &mx::g_store_policy;   // "store_policy": one setting, shared with the mean
 };
 Tune g_tune;
-
-// accesses per lane per slot per tile: the NS = 8 kernels take 1, 2 or 4 (the LDS one 1 or 2)
-int unroll_for(int ns) {
-    if (ns != 8) return 1;
-    if (!g_tune.regidx && g_tune.unroll > 2) return 2;
-    return g_tune.unroll;
-}
-
-// grid: CUs x blocks_per_cu persistent workgroups, never more than there are tiles; a single
-// segment is split into equal contiguous chunks (chunked = 1)
-inline int64_t grid_target() {
-    return g_tune.grid > 0 ? (int64_t)g_tune.grid : (int64_t)mx::cu_count() * g_tune.blocks_per_cu;
-}
-inline int64_t grid_for(int64_t total_tiles) {
-    int64_t grid = grid_target();
-    if (grid > total_tiles) grid = total_tiles;
-    return grid < 1 ? 1 : grid;
-}
-
-// 8 slots, mid-sized rows (0.4-2M params: a few work items per CU): a persistent grid of mid_bpc
-// workgroups per CU, each with its next item's loads in flight, beats one workgroup per item by 7-13 %
-// (graph-replayed rounds, tools/small_cfg.py; equal at 181k, the flat grid 1-3 % ahead from 4M on)
-inline bool rows_mid(int ns, int64_t total_tiles) {
-    return ns == 8 && g_tune.mid_bpc > 0 && g_tune.flat_small > 0 && g_tune.grid == 0 &&
-           total_tiles <= (int64_t)g_tune.mid_tiles * mx::cu_count();
-}
-
-// row kernel sub-tiles per layout tile: a sub-tile keeps >= 256 columns (one wave pass), and
-// auto picks the smallest split giving the persistent grid 1.5 work items per workgroup
-// (measured, 8 slots: 651 tiles run 11 % faster as 1302 sub-tiles, 977 tiles 5 % slower as 1954)
-int row_split(int ns, int64_t total_tiles) {
-    const int cap = ns >= 48 ? 1 : (ns == 32 ? 2 : 4);
-    if (g_tune.split > 0) return g_tune.split < cap ? g_tune.split : cap;
-    int s = 1;
-    if (rows_mid(ns, total_tiles)) {
-        while (s < cap && 2 * total_tiles * s < 3 * (int64_t)mx::cu_count() * g_tune.mid_bpc) s *= 2;
-        return s;
-    }
-    while (s < cap && 2 * total_tiles * s < 3 * grid_target()) s *= 2;
-    // with one workgroup per work item (flat_small), 512-column sub-tiles beat whole 1024-column
-    // tiles at every size measured for 8 slots (2M-36.5M params: -1 to -6 %; headline 283.8 ->
-    // 272.3 us, tools/split_sweep.py); persistent grids keep whole tiles (split 2 was slower there)
-    if (s < 2 && ns <= 16 && g_tune.flat_small > 0 && g_tune.grid == 0 &&
-        2 * total_tiles <= (int64_t)g_tune.flat_small * grid_target())
-        s = 2;
-    return s;
-}
-
-// per-call options of the row kernel's SPEC form, set by gossip_mix for the launch it dispatches
-struct RowsOpt {
-    uint64_t hint = 0;       // local rows whose tiles are loaded before the plan record arrives
-    int wg_per_cu = 0;       // SPEC launches: workgroups per CU (0 = as many as fit)
-};
-thread_local RowsOpt g_rows_opt;
 std::atomic<int64_t> g_spec_launches{0};   // SPEC launches so far (mx_mix_get "spec_launches": tests)
+int g_spec_seen = 0;                       // ... as the int mx_mix_get reads through the knob table
 
-template <int VEC, int NS, int U, bool NT, bool PF>
-int launch(float* const* seg_ptrs, const int64_t* seg_len, const int64_t* tile_off,
-           const uint8_t* seg_vec, int nseg, int n_slots, const int32_t* plan, int64_t iter, const int64_t* iter_dev,
-           int n_local, int M, float alpha, int64_t total_tiles, hipStream_t st) {
-    const int mode = ((nseg == 1 && g_tune.chunked) ? 1 : 0) | (NS >= g_tune.readlane_min ? 2 : 0);
-    hipLaunchKernelGGL((mix_kernel<VEC, NS, U, NT, PF>), dim3((unsigned)grid_for(total_tiles)), dim3(kTPB),
-                       0, st, seg_ptrs, seg_len, tile_off, seg_vec, nseg, total_tiles, n_slots, plan,
-                       iter, iter_dev, n_local, M, alpha, mode);
-    MX_LAUNCH_CHECK();
-    return MX_OK;
-}
+const mx::Knob kKnobs[] = {
+    mx::knob_range("blocks_per_cu", &g_tune.blocks_per_cu, 1, 64),
+    mx::knob_one_of("unroll", &g_tune.unroll, 1, 2, 4, 4),
+    mx::knob_tri("nontemporal", &g_tune.nontemporal),
+    mx::knob_bool("prefetch", &g_tune.prefetch),
+    mx::knob_bool("regidx", &g_tune.regidx),
+    mx::knob_bool("chunked", &g_tune.chunked),
+    mx::knob_range("grid", &g_tune.grid, 0, 65536),
+    mx::knob_range("readlane_min", &g_tune.readlane_min, 8, 128),
+    mx::knob_range("rows", &g_tune.rows, 0, 2),
+    mx::knob_one_of("split", &g_tune.split, 0, 1, 2, 4),
+    mx::knob_bool("ns48", &g_tune.ns48),
+    mx::knob_range("wide_lds_kb", &g_tune.wide_lds_kb, 8, 158),
+    mx::knob_one_of("rows_tpb", &g_tune.rows_tpb, 256, 512, 1024, 1024),
+    mx::knob_one_of("wide_tpb", &g_tune.wide_tpb, 256, 512, 1024, 1024),
+    mx::knob_range("wide_pf2", &g_tune.wide_pf2, 0, 1),
+    mx::knob_range("wide_per_cu", &g_tune.wide_per_cu, 0, 8),
+    mx::knob_range("wide_plan_lds", &g_tune.wide_plan_lds, 0, 1),
+    mx::knob_range("rows_pf2", &g_tune.rows_pf2, 0, 2),
+    mx::knob_range("flat_small", &g_tune.flat_small, 0, 4096),
+    mx::knob_range("mid_bpc", &g_tune.mid_bpc, 0, 16),
+    mx::knob_range("mid_tiles", &g_tune.mid_tiles, 0, 1024),
+    mx::knob_bool("spec", &g_tune.spec),
+    mx::knob_range("spec_wgpc", &g_tune.spec_wgpc, 0, 32),
+    mx::knob_bool("spec_glds", &g_tune.spec_glds),
+    mx::knob_range("mean_wgpc", &mx::g_mean_wgpc, 0, 32),
+    mx::knob_range("store_policy", &mx::g_store_policy, 0, mx::kStorePolicyMax),
+    mx::knob_read_only("spec_launches", &g_spec_seen),
+};
+constexpr int kNumKnobs = sizeof(kKnobs) / sizeof(kKnobs[0]);
 
-template <int NS, int TW, bool NT, int SPLIT = 1, bool PF2 = false, int TPB = kTPB, bool SPEC = false, bool GL = false,
-          int SP = NT ? mx::kStoreNt : mx::kStorePlain>
-int launch_rows(float* const* seg_ptrs, const int64_t* seg_len, const int64_t* tile_off,
-                const uint8_t* seg_vec, int nseg, int n_slots, const int32_t* plan, int64_t iter, const int64_t* iter_dev,
-                int n_local, int M, float alpha, int64_t total_tiles, hipStream_t st) {
-    const int64_t work = total_tiles * SPLIT;
-    // one workgroup per item only for 8-16 slots: with 32 / 64 slots (narrower tiles, longer partner
-    // walks) the persistent grid stays faster (ER(32): 286 vs 350 us, ER(64): 324 vs 426 us)
-    const int64_t mid = rows_mid(NS, total_tiles) ? (int64_t)mx::cu_count() * g_tune.mid_bpc : 0;
-    const int64_t grid = mid ? (work < mid ? work : mid)
-                         : (NS <= 16 && g_tune.flat_small > 0 && g_tune.grid == 0 &&
-                            work <= (int64_t)g_tune.flat_small * grid_target()) ? work : grid_for(work);
-    // SPEC launches cap the workgroups per CU (g_rows_opt.wg_per_cu) with dynamic LDS on top of
-    // the kernel's static LDS: fewer tiles in flight per CU, each issued at once
-    size_t pad = 0;
-    if (SPEC && g_rows_opt.wg_per_cu > 0) {
-        static const int stat = [] {                           // static LDS of this instantiation
-            hipFuncAttributes fa{};
-            return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(
-                       mix_kernel_rows<NS, TW, NT, SPLIT, PF2, TPB, SPEC, GL, SP>)) == hipSuccess ? (int)fa.sharedSizeBytes : 0;
-        }();
-        pad = mx::lds_cap_pad(stat, g_rows_opt.wg_per_cu);
+// Which kernel a round launches.  choose() turns the knobs and the round's shape into a Choice -- the
+// kernel family, its template coordinates and the launch geometry -- and depends on nothing else;
+// kInst names every instantiation the library contains; launch() matches the Choice against it.  A
+// new variant is two edits: its rule in choose() and its row in kInst.
+enum Family { kNone = 0, kLds, kReg, kRows, kWide };
+const char* const kFamilyName[] = {"", "mix_kernel", "mix_kernel_reg", "mix_kernel_rows", "mix_kernel_wide"};
+
+// the template coordinates of one instantiation (those its family does not use keep their defaults)
+struct Coord {
+    int family = kNone;
+    int ns = 0;        // NS (all but wide)
+    int vec = 0;       // VEC (LDS-column, wide)
+    int tw = 0;        // TW (rows)
+    int u = 1;         // U (LDS-column, register-indexed)
+    bool nt = false, pf = false;
+    int split = 1;     // SPLIT, PF2, TPB, SPEC, GL, SP (rows); TPB and PF2 also wide
+    bool pf2 = false;
+    int tpb = kTPB;
+    bool spec = false, gl = false;
+    int sp = mx::kStorePlain;
+    bool big = false, plds = false;   // BIG, PLDS (wide)
+
+    constexpr uint64_t key() const {
+        uint64_t k = (uint64_t)family;
+        k = k << 7 | (uint64_t)ns;
+        k = k << 3 | (uint64_t)vec;
+        k = k << 12 | (uint64_t)tw;
+        k = k << 3 | (uint64_t)u;
+        k = k << 3 | (uint64_t)split;
+        k = k << 11 | (uint64_t)tpb;
+        k = k << 3 | (uint64_t)sp;
+        return k << 7 | (uint64_t)(nt | pf << 1 | pf2 << 2 | spec << 3 | gl << 4 | big << 5 | plds << 6);
     }
-    hipLaunchKernelGGL((mix_kernel_rows<NS, TW, NT, SPLIT, PF2, TPB, SPEC, GL, SP>), dim3((unsigned)grid), dim3(TPB),
-                       pad, st, seg_ptrs, seg_len, tile_off, seg_vec, nseg, total_tiles, n_slots, plan,
-                       iter, iter_dev, n_local, M, alpha, g_rows_opt.hint);
+};
+
+// a launch: the instantiation and what it is launched with (the workgroup size is tpb)
+struct Choice : Coord {
+    int tile = 0;          // layout tile in columns (mx_mix_tile)
+    int64_t grid = 1;
+    size_t lds = 0;        // dynamic LDS (wide; a SPEC launch adds its pad from wgpc)
+    int wgpc = 0;          // SPEC launches: workgroups per CU (0 = as many as fit)
+    uint64_t hint = 0;     // SPEC launches: local rows whose tiles are loaded before the plan record arrives
+    int mode = 0;          // LDS-column / register-indexed: bit 0 chunked (single-segment layouts), bit 1 readlane
+};
+
+// The family: what needs only the knobs, n_slots and M (mx_mix_tile and mx_mix_kernel_name stop here).
+// kNone beyond kWideMaxSlots.
+Choice family_of(const Tune& t, int n_slots, int M) {
+    Choice c;
+    if (n_slots > kWideMaxSlots) return c;
+    const int ns = n_slots <= 8 ? 8 : n_slots <= 16 ? 16 : n_slots <= 32 ? 32
+                   : (n_slots <= 48 && t.ns48) ? 48 : n_slots <= 64 ? 64 : 0;   // 0: wide kernel only
+    const int vec = ns == 0 ? 1 : ns <= 16 ? 4 : ns == 32 ? 2 : 1;
+    // accesses per lane per slot per tile: the NS = 8 kernels take 1, 2 or 4 (the LDS one 1 or 2)
+    const int u = ns != 8 ? 1 : (!t.regidx && t.unroll > 2) ? 2 : t.unroll;
+    c.tile = vec * kTPB * u;                  // wide kernel only: 256-column tiles
+    if (ns == 0 || M > kMaxM) {               // wide kernel: > 64 slots or > 32 matchings
+        c.family = kWide;
+    } else if (t.rows && (ns >= 16 || (t.rows == 2 && u <= 2))) {
+        c.family = kRows;
+        c.ns = ns;
+    } else if (t.regidx && ns == 8) {
+        c.family = kReg;
+        c.ns = ns;
+        c.u = u;
+    } else {
+        c.family = kLds;
+        c.ns = ns == 48 ? 64 : ns;            // no 48-slot LDS-column class
+        c.vec = vec;
+        c.u = u;
+    }
+    return c;
+}
+
+Choice choose(const Tune& t, int cus, int n_slots, int n_local, int M, int64_t total_tiles, uint64_t hint) {
+    Choice c = family_of(t, n_slots, M);
+    // persistent grid: CUs x blocks_per_cu workgroups (or the forced grid), never more than there is work
+    const int64_t target = t.grid > 0 ? (int64_t)t.grid : (int64_t)cus * t.blocks_per_cu;
+    auto persistent = [&](int64_t work) { return std::max<int64_t>(1, std::min(target, work)); };
+    if (c.family == kLds || c.family == kReg) {
+        c.nt = t.nontemporal != 0;
+        c.pf = t.prefetch != 0 && (c.family == kLds || c.u == 1);
+        c.grid = persistent(total_tiles);
+        // a single segment may be split into equal contiguous chunks (launch() looks at nseg)
+        c.mode = (t.chunked ? 1 : 0) | (c.family == kLds && c.ns >= t.readlane_min ? 2 : 0);
+    } else if (c.family == kWide) {
+        // the widest piece (64 x VEC columns of every slot) within the LDS budget (default 40 KB:
+        // 4 workgroups per CU); the persistent grid as many per CU as that LDS allows (<= 4)
+        const size_t budget = (size_t)t.wide_lds_kb * 1024, slot_bytes = (size_t)n_slots * 64 * sizeof(float);
+        c.vec = 4 * slot_bytes <= budget ? 4 : 2 * slot_bytes <= budget ? 2 : 1;
+        const size_t plan_bytes = (size_t)mx::plan_words(n_local, M) * sizeof(int32_t);
+        const size_t piece_bytes = slot_bytes * c.vec;
+        auto fit = [](size_t b) { return std::min<int64_t>(4, (int64_t)((159 * 1024) / b)); };
+        // the plan goes to LDS only when it costs no workgroup per CU (occupancy beats ds_read here)
+        c.plds = t.wide_plan_lds && plan_bytes <= 32 * 1024 && piece_bytes + plan_bytes <= 158 * 1024 &&
+                 fit(piece_bytes + plan_bytes) == fit(piece_bytes);
+        c.lds = piece_bytes + (c.plds ? plan_bytes : 0);
+        c.tpb = t.wide_tpb;
+        c.pf2 = c.tpb == 1024 && t.wide_pf2;
+        c.nt = t.nontemporal != 0;
+        c.big = (c.vec == 4 && n_slots > 40) || (c.vec == 2 && n_slots > 80);
+        int64_t cap = t.wide_per_cu > 0 ? t.wide_per_cu : 4;
+        cap = std::min<int64_t>(cap, 2048 / c.tpb);   // 32 waves per CU
+        const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(cap, (int64_t)((159 * 1024) / c.lds)));
+        c.grid = std::max<int64_t>(1, std::min(cus * per_cu, total_tiles * (c.tile / (64 * c.vec))));
+    } else if (c.family == kRows) {
+        const int ns = c.ns;
+        // auto: rows of 32-320 MB (about the 256 MB Infinity Cache) keep ordinary (cacheable)
+        // accesses -- back-to-back rounds then find them on die (8 x 2M params 25.1 -> 23.7 us,
+        // 8 x 8M 90.3 -> 75.2 us, 8 x 10M 111.5 -> 107.7 us); above, the streaming hints win
+        // (8 x 12M 138.9 -> 130.8 us, headline 294 -> 272 us), and below, where the rows fit in the
+        // L2s, too (8 x 181k / 666k: 5-7 % slower with ordinary accesses; tools/sessions/r2_s80.sh)
+        const int64_t ws = total_tiles * (int64_t)c.tile * n_slots * 4;
+        c.nt = t.nontemporal == 2 ? mx::streams(ws) : t.nontemporal != 0;
+        // store policy of the streaming (nt) 8- and 16-slot launches: forced, or auto -- the chosen
+        // policy above 320 MB, nt below (rows that fit the L2s rely on finding their lines again)
+        c.sp = !c.nt ? mx::kStorePlain
+               : ns <= 16 ? mx::store_policy_of(*t.store_policy, ws, mx::kStoreAutoPolicy) : mx::kStoreNt;
+        // one workgroup per work item only for 8-16 slots: with 32 / 64 slots (narrower tiles, longer partner
+        // walks) the persistent grid stays faster (ER(32): 286 vs 350 us, ER(64): 324 vs 426 us)
+        const bool may_flat = ns <= 16 && t.flat_small > 0 && t.grid == 0;
+        auto fits_flat = [&](int64_t work) { return may_flat && work <= (int64_t)t.flat_small * target; };
+        // 8 slots, mid-sized rows (0.4-2M params: a few work items per CU): a persistent grid of mid_bpc
+        // workgroups per CU, each with its next item's loads in flight, beats one workgroup per item by 7-13 %
+        // (graph-replayed rounds, tools/small_cfg.py; equal at 181k, the flat grid 1-3 % ahead from 4M on)
+        const int64_t mid_grid = (int64_t)cus * t.mid_bpc;
+        const bool mid = may_flat && ns == 8 && t.mid_bpc > 0 && total_tiles <= (int64_t)t.mid_tiles * cus;
+        // sub-tiles per layout tile: a sub-tile keeps >= 256 columns (one wave pass), and auto picks
+        // the smallest split giving the persistent grid 1.5 work items per workgroup (measured, 8
+        // slots: 651 tiles run 11 % faster as 1302 sub-tiles, 977 tiles 5 % slower as 1954); the
+        // two-access 8-slot form (2048-column tiles) is never split
+        const int cap = (ns >= 48 || c.tile == 2048) ? 1 : ns == 32 ? 2 : 4;
+        int s = 1;
+        if (t.split > 0) {
+            s = std::min(t.split, cap);
+        } else {
+            while (s < cap && 2 * total_tiles * s < 3 * (mid ? mid_grid : target)) s *= 2;
+            // with one workgroup per work item (flat_small), 512-column sub-tiles beat whole 1024-column
+            // tiles at every size measured for 8 slots (2M-36.5M params: -1 to -6 %; headline 283.8 ->
+            // 272.3 us, tools/split_sweep.py); persistent grids keep whole tiles (split 2 was slower there)
+            if (!mid && s < 2 && cap >= 2 && fits_flat(2 * total_tiles)) s = 2;
+        }
+        c.split = s;
+        c.tw = c.tile / s;
+        const int64_t work = total_tiles * s;
+        const bool flat = !mid && fits_flat(work);
+        c.grid = mid ? std::min(work, mid_grid) : flat ? work : persistent(work);
+        if (ns >= 32) {
+            // unsplit tiles take the rows_tpb workgroup size; PF2 as the knob says (auto: at most 5/8
+            // of the class's slots staged)
+            if (s == 1) c.tpb = t.rows_tpb;
+            c.pf2 = t.rows_pf2 == 1 || (t.rows_pf2 == 2 && 8 * n_slots <= 5 * ns);
+        }
+        // SPEC (knob "spec"): a round whose local active rows the caller passed (hint, from the
+        // host's copy of the flags: mx_gossip_mix_packed) loads their first tile before the plan
+        // record arrives, at spec_wgpc workgroups per CU -- 8-slot rounds of > 64 MB on the flat
+        // grid with streaming hints (auto hints: > 320 MB; 8 x 14.8M-60M params: -0.5 to -3.5 %,
+        // the headline 0.2700 -> 0.2637 ms; neutral at 8 x 4M; tools/occ_sweep.py, profiles/r06t_*)
+        // only when every slot is a local row: receive slots (RCCL slab, or a peer's HBM under the
+        // pull transport, read over xGMI) keep the uncapped launch measured at N > 1
+        if (ns == 8 && c.tile == 1024 && c.nt && hint && t.spec && flat && n_slots == n_local &&
+            ws > ((int64_t)64 << 20)) {
+            c.spec = true;
+            c.gl = t.spec_glds && s == 2;
+            c.hint = hint;
+            c.wgpc = t.spec_wgpc;
+        }
+    }
+    return c;
+}
+
+struct Args {
+    float* const* seg_ptrs;
+    const int64_t* seg_len;
+    const int64_t* tile_off;
+    const uint8_t* seg_vec;
+    int nseg, n_slots;
+    const int32_t* plan;
+    int64_t iter;
+    const int64_t* iter_dev;
+    int n_local, M;
+    float alpha;
+    int64_t total_tiles;
+    hipStream_t st;
+};
+
+constexpr Coord lds_inst(int vec, int ns, int u, bool nt, bool pf) {
+    Coord c{};
+    c.family = kLds, c.vec = vec, c.ns = ns, c.u = u, c.nt = nt, c.pf = pf;
+    return c;
+}
+constexpr Coord reg_inst(int u, bool nt, bool pf) {
+    Coord c{};
+    c.family = kReg, c.ns = 8, c.u = u, c.nt = nt, c.pf = pf;
+    return c;
+}
+constexpr Coord rows_inst(int ns, int tw, int split, bool nt, int sp, bool pf2 = false, int tpb = kTPB,
+                          bool spec = false, bool gl = false) {
+    Coord c{};
+    c.family = kRows, c.ns = ns, c.tw = tw, c.split = split, c.nt = nt, c.sp = sp, c.pf2 = pf2, c.tpb = tpb;
+    c.spec = spec, c.gl = gl;
+    return c;
+}
+constexpr Coord wide_inst(int vec, bool big, bool nt, bool plds, int tpb, bool pf2) {
+    Coord c{};
+    c.family = kWide, c.vec = vec, c.big = big, c.nt = nt, c.plds = plds, c.tpb = tpb, c.pf2 = pf2;
+    return c;
+}
+
+// Every instantiation in the library, each once; run<I> below builds the I-th.
+struct InstTable {
+    Coord row[208];
+    uint64_t key[208] = {};
+    int n = 0;
+    constexpr void add(const Coord& c) {
+        row[n] = c;
+        key[n] = c.key();
+        ++n;
+    }
+};
+constexpr InstTable kInst = [] {
+    InstTable t;
+    constexpr bool both[] = {false, true};
+    // rows, 8 / 16 slots {NS, TW, SPLIT}: ordinary accesses, or streaming under each store policy
+    constexpr int small[][3] = {{8, 1024, 1}, {8, 512, 2}, {8, 256, 4}, {8, 2048, 1}, {16, 1024, 1}, {16, 512, 2}, {16, 256, 4}};
+    // ... SPEC forms {TW, SPLIT, GL} of the 8-slot ones: streaming only
+    constexpr int spec[][3] = {{1024, 1, 0}, {512, 2, 0}, {512, 2, 1}, {256, 4, 0}};
+    for (auto& s : small) t.add(rows_inst(s[0], s[1], s[2], false, mx::kStorePlain));
+    for (int sp = mx::kStoreNt; sp <= mx::kStorePolicyMax; ++sp) {
+        for (auto& s : small) t.add(rows_inst(s[0], s[1], s[2], true, sp));
+        for (auto& s : spec) t.add(rows_inst(8, s[0], s[1], true, sp, false, kTPB, true, s[2] != 0));
+    }
+    // rows, 32-64 slots {NS, TW}: hints and PF2 free; unsplit at each workgroup size, 32 slots also split in two
+    constexpr int large[][2] = {{32, 512}, {48, 256}, {64, 256}};
+    for (bool nt : both)
+        for (bool pf2 : both) {
+            const int sp = nt ? mx::kStoreNt : mx::kStorePlain;
+            for (auto& l : large)
+                for (int tpb = 256; tpb <= 1024; tpb *= 2) t.add(rows_inst(l[0], l[1], 1, nt, sp, pf2, tpb));
+            t.add(rows_inst(32, 256, 2, nt, sp, pf2));
+        }
+    // wide {VEC, BIG} x {TPB, PF2}: hints and PLDS free
+    constexpr int wide[][2] = {{4, 0}, {4, 1}, {2, 0}, {2, 1}, {1, 0}};
+    constexpr int wg[][2] = {{1024, 1}, {1024, 0}, {512, 0}, {256, 0}};
+    for (auto& w : wide)
+        for (auto& g : wg)
+            for (bool nt : both)
+                for (bool plds : both) t.add(wide_inst(w[0], w[1] != 0, nt, plds, g[0], g[1] != 0));
+    // LDS-column {VEC, NS, U} and register-indexed {U}: hints and prefetch free (the latter: U = 1 only)
+    constexpr int lds[][3] = {{4, 8, 1}, {4, 8, 2}, {4, 16, 1}, {2, 32, 1}, {1, 64, 1}};
+    for (bool nt : both)
+        for (bool pf : both) {
+            for (auto& l : lds) t.add(lds_inst(l[0], l[1], l[2], nt, pf));
+            for (int u = 1; u <= 4; u *= 2)
+                if (!pf || u == 1) t.add(reg_inst(u, nt, pf));
+        }
+    return t;
+}();
+static_assert(kInst.n == 199, "91 rows + 80 wide + 20 LDS-column + 8 register-indexed kernels");
+
+template <size_t I>
+int run(const Choice& c, const Args& a) {
+    constexpr Coord k = kInst.row[I];
+    const dim3 grid((unsigned)c.grid), block((unsigned)k.tpb);
+    if constexpr (k.family == kRows) {
+        constexpr auto kern = &mix_kernel_rows<k.ns, k.tw, k.nt, k.split, k.pf2, k.tpb, k.spec, k.gl, k.sp>;
+        // SPEC launches cap the workgroups per CU (wgpc) with dynamic LDS on top of the kernel's
+        // static LDS: fewer tiles in flight per CU, each issued at once
+        size_t pad = 0;
+        if constexpr (k.spec) {
+            if (c.wgpc > 0) {
+                static const int stat = [] {                       // static LDS of this instantiation
+                    hipFuncAttributes fa{};
+                    return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern)) == hipSuccess
+                               ? (int)fa.sharedSizeBytes : 0;
+                }();
+                pad = mx::lds_cap_pad(stat, c.wgpc);
+            }
+        }
+        hipLaunchKernelGGL(kern, grid, block, pad, a.st, a.seg_ptrs, a.seg_len, a.tile_off, a.seg_vec, a.nseg,
+                           a.total_tiles, a.n_slots, a.plan, a.iter, a.iter_dev, a.n_local, a.M, a.alpha, c.hint);
+    } else if constexpr (k.family == kWide) {
+        constexpr auto kern = &mix_kernel_wide<k.vec, k.nt, k.big, k.plds, k.tpb, k.pf2>;
+        static bool big_lds = false;          // once per instantiation: the most the kernel may ask
+        if (c.lds > 64 * 1024 && !big_lds) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);
+            big_lds = true;
+        }
+        hipLaunchKernelGGL(kern, grid, block, c.lds, a.st, a.seg_ptrs, a.seg_len, a.tile_off, a.seg_vec, a.nseg,
+                           a.total_tiles, c.tile, a.n_slots, a.plan, a.iter, a.iter_dev, a.n_local, a.M, a.alpha);
+    } else {
+        const int mode = c.mode & (a.nseg == 1 ? 3 : 2);
+        if constexpr (k.family == kLds)
+            hipLaunchKernelGGL((mix_kernel<k.vec, k.ns, k.u, k.nt, k.pf>), grid, block, 0, a.st, a.seg_ptrs, a.seg_len,
+                               a.tile_off, a.seg_vec, a.nseg, a.total_tiles, a.n_slots, a.plan, a.iter, a.iter_dev,
+                               a.n_local, a.M, a.alpha, mode);
+        else
+            hipLaunchKernelGGL((mix_kernel_reg<k.ns, k.u, k.nt, k.pf>), grid, block, 0, a.st, a.seg_ptrs, a.seg_len,
+                               a.tile_off, a.seg_vec, a.nseg, a.total_tiles, a.n_slots, a.plan, a.iter, a.iter_dev,
+                               a.n_local, a.M, a.alpha, mode);
+    }
     MX_LAUNCH_CHECK();
     return MX_OK;
 }
 
-template <int NS, int U, bool NT, bool PF>
-int launch_reg(float* const* seg_ptrs, const int64_t* seg_len, const int64_t* tile_off,
-               const uint8_t* seg_vec, int nseg, int n_slots, const int32_t* plan, int64_t iter, const int64_t* iter_dev,
-               int n_local, int M, float alpha, int64_t total_tiles, hipStream_t st) {
-    hipLaunchKernelGGL((mix_kernel_reg<NS, U, NT, PF>), dim3((unsigned)grid_for(total_tiles)), dim3(kTPB),
-                       0, st, seg_ptrs, seg_len, tile_off, seg_vec, nseg, total_tiles, n_slots, plan,
-                       iter, iter_dev, n_local, M, alpha, (nseg == 1 && g_tune.chunked) ? 1 : 0);
-    MX_LAUNCH_CHECK();
-    return MX_OK;
+template <size_t... I>
+constexpr std::array<int (*)(const Choice&, const Args&), sizeof...(I)> runners(std::index_sequence<I...>) {
+    return {{&run<I>...}};
+}
+constexpr auto kRun = runners(std::make_index_sequence<kInst.n>{});
+
+// the Choice's instantiation, launched; a Choice the library does not contain is an error
+int launch(const Choice& c, const Args& a) {
+    const uint64_t key = c.key();
+    for (int i = 0; i < kInst.n; ++i)
+        if (kInst.key[i] == key) return kRun[i](c, a);
+    MX_CHECK(false, "mx_gossip_mix: no %s<ns=%d vec=%d tw=%d u=%d nt=%d pf=%d split=%d pf2=%d tpb=%d spec=%d gl=%d "
+             "sp=%d big=%d plds=%d> in this library", kFamilyName[c.family], c.ns, c.vec, c.tw, c.u, c.nt, c.pf, c.split,
+             c.pf2, c.tpb, c.spec, c.gl, c.sp, c.big, c.plds);
 }
 
+int gossip_mix(float* const* seg_ptrs_dev, const int64_t* seg_len_dev, const int64_t* tile_off_dev,
+               const uint8_t* seg_vec_dev, int nseg, int64_t total_tiles, int n_slots, const int32_t* plan_dev,
+               int64_t iter, const int64_t* iter_dev, int n_local, int M, float alpha, void* stream,
+               uint64_t hint = 0) {
+    MX_CHECK(seg_ptrs_dev && seg_len_dev && tile_off_dev && seg_vec_dev && plan_dev,
+             "mx_gossip_mix: null pointer");
+    MX_CHECK(nseg >= 1 && n_local >= 1 && n_slots >= n_local, "mx_gossip_mix: nseg=%d n_local=%d n_slots=%d",
+             nseg, n_local, n_slots);
+    MX_CHECK(M >= 1, "mx_gossip_mix: M=%d", M);
+    MX_CHECK(iter >= 0, "mx_gossip_mix: iter < 0");
+    const Choice c = choose(g_tune, mx::cu_count(), n_slots, n_local, M, total_tiles, hint);
+    MX_CHECK(c.family != kNone, "mx_gossip_mix: n_slots=%d exceeds %d", n_slots, kWideMaxSlots);
+    if (total_tiles <= 0) return MX_OK;
+    MX_CHECK(c.lds <= 158 * 1024, "mx_gossip_mix: wide kernel LDS %zu", c.lds);
+    if (c.spec) ++g_spec_launches;
+    return launch(c, Args{seg_ptrs_dev, seg_len_dev, tile_off_dev, seg_vec_dev, nseg, n_slots, plan_dev, iter, iter_dev,
+                          n_local, M, alpha, total_tiles, mx::as_stream(stream)});
+}
+
+__global__ void advance_kernel(int64_t* it, int64_t by) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) it[0] += by;
+}
+
+__global__ void expand_kernel(int64_t* it, int64_t* ctrs, int n) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int64_t base = it[0];
+    for (int j = 0; j < n; ++j) ctrs[j] = base + j;
+    it[0] = base + n;
+}
 }  // namespace
 
-extern "C" int mx_mix_tile(int n_slots) {
-    const Cfg c = pick(n_slots);
-    if (c.vec > 0 && c.ns == 0) return kTPB;           // wide kernel: 256-column tiles
-    return c.vec * kTPB * unroll_for(c.ns);
-}
+extern "C" int mx_mix_tile(int n_slots) { return family_of(g_tune, n_slots, 1).tile; }
 
-extern "C" int mx_mix_set(const char* key, int value) {
-    MX_CHECK(key, "mx_mix_set: null key");
-    int* slot = nullptr;
-    if (!strcmp(key, "blocks_per_cu")) {
-        MX_CHECK(value >= 1 && value <= 64, "mx_mix_set: blocks_per_cu %d", value);
-        slot = &g_tune.blocks_per_cu;
-    } else if (!strcmp(key, "unroll")) {
-        MX_CHECK(value == 1 || value == 2 || value == 4, "mx_mix_set: unroll %d", value);
-        slot = &g_tune.unroll;
-    } else if (!strcmp(key, "nontemporal")) {
-        slot = &g_tune.nontemporal;
-        value = value == 2 ? 2 : (value ? 1 : 0);
-    } else if (!strcmp(key, "prefetch")) {
-        slot = &g_tune.prefetch;
-        value = value ? 1 : 0;
-    } else if (!strcmp(key, "regidx")) {
-        slot = &g_tune.regidx;
-        value = value ? 1 : 0;
-    } else if (!strcmp(key, "readlane_min")) {
-        MX_CHECK(value >= 8 && value <= 128, "mx_mix_set: readlane_min %d", value);
-        slot = &g_tune.readlane_min;
-    } else if (!strcmp(key, "grid")) {
-        MX_CHECK(value >= 0 && value <= 65536, "mx_mix_set: grid %d", value);
-        slot = &g_tune.grid;
-    } else if (!strcmp(key, "chunked")) {
-        slot = &g_tune.chunked;
-        value = value ? 1 : 0;
-    } else if (!strcmp(key, "rows")) {
-        MX_CHECK(value >= 0 && value <= 2, "mx_mix_set: rows %d", value);
-        slot = &g_tune.rows;
-    } else if (!strcmp(key, "split")) {
-        MX_CHECK(value == 0 || value == 1 || value == 2 || value == 4, "mx_mix_set: split %d", value);
-        slot = &g_tune.split;
-    } else if (!strcmp(key, "wide_lds_kb")) {
-        MX_CHECK(value >= 8 && value <= 158, "mx_mix_set: wide_lds_kb %d", value);
-        slot = &g_tune.wide_lds_kb;
-    } else if (!strcmp(key, "rows_tpb")) {
-        MX_CHECK(value == 256 || value == 512 || value == 1024, "mx_mix_set: rows_tpb %d", value);
-        slot = &g_tune.rows_tpb;
-    } else if (!strcmp(key, "wide_pf2")) {
-        MX_CHECK(value == 0 || value == 1, "mx_mix_set: wide_pf2 %d", value);
-        slot = &g_tune.wide_pf2;
-    } else if (!strcmp(key, "wide_tpb")) {
-        MX_CHECK(value == 256 || value == 512 || value == 1024, "mx_mix_set: wide_tpb %d", value);
-        slot = &g_tune.wide_tpb;
-    } else if (!strcmp(key, "wide_per_cu")) {
-        MX_CHECK(value >= 0 && value <= 8, "mx_mix_set: wide_per_cu %d", value);
-        slot = &g_tune.wide_per_cu;
-    } else if (!strcmp(key, "wide_plan_lds")) {
-        MX_CHECK(value == 0 || value == 1, "mx_mix_set: wide_plan_lds %d", value);
-        slot = &g_tune.wide_plan_lds;
-    } else if (!strcmp(key, "rows_pf2")) {
-        MX_CHECK(value >= 0 && value <= 2, "mx_mix_set: rows_pf2 %d", value);
-        slot = &g_tune.rows_pf2;
-    } else if (!strcmp(key, "mid_bpc")) {
-        MX_CHECK(value >= 0 && value <= 16, "mx_mix_set: mid_bpc %d", value);
-        slot = &g_tune.mid_bpc;
-    } else if (!strcmp(key, "mid_tiles")) {
-        MX_CHECK(value >= 0 && value <= 1024, "mx_mix_set: mid_tiles %d", value);
-        slot = &g_tune.mid_tiles;
-
-    } else if (!strcmp(key, "spec")) {
-        slot = &g_tune.spec;
-        value = value ? 1 : 0;
-    } else if (!strcmp(key, "spec_glds")) {
-        slot = &g_tune.spec_glds;
-        value = value ? 1 : 0;
-    } else if (!strcmp(key, "spec_wgpc")) {
-        MX_CHECK(value >= 0 && value <= 32, "mx_mix_set: spec_wgpc %d", value);
-        slot = &g_tune.spec_wgpc;
-    } else if (!strcmp(key, "mean_wgpc")) {
-        MX_CHECK(value >= 0 && value <= 32, "mx_mix_set: mean_wgpc %d", value);
-        slot = &mx::g_mean_wgpc;
-    } else if (!strcmp(key, "store_policy")) {
-        MX_CHECK(value >= 0 && value <= mx::kStorePolicyMax, "mx_mix_set: store_policy %d", value);
-        slot = &mx::g_store_policy;
-    } else if (!strcmp(key, "flat_small")) {
-        MX_CHECK(value >= 0 && value <= 4096, "mx_mix_set: flat_small %d", value);
-        slot = &g_tune.flat_small;
-    } else if (!strcmp(key, "ns48")) {
-        slot = &g_ns48;
-        value = value ? 1 : 0;
-    }
-    MX_CHECK(slot, "mx_mix_set: unknown key '%s'", key);
-    *slot = value;
-    return MX_OK;
-}
+extern "C" int mx_mix_set(const char* key, int value) { return mx::knob_set("mx_mix_set", kKnobs, kNumKnobs, key, value); }
 
 extern "C" int mx_mix_get(const char* key) {
-    if (!key) return MX_ERR_INVALID;
-    if (!strcmp(key, "blocks_per_cu")) return g_tune.blocks_per_cu;
-    if (!strcmp(key, "unroll")) return g_tune.unroll;
-    if (!strcmp(key, "nontemporal")) return g_tune.nontemporal;
-    if (!strcmp(key, "prefetch")) return g_tune.prefetch;
-    if (!strcmp(key, "regidx")) return g_tune.regidx;
-    if (!strcmp(key, "chunked")) return g_tune.chunked;
-    if (!strcmp(key, "grid")) return g_tune.grid;
-    if (!strcmp(key, "readlane_min")) return g_tune.readlane_min;
-    if (!strcmp(key, "rows")) return g_tune.rows;
-    if (!strcmp(key, "split")) return g_tune.split;
-    if (!strcmp(key, "flat_small")) return g_tune.flat_small;
-    if (!strcmp(key, "spec")) return g_tune.spec;
-    if (!strcmp(key, "spec_wgpc")) return g_tune.spec_wgpc;
-    if (!strcmp(key, "spec_glds")) return g_tune.spec_glds;
-    if (!strcmp(key, "mean_wgpc")) return mx::g_mean_wgpc;
-    if (!strcmp(key, "store_policy")) return mx::g_store_policy;
-    if (!strcmp(key, "spec_launches")) return (int)(g_spec_launches.load() & 0x7fffffff);
-    if (!strcmp(key, "mid_bpc")) return g_tune.mid_bpc;
-    if (!strcmp(key, "mid_tiles")) return g_tune.mid_tiles;
-    if (!strcmp(key, "rows_pf2")) return g_tune.rows_pf2;
-    if (!strcmp(key, "wide_lds_kb")) return g_tune.wide_lds_kb;
-    if (!strcmp(key, "wide_plan_lds")) return g_tune.wide_plan_lds;
-    if (!strcmp(key, "wide_per_cu")) return g_tune.wide_per_cu;
-    if (!strcmp(key, "wide_tpb")) return g_tune.wide_tpb;
-    if (!strcmp(key, "wide_pf2")) return g_tune.wide_pf2;
-    if (!strcmp(key, "rows_tpb")) return g_tune.rows_tpb;
-    if (!strcmp(key, "ns48")) return g_ns48;
-    mx::set_error("mx_mix_get: unknown key '%s'", key);
-    return MX_ERR_INVALID;
+    g_spec_seen = (int)(g_spec_launches.load() & 0x7fffffff);
+    return mx::knob_get("mx_mix_get", kKnobs, kNumKnobs, key);
 }
 
-// mirrors mx_gossip_mix's dispatch (for M <= 32 matchings; more always take mix_kernel_wide)
-extern "C" const char* mx_mix_kernel_name(int n_slots) {
-    const Cfg c = pick(n_slots);
-    if (c.vec == 0) return "";
-    if (c.ns == 0) return "mix_kernel_wide";
-    if ((g_tune.rows && c.ns >= 16) || (g_tune.rows == 2 && unroll_for(8) <= 2)) return "mix_kernel_rows";
-    if (g_tune.regidx && c.ns == 8) return "mix_kernel_reg";
-    return "mix_kernel";
-}
+// the family mx_gossip_mix launches for M <= 32 matchings (more always take mix_kernel_wide)
+extern "C" const char* mx_mix_kernel_name(int n_slots) { return kFamilyName[family_of(g_tune, n_slots, 1).family]; }
 
 extern "C" int mx_mix_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host) {
     MX_CHECK(seg_len_host && tile_off_host && nseg >= 1, "mx_mix_layout: bad arguments");
     const int tile = mx_mix_tile(n_slots);
     MX_CHECK(tile > 0, "mx_mix_layout: n_slots=%d exceeds %d", n_slots, kWideMaxSlots);
     return mx::tile_prefix("mx_mix_layout", tile, seg_len_host, nseg, tile_off_host);
-}
-
-namespace {
-int gossip_mix(float* const* seg_ptrs_dev, const int64_t* seg_len_dev, const int64_t* tile_off_dev,
-               const uint8_t* seg_vec_dev, int nseg, int64_t total_tiles, int n_slots, const int32_t* plan_dev,
-               int64_t iter, const int64_t* iter_dev, int n_local, int M, float alpha, void* stream,
-               uint64_t hint = 0);
 }
 
 extern "C" int mx_gossip_mix(float* const* seg_ptrs_dev, const int64_t* seg_len_dev,
@@ -1190,21 +1323,6 @@ extern "C" int mx_gossip_mix_at(float* const* seg_ptrs_dev, const int64_t* seg_l
                       n_iters, iter_dev, n_local, M, alpha, stream);
 }
 
-namespace {
-__global__ void advance_kernel(int64_t* it, int64_t by) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) it[0] += by;
-}
-}  // namespace
-
-namespace {
-__global__ void expand_kernel(int64_t* it, int64_t* ctrs, int n) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int64_t base = it[0];
-    for (int j = 0; j < n; ++j) ctrs[j] = base + j;
-    it[0] = base + n;
-}
-}  // namespace
-
 // K graph-replayable rounds for one launch of bookkeeping: ctrs[j] = *iter_dev + j, then
 // *iter_dev += n; the K mixing launches that follow read ctrs[0..K-1] (one counter each).
 extern "C" int mx_iter_expand(int64_t* iter_dev, int64_t* ctrs, int n, void* stream) {
@@ -1220,182 +1338,3 @@ extern "C" int mx_iter_advance(int64_t* iter_dev, int64_t by, void* stream) {
     MX_LAUNCH_CHECK();
     return MX_OK;
 }
-
-namespace {
-int gossip_mix(float* const* seg_ptrs_dev, const int64_t* seg_len_dev, const int64_t* tile_off_dev,
-               const uint8_t* seg_vec_dev, int nseg, int64_t total_tiles, int n_slots, const int32_t* plan_dev,
-               int64_t iter, const int64_t* iter_dev, int n_local, int M, float alpha, void* stream,
-               uint64_t hint) {
-    MX_CHECK(seg_ptrs_dev && seg_len_dev && tile_off_dev && seg_vec_dev && plan_dev,
-             "mx_gossip_mix: null pointer");
-    MX_CHECK(nseg >= 1 && n_local >= 1 && n_slots >= n_local, "mx_gossip_mix: nseg=%d n_local=%d n_slots=%d",
-             nseg, n_local, n_slots);
-    MX_CHECK(M >= 1, "mx_gossip_mix: M=%d", M);
-    MX_CHECK(iter >= 0, "mx_gossip_mix: iter < 0");
-    const Cfg c = pick(n_slots);
-    MX_CHECK(c.vec > 0, "mx_gossip_mix: n_slots=%d exceeds %d", n_slots, kWideMaxSlots);
-    hipStream_t st = mx::as_stream(stream);
-    if (total_tiles <= 0) return MX_OK;
-    if (c.ns == 0 || M > kMaxM) {             // wide kernel: > 64 slots or > 32 matchings
-        const int tile_cols = mx_mix_tile(n_slots);
-        // the widest piece (64 x VEC columns of every slot) within the LDS budget (default 40 KB:
-        // 4 workgroups per CU); the persistent grid as many per CU as that LDS allows (<= 4)
-        const size_t budget = (size_t)g_tune.wide_lds_kb * 1024;
-        int vec = 1;
-        if ((size_t)n_slots * 64 * 4 * sizeof(float) <= budget) vec = 4;
-        else if ((size_t)n_slots * 64 * 2 * sizeof(float) <= budget) vec = 2;
-        const size_t plan_bytes = (size_t)mx::plan_words(n_local, M) * sizeof(int32_t);
-        const size_t piece_bytes = (size_t)n_slots * 64 * vec * sizeof(float);
-        auto fit = [](size_t b) { return std::min<int64_t>(4, (int64_t)((159 * 1024) / b)); };
-        // the plan goes to LDS only when it costs no workgroup per CU (occupancy beats ds_read here)
-        const bool plds = g_tune.wide_plan_lds && plan_bytes <= 32 * 1024 &&
-                          piece_bytes + plan_bytes <= 158 * 1024 && fit(piece_bytes + plan_bytes) == fit(piece_bytes);
-        const size_t lds = (size_t)n_slots * 64 * vec * sizeof(float) + (plds ? plan_bytes : 0);
-        MX_CHECK(lds <= 158 * 1024, "mx_gossip_mix: wide kernel LDS %zu", lds);
-        const int tpb = g_tune.wide_tpb;
-        int64_t per_cu = (int64_t)((159 * 1024) / lds);
-        int64_t cap = g_tune.wide_per_cu > 0 ? g_tune.wide_per_cu : 4;
-        if (cap > 2048 / tpb) cap = 2048 / tpb;  // 32 waves per CU
-        per_cu = per_cu > cap ? cap : per_cu < 1 ? 1 : per_cu;
-        int64_t grid = (int64_t)mx::cu_count() * per_cu;
-        const int64_t work = total_tiles * (tile_cols / (64 * vec));
-        if (grid > work) grid = work;
-        const bool nt = g_tune.nontemporal != 0;
-        const bool big = (vec == 4 && n_slots > 40) || (vec == 2 && n_slots > 80);
-        MX_CHECK(n_slots <= (big || vec == 1 ? kWideMaxSlots : vec == 4 ? 40 : 80), "mx_gossip_mix: wide staging");
-#define MX_WIDE1(V, N, B, PL, T, F2)                                                                           \
-    do {                                                                                                      \
-        static bool big_lds = false;          /* once per instantiation: the most the kernel may ask */   \
-        if (lds > 64 * 1024 && !big_lds) {                                                                    \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mix_kernel_wide<V, N, B, PL, T, F2>),     \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);               \
-            big_lds = true;                                                                                   \
-        }                                                                                                     \
-        hipLaunchKernelGGL((mix_kernel_wide<V, N, B, PL, T, F2>), dim3((unsigned)(grid < 1 ? 1 : grid)),      \
-                           dim3(T), lds, st, seg_ptrs_dev, seg_len_dev, tile_off_dev, seg_vec_dev, nseg,      \
-                           total_tiles, tile_cols, n_slots, plan_dev, iter, iter_dev, n_local, M, alpha);     \
-    } while (0)
-#define MX_WIDE2(V, N, B, PL)                                                                                 \
-    do {                                                                                                      \
-        if (tpb == 1024 && g_tune.wide_pf2) MX_WIDE1(V, N, B, PL, 1024, true);                               \
-        else if (tpb == 1024) MX_WIDE1(V, N, B, PL, 1024, false);                                            \
-        else if (tpb == 512) MX_WIDE1(V, N, B, PL, 512, false);                                              \
-        else MX_WIDE1(V, N, B, PL, 256, false);                                                              \
-    } while (0)
-#define MX_WIDE(V, N, B)                                                                                      \
-    do {                                                                                                      \
-        if (plds) MX_WIDE2(V, N, B, true); else MX_WIDE2(V, N, B, false);                                     \
-    } while (0)
-        if (vec == 4 && big) { if (nt) MX_WIDE(4, true, true); else MX_WIDE(4, false, true); }
-        else if (vec == 4) { if (nt) MX_WIDE(4, true, false); else MX_WIDE(4, false, false); }
-        else if (vec == 2 && big) { if (nt) MX_WIDE(2, true, true); else MX_WIDE(2, false, true); }
-        else if (vec == 2) { if (nt) MX_WIDE(2, true, false); else MX_WIDE(2, false, false); }
-        else { if (nt) MX_WIDE(1, true, false); else MX_WIDE(1, false, false); }
-#undef MX_WIDE
-#undef MX_WIDE2
-#undef MX_WIDE1
-        MX_LAUNCH_CHECK();
-        return MX_OK;
-    }
-    const int key = (g_tune.nontemporal ? 1 : 0) | (g_tune.prefetch ? 2 : 0);
-#define MX_ARGS seg_ptrs_dev, seg_len_dev, tile_off_dev, seg_vec_dev, nseg, n_slots, plan_dev, iter, \
-                iter_dev, n_local, M, alpha, total_tiles, st
-#define MX_DISPATCH(V, N, U)                                                  \
-    switch (key) {                                                            \
-        case 0: return launch<V, N, U, false, false>(MX_ARGS);                \
-        case 1: return launch<V, N, U, true, false>(MX_ARGS);                 \
-        case 2: return launch<V, N, U, false, true>(MX_ARGS);                 \
-        default: return launch<V, N, U, true, true>(MX_ARGS);                 \
-    }
-#define MX_DISPATCH_REG(N, U)                                                 \
-    switch (key) {                                                            \
-        case 0: return launch_reg<N, U, false, false>(MX_ARGS);               \
-        case 1: return launch_reg<N, U, true, false>(MX_ARGS);                \
-        case 2: return launch_reg<N, U, false, U == 1>(MX_ARGS);              \
-        default: return launch_reg<N, U, true, U == 1>(MX_ARGS);              \
-    }
-    if ((g_tune.rows && c.ns >= 16) || (g_tune.rows == 2 && unroll_for(8) <= 2)) {
-        // auto: rows of 32-320 MB (about the 256 MB Infinity Cache) keep ordinary (cacheable)
-        // accesses -- back-to-back rounds then find them on die (8 x 2M params 25.1 -> 23.7 us,
-        // 8 x 8M 90.3 -> 75.2 us, 8 x 10M 111.5 -> 107.7 us); above, the streaming hints win
-        // (8 x 12M 138.9 -> 130.8 us, headline 294 -> 272 us), and below, where the rows fit in the
-        // L2s, too (8 x 181k / 666k: 5-7 % slower with ordinary accesses; tools/sessions/r2_s80.sh)
-        const int64_t ws = total_tiles * (int64_t)mx_mix_tile(n_slots) * n_slots * 4;
-        const bool nt = g_tune.nontemporal == 2 ? (ws <= ((int64_t)32 << 20) || ws > ((int64_t)320 << 20))
-                                                : g_tune.nontemporal != 0;
-        // store policy of the streaming (nt) 8- and 16-slot launches: forced, or auto -- the chosen
-        // policy above 320 MB, nt below (rows that fit the L2s rely on finding their lines again)
-        const int pol = mx::g_store_policy > 0 ? mx::g_store_policy
-                        : ws > mx::kStoreAutoBytes ? mx::kStoreAutoPolicy : mx::kStoreNt;
-#define MX_POL(N, TW, S, SPEC, GL)                                                                                \
-    (pol == mx::kStoreSc1      ? launch_rows<N, TW, true, S, false, kTPB, SPEC, GL, mx::kStoreSc1>(MX_ARGS)       \
-     : pol == mx::kStoreSc1Nt  ? launch_rows<N, TW, true, S, false, kTPB, SPEC, GL, mx::kStoreSc1Nt>(MX_ARGS)     \
-     : pol == mx::kStoreSc0Sc1 ? launch_rows<N, TW, true, S, false, kTPB, SPEC, GL, mx::kStoreSc0Sc1>(MX_ARGS)    \
-                               : launch_rows<N, TW, true, S, false, kTPB, SPEC, GL>(MX_ARGS))
-#define MX_ROWS(N, TW, S) (nt ? launch_rows<N, TW, true, S>(MX_ARGS) : launch_rows<N, TW, false, S>(MX_ARGS))
-#define MX_ROWSS(N, TW, S) (nt ? MX_POL(N, TW, S, false, false) : launch_rows<N, TW, false, S>(MX_ARGS))
-        if (c.ns == 8 && unroll_for(8) == 2) return MX_ROWSS(8, 2048, 1);
-        const int sp = row_split(c.ns, total_tiles);
-        if (c.ns == 8) {
-            // SPEC (knob "spec"): a round whose local active rows the caller passed (hint, from the
-            // host's copy of the flags: mx_gossip_mix_packed) loads their first tile before the plan
-            // record arrives, at spec_wgpc workgroups per CU -- 8-slot rounds of > 64 MB on the flat
-            // grid with streaming hints (auto hints: > 320 MB; 8 x 14.8M-60M params: -0.5 to -3.5 %,
-            // the headline 0.2700 -> 0.2637 ms; neutral at 8 x 4M; tools/occ_sweep.py, profiles/r06t_*)
-            const int64_t work = total_tiles * sp;
-            const bool flat = !rows_mid(8, total_tiles) && g_tune.flat_small > 0 && g_tune.grid == 0 &&
-                              work <= (int64_t)g_tune.flat_small * grid_target();
-            // only when every slot is a local row: receive slots (RCCL slab, or a peer's HBM under the
-            // pull transport, read over xGMI) keep the uncapped launch measured at N > 1
-            if (nt && hint && g_tune.spec && flat && n_slots == n_local && ws > ((int64_t)64 << 20)) {
-                g_rows_opt.hint = hint;
-                g_rows_opt.wg_per_cu = g_tune.spec_wgpc;
-                ++g_spec_launches;
-                if (g_tune.spec_glds && sp == 2) return MX_POL(8, 512, 2, true, true);
-                return sp == 4 ? MX_POL(8, 256, 4, true, false)
-                               : sp == 2 ? MX_POL(8, 512, 2, true, false) : MX_POL(8, 1024, 1, true, false);
-            }
-            return sp == 4 ? MX_ROWSS(8, 256, 4) : sp == 2 ? MX_ROWSS(8, 512, 2) : MX_ROWSS(8, 1024, 1);
-        }
-        if (c.ns == 16) return sp == 4 ? MX_ROWSS(16, 256, 4) : sp == 2 ? MX_ROWSS(16, 512, 2) : MX_ROWSS(16, 1024, 1);
-#define MX_ROWSP(N, TW, S)                                                                                  \
-    ((g_tune.rows_pf2 == 1 || (g_tune.rows_pf2 == 2 && 8 * n_slots <= 5 * (N)))                                  \
-         ? (nt ? launch_rows<N, TW, true, S, true>(MX_ARGS) : launch_rows<N, TW, false, S, true>(MX_ARGS))     \
-         : MX_ROWS(N, TW, S))
-#define MX_ROWST(N, TW, T)                                                                                  \
-    ((g_tune.rows_pf2 == 1 || (g_tune.rows_pf2 == 2 && 8 * n_slots <= 5 * (N)))                                  \
-         ? (nt ? launch_rows<N, TW, true, 1, true, T>(MX_ARGS) : launch_rows<N, TW, false, 1, true, T>(MX_ARGS)) \
-         : (nt ? launch_rows<N, TW, true, 1, false, T>(MX_ARGS) : launch_rows<N, TW, false, 1, false, T>(MX_ARGS)))
-#define MX_ROWSW(N, TW)                                                                                     \
-    (g_tune.rows_tpb == 1024 ? MX_ROWST(N, TW, 1024) : g_tune.rows_tpb == 512 ? MX_ROWST(N, TW, 512) : MX_ROWSP(N, TW, 1))
-        if (c.ns == 32) return sp == 2 ? MX_ROWSP(32, 256, 2) : MX_ROWSW(32, 512);
-        if (c.ns == 48) return MX_ROWSW(48, 256);
-        return MX_ROWSW(64, 256);
-#undef MX_ROWSW
-#undef MX_ROWST
-#undef MX_ROWSP
-#undef MX_ROWSS
-#undef MX_ROWS
-#undef MX_POL
-    }
-    if (g_tune.regidx && c.ns == 8) {
-        if (unroll_for(8) == 4) { MX_DISPATCH_REG(8, 4) }
-        if (unroll_for(8) == 2) { MX_DISPATCH_REG(8, 2) }
-        MX_DISPATCH_REG(8, 1)
-    }
-    switch (c.ns) {
-        case 8:
-            if (unroll_for(8) == 2) { MX_DISPATCH(4, 8, 2) }
-            MX_DISPATCH(4, 8, 1)
-        case 16:
-            MX_DISPATCH(4, 16, 1)
-        case 32:
-            MX_DISPATCH(2, 32, 1)
-        default:
-            MX_DISPATCH(1, 64, 1)
-    }
-#undef MX_DISPATCH
-#undef MX_DISPATCH_REG
-#undef MX_ARGS
-}
-}  // namespace

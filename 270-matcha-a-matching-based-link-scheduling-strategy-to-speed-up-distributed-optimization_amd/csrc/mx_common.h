@@ -77,8 +77,42 @@ constexpr int kStorePolicyMax = kStoreSc0Sc1;
 // 8 x 14.8M: 0.1549 -> 0.1533 ms, mean 8 x 25.6M: 0.2629 -> 0.2584 ms; sc1 and sc0 sc1 in
 // between; tools/store_policy_ab.py, profiles/store_policy_ab.json)
 constexpr int kStoreAutoPolicy = kStoreSc1Nt;
-constexpr int64_t kStoreAutoBytes = (int64_t)320 << 20;
 extern int g_store_policy;   // 0 = auto, 1..kStorePolicyMax = that policy at every size
+
+// The working-set rules every streaming launch shares (each caller brings its own byte count and its
+// own auto policy).  Rounds of kCachedLoBytes..kCachedHiBytes, about the 256 MB Infinity Cache, keep
+// ordinary (cacheable) accesses: back-to-back rounds then find their rows on die.  Above, and below
+// where the rows fit in the L2s, the streaming hints win (figures at mix.hip's choose()).
+constexpr int64_t kCachedLoBytes = (int64_t)32 << 20;
+constexpr int64_t kCachedHiBytes = (int64_t)320 << 20;
+constexpr int64_t kStoreAutoBytes = kCachedHiBytes;
+inline bool streams(int64_t ws) { return ws <= kCachedLoBytes || ws > kCachedHiBytes; }
+// the store policy of a streaming launch: forced, else above kStoreAutoBytes the caller's auto policy, else nt
+inline int store_policy_of(int forced, int64_t ws, int auto_policy) {
+    return forced > 0 ? forced : ws > kStoreAutoBytes ? auto_policy : (int)kStoreNt;
+}
+
+// A knob of an mx_*_set / mx_*_get pair: its key, where it lives and what it accepts.  knob_set
+// stores an accepted value (normalised: kBool to 0 / 1, kTri to 0 / 1 with 2 kept) or refuses with
+// "<who>: <key> <value>" and leaves the knob alone; both report "<who>: unknown key '<key>'".  A
+// read-only knob is unknown to knob_set.
+struct Knob {
+    enum Kind { kRange, kOneOf, kBool, kTri };
+    const char* key;
+    int* slot;
+    Kind kind;
+    int v[4];          // kRange: [v[0], v[1]]; kOneOf: the accepted values (the last one repeated)
+    bool read_only;
+};
+inline Knob knob_range(const char* key, int* slot, int lo, int hi) { return {key, slot, Knob::kRange, {lo, hi, 0, 0}, false}; }
+inline Knob knob_one_of(const char* key, int* slot, int a, int b, int c, int d) {
+    return {key, slot, Knob::kOneOf, {a, b, c, d}, false};
+}
+inline Knob knob_bool(const char* key, int* slot) { return {key, slot, Knob::kBool, {0, 0, 0, 0}, false}; }
+inline Knob knob_tri(const char* key, int* slot) { return {key, slot, Knob::kTri, {0, 0, 0, 0}, false}; }
+inline Knob knob_read_only(const char* key, int* slot) { return {key, slot, Knob::kRange, {0, 0, 0, 0}, true}; }
+int knob_set(const char* who, const Knob* table, int n, const char* key, int value);
+int knob_get(const char* who, const Knob* table, int n, const char* key);
 
 #if defined(__HIPCC__)
 // One 16-byte store to global memory under policy SP.  The write-through forms have no builtin on

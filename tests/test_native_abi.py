@@ -127,6 +127,81 @@ def test_mix_kernel_dispatch_names(pkg):
         E.set_mix_tuning(**saved)
 
 
+# mx_mix_set's knobs: key -> (default, accepted values as (set, read back), first values outside the range)
+_BOOL = ((0, 0), (1, 1), (7, 1), (-1, 1))
+_TPB = ((256, 256), (512, 512), (1024, 1024))
+MIX_KNOBS = {
+    "blocks_per_cu": (2, ((1, 1), (64, 64)), (0, 65)),
+    "unroll": (1, ((1, 1), (2, 2), (4, 4)), (0, 3, 5)),
+    "nontemporal": (2, ((0, 0), (1, 1), (2, 2), (5, 1), (-1, 1)), ()),
+    "prefetch": (0, _BOOL, ()),
+    "regidx": (1, _BOOL, ()),
+    "chunked": (0, _BOOL, ()),
+    "grid": (0, ((0, 0), (65536, 65536)), (-1, 65537)),
+    "readlane_min": (32, ((8, 8), (128, 128)), (7, 129)),
+    "rows": (2, ((0, 0), (1, 1), (2, 2)), (-1, 3)),
+    "split": (0, ((0, 0), (1, 1), (2, 2), (4, 4)), (-1, 3, 5)),
+    "flat_small": (256, ((0, 0), (4096, 4096)), (-1, 4097)),
+    "ns48": (0, _BOOL, ()),
+    "rows_pf2": (2, ((0, 0), (1, 1), (2, 2)), (-1, 3)),
+    "wide_lds_kb": (158, ((8, 8), (158, 158)), (7, 159)),
+    "wide_plan_lds": (1, ((0, 0), (1, 1)), (-1, 2)),
+    "wide_per_cu": (0, ((0, 0), (8, 8)), (-1, 9)),
+    "wide_tpb": (1024, _TPB, (128, 255, 2048)),
+    "rows_tpb": (256, _TPB, (128, 255, 2048)),
+    "mid_bpc": (4, ((0, 0), (16, 16)), (-1, 17)),
+    "mid_tiles": (8, ((0, 0), (1024, 1024)), (-1, 1025)),
+    "wide_pf2": (1, ((0, 0), (1, 1)), (-1, 2)),
+    "spec": (1, _BOOL, ()),
+    "spec_wgpc": (5, ((0, 0), (32, 32)), (-1, 33)),
+    "spec_glds": (1, _BOOL, ()),
+    "mean_wgpc": (3, ((0, 0), (32, 32)), (-1, 33)),
+    "store_policy": (0, ((0, 0), (4, 4)), (-1, 5)),
+}
+
+
+def test_mix_knobs_defaults_ranges_and_refusals(pkg):
+    """mx_mix_set / mx_mix_get, every key of TUNE_KEYS: the default, each accepted boundary value read back
+    as stored (booleans and nontemporal normalised), each first value outside the range refused with the key
+    in mx_last_error and the knob left as it was; spec_launches reads and cannot be set (host-only)."""
+    L, E = pkg.lib, pkg.engine
+    INV = pkg._lib.MX_ERR_INVALID
+    assert set(MIX_KNOBS) == set(E.TUNE_KEYS) and len(E.TUNE_KEYS) == 26
+
+    def get(k):
+        return L.mx_mix_get(k.encode())
+
+    def put(k, v):
+        return L.mx_mix_set(k.encode(), v)
+
+    saved = {k: get(k) for k in MIX_KNOBS}
+    try:
+        for k, (default, _, _) in MIX_KNOBS.items():
+            assert put(k, default) == 0, k
+        assert {k: get(k) for k in MIX_KNOBS} == {k: d for k, (d, _, _) in MIX_KNOBS.items()}
+        for k, (default, accepted, refused) in MIX_KNOBS.items():
+            for v, back in accepted:
+                assert put(k, v) == 0 and get(k) == back, (k, v)
+            before = get(k)
+            for v in refused:
+                assert put(k, v) == INV, (k, v)
+                err = L.mx_last_error()
+                assert b"mx_mix_set:" in err and k.encode() in err and str(v).encode() in err, (k, v, err)
+                assert get(k) == before, (k, v)
+            assert put(k, default) == 0 and get(k) == default, k
+        n = get("spec_launches")
+        assert n >= 0
+        assert put("spec_launches", 0) == INV and b"spec_launches" in L.mx_last_error()
+        assert get("spec_launches") == n
+        assert put("no_such_knob", 1) == INV and L.mx_last_error() == b"mx_mix_set: unknown key 'no_such_knob'"
+        assert get("no_such_knob") == INV and L.mx_last_error() == b"mx_mix_get: unknown key 'no_such_knob'"
+        assert L.mx_mix_set(None, 1) == INV and b"null key" in L.mx_last_error()
+        assert L.mx_mix_get(None) == INV
+    finally:
+        for k, v in saved.items():
+            put(k, v)
+
+
 def test_mean_rows_to_refuses_partial_overlap_and_names_kernels(pkg):
     """a destination overlapping the rows at a column offset is refused before any
     launch (host-side validation, fake device addresses); whole-row aliasing passes validation.
