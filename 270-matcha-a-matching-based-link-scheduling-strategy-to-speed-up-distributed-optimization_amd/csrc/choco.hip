@@ -38,6 +38,7 @@
 // caller zero-fills the scratch once; every call leaves it that way), so no zeroing launch runs.
 #include "mx_common.h"
 
+#include <climits>
 #include <mutex>
 
 namespace {
@@ -600,6 +601,90 @@ __device__ void record_round(const Rows& R, SelState* st, uint32_t T, unsigned l
     st->win_digit = st->b0;               // this call's floor digit (written by its compaction)
 }
 
+// ---- the steps compact_run and compact_wave_kernel share (one 1024-element wave step each: 4 quads per lane)
+// the four quads of a lane from quad q0 on, 64 lanes apart (non-temporal; zeros for an absent x_hat)
+__device__ __forceinline__ void issue_quads(const f4* x4, const f4* h4, int64_t q0, f4 (&X)[4], f4 (&H)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        X[j] = __builtin_nontemporal_load(x4 + q0 + j * 64);
+        H[j] = h4 ? __builtin_nontemporal_load(h4 + q0 + j * 64) : f4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+}
+
+// d = x - x_hat of four loaded quads (x itself without an x_hat)
+__device__ __forceinline__ void diff_quads(const f4 (&ax)[4], const f4 (&ah)[4], bool have_xhat, float (&d)[4][4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[j][e] = have_xhat ? __fsub_rn(ax[j][e], ah[j][e]) : ax[j][e];
+}
+
+// Ranking: element e < n[j] of quad j is kept when its key is >= fkey (bit 4j + e of `keep`) and its top
+// digit counted into the LDS histogram h; ex[j] = kept elements of quad j in the lanes below this one,
+// wt[j] = in the whole wave.
+template <bool BAL>
+__device__ __forceinline__ void rank_quads(const float (&d)[4][4], const int (&n)[4], uint32_t fkey, uint32_t* h,
+                                           uint32_t& keep, uint32_t (&ex)[4], uint32_t (&wt)[4]) {
+    keep = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        ex[j] = 0;
+        wt[j] = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t key = key_of(d[j][e]);
+            const uint32_t dg = key >> kTopShift;
+            const bool f = e < n[j] && key >= fkey;
+            keep |= (f ? 1u : 0u) << (4 * j + e);
+            if constexpr (BAL) {                    // ballots + mbcnt instead of a shuffle scan
+                const uint64_t b = __ballot(f);
+                ex[j] += lanes_below(b);
+                wt[j] += (uint32_t)__popcll(b);
+            } else {
+                ex[j] += f;                         // this lane's count; scanned below
+            }
+            if (f) atomicAdd(&h[dg], 1u);
+        }
+        if constexpr (!BAL) {
+            const uint32_t incl = wave_incl_scan(ex[j]);
+            wt[j] = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            ex[j] = incl - ex[j];
+        }
+    }
+}
+
+// Candidate stores: one store pair per kept element of the lane, the wave looping as often as its
+// fullest lane keeps (1-2 at 1 % density) instead of 16 masked store pairs.  The wave step's kept
+// elements start at `pos` of the region (returned: where the next step's start); sub = the step's
+// 1024-element sub-block of the chunk (the stored location is chunk-local).
+__device__ __forceinline__ uint32_t store_kept(uint32_t keep, uint32_t pos, const uint32_t (&ex)[4],
+                                               const uint32_t (&wt)[4], const float (&d)[4][4], float* cv,
+                                               uint16_t* cl, int sub, int lane) {
+    uint32_t base[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        base[j] = pos + ex[j];
+        pos += wt[j];
+    }
+    for (uint32_t rem = keep; rem; rem &= rem - 1) {
+        const int b = __builtin_ctz(rem);
+        const int j = b >> 2;
+        float val = d[0][0];
+        uint32_t bj = base[0];
+#pragma unroll
+        for (int t = 1; t < 16; ++t) {           // d read outside the select: a read inside it is folded into
+            const float dt = d[t >> 2][t & 3];     // one dynamically indexed load, which puts d into scratch
+            val = b == t ? dt : val;
+        }
+#pragma unroll
+        for (int t = 1; t < 4; ++t) bj = j == t ? base[t] : bj;
+        const uint32_t p = bj + __popc(keep & ((1u << b) - 1) & (0xfu << (4 * j)));
+        cv[p] = val;
+        cl[p] = (uint16_t)(kSub * sub + 4 * (64 * j + lane) + (b & 3));
+    }
+    return pos;
+}
+
 template <bool BAL, bool LOOP, bool PF2 = false>
 __device__ void compact_run(const Rows& R, const RowView& v, int64_t S, double frac, int fallback, int64_t bx,
                             int64_t gx) {
@@ -614,12 +699,7 @@ __device__ void compact_run(const Rows& R, const RowView& v, int64_t S, double f
     f4 ax[4], ah[4];                               // raw loads of the next full chunk
     f4 px[4], ph[4];                               // PF2: and of the one after
     auto issue_to = [&](f4 (&X)[4], f4 (&H)[4], int64_t c) {
-        const int64_t q0 = c * (kChunk / 4) + wave * kSubQuads + lane;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            X[j] = __builtin_nontemporal_load(x4 + q0 + j * 64);
-            H[j] = h4 ? __builtin_nontemporal_load(h4 + q0 + j * 64) : f4{0.0f, 0.0f, 0.0f, 0.0f};
-        }
+        issue_quads(x4, h4, c * (kChunk / 4) + wave * kSubQuads + lane, X, H);
     };
     auto issue = [&](int64_t c) { issue_to(ax, ah, c); };
     if (!fallback) ctrace(0);
@@ -652,36 +732,10 @@ __device__ void compact_run(const Rows& R, const RowView& v, int64_t S, double f
     const int64_t nfull = vec ? R.P / kChunk : 0;  // chunks whole(c) holds for: [0, nfull)
     int par = 0;
     auto step = [&](int64_t c, float (&d)[4][4], const int (&n)[4]) {
-        uint32_t keep = 0;                           // bit 4j + e: element e of step j is kept
+        uint32_t keep;                               // bit 4j + e: element e of step j is kept
         uint32_t ex[4], wt[4];                       // kept in lower lanes / in the wave, per step
-        uint32_t tot = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            ex[j] = 0;
-            wt[j] = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const uint32_t key = key_of(d[j][e]);
-                const uint32_t dg = key >> kTopShift;
-                const bool f = e < n[j] && key >= fkey;
-                keep |= (f ? 1u : 0u) << (4 * j + e);
-                if constexpr (BAL) {                    // ballots + mbcnt instead of a shuffle scan
-                    const uint64_t b = __ballot(f);
-                    ex[j] += lanes_below(b);
-                    wt[j] += (uint32_t)__popcll(b);
-                } else {
-                    ex[j] += f;                         // this lane's count; scanned below
-                }
-                if (f) atomicAdd(&h[dg], 1u);
-            }
-            if constexpr (!BAL) {
-                const uint32_t incl = wave_incl_scan(ex[j]);
-                wt[j] = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                ex[j] = incl - ex[j];
-            }
-            tot += wt[j];
-        }
-        if (lane == 0) wtot[par][wave] = tot;
+        rank_quads<BAL>(d, n, fkey, h, keep, ex, wt);
+        if (lane == 0) wtot[par][wave] = wt[0] + wt[1] + wt[2] + wt[3];
         __syncthreads();                             // double-buffered by parity: one barrier
         uint32_t pos = 0, all = 0;
         for (int w = 0; w < kWaves; ++w) {
@@ -691,27 +745,7 @@ __device__ void compact_run(const Rows& R, const RowView& v, int64_t S, double f
         float* cv = v.cval + c * kCvLd;
         uint16_t* cl = v.cloc + c * kClLd;
         if constexpr (LOOP) {
-            // one store pair per kept element of the lane, the wave looping as often as its
-            // fullest lane keeps (1-2 at 1 % density) instead of 16 masked store pairs
-            uint32_t base[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                base[j] = pos + ex[j];
-                pos += wt[j];
-            }
-            for (uint32_t rem = keep; rem; rem &= rem - 1) {
-                const int b = __builtin_ctz(rem);
-                const int j = b >> 2;
-                float val = d[0][0];
-                uint32_t bj = base[0];
-#pragma unroll
-                for (int t = 1; t < 16; ++t) val = b == t ? d[t >> 2][t & 3] : val;
-#pragma unroll
-                for (int t = 1; t < 4; ++t) bj = j == t ? base[t] : bj;
-                const uint32_t p = bj + __popc(keep & ((1u << b) - 1) & (0xfu << (4 * j)));
-                cv[p] = val;
-                cl[p] = (uint16_t)(kSub * wave + 4 * (64 * j + lane) + (b & 3));
-            }
+            store_kept(keep, pos, ex, wt, d, cv, cl, wave, lane);
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -731,43 +765,24 @@ __device__ void compact_run(const Rows& R, const RowView& v, int64_t S, double f
         if (threadIdx.x == 0) kept += all;
         par ^= 1;
     };
+    const int n4[4] = {4, 4, 4, 4};
+    auto whole_step = [&](int64_t c, f4 (&X)[4], f4 (&H)[4], int64_t next) {   // rank chunk c out of X / H,
+        float d[4][4];                                                          // refilled with chunk `next`
+        diff_quads(X, H, h4 != nullptr, d);
+        if (next < nfull) issue_to(X, H, next);
+        step(c, d, n4);
+    };
     if constexpr (PF2) {
-        const int n[4] = {4, 4, 4, 4};
         for (; c < nfull; c += 2 * gx) {
-            {
-                float d[4][4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) d[j][e] = h4 ? __fsub_rn(ax[j][e], ah[j][e]) : ax[j][e];
-                if (c + 2 * gx < nfull) issue_to(ax, ah, c + 2 * gx);
-                step(c, d, n);
-            }
+            whole_step(c, ax, ah, c + 2 * gx);
             if (c + gx >= nfull) {                 // the stride sequence's next chunk is past the whole ones
                 c += gx;
                 break;
             }
-            {
-                float d[4][4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) d[j][e] = h4 ? __fsub_rn(px[j][e], ph[j][e]) : px[j][e];
-                if (c + 3 * gx < nfull) issue_to(px, ph, c + 3 * gx);
-                step(c + gx, d, n);
-            }
+            whole_step(c + gx, px, ph, c + 3 * gx);
         }
     } else {
-        for (; c < nfull; c += gx) {
-            float d[4][4];
-            const int n[4] = {4, 4, 4, 4};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) d[j][e] = h4 ? __fsub_rn(ax[j][e], ah[j][e]) : ax[j][e];
-            if (c + gx < nfull) issue(c + gx);
-            step(c, d, n);
-        }
+        for (; c < nfull; c += gx) whole_step(c, ax, ah, c + gx);
     }
     for (; c < nc; c += gx) {
         float d[4][4];
@@ -791,6 +806,14 @@ __global__ __launch_bounds__(kTPB) void compact_kernel(Rows R, int64_t S, double
     compact_run<BAL, LOOP, PF2>(R, v, S, frac, 0, blockIdx.x, gridDim.x);
 }
 
+// the compaction launched: [one row (BAL)][compact_store (LOOP)][compact_pf2 (PF2; ignored with compact_store 0)]
+using TopkFn = void (*)(Rows, int64_t, double);
+constexpr TopkFn kCompact[2][2][2] = {
+    {{compact_kernel<false, false>, compact_kernel<false, false>},
+     {compact_kernel<false, true>, compact_kernel<false, true, true>}},
+    {{compact_kernel<true, false>, compact_kernel<true, false>},
+     {compact_kernel<true, true>, compact_kernel<true, true, true>}}};
+
 // The same pass with wave-owned chunks (mx_topk_set "compact_wave" 1): every wave streams whole
 // chunks of its own -- gw, gw + GW, ... (gw = the wave's index over the grid) -- in four
 // 1024-element sub-steps, each the 4 quads per lane of one wave step above, the next sub-step's
@@ -813,12 +836,7 @@ __global__ __launch_bounds__(kTPB) void compact_wave_kernel(Rows R, int64_t S, d
     auto chunk_of = [&](int64_t s) { return gw + (s >> 2) * GW; };
     f4 ax[4], ah[4];
     auto issue = [&](int64_t s) {
-        const int64_t q0 = chunk_of(s) * (kChunk / 4) + (s & 3) * kSubQuads + lane;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            ax[j] = __builtin_nontemporal_load(x4 + q0 + j * 64);
-            ah[j] = h4 ? __builtin_nontemporal_load(h4 + q0 + j * 64) : f4{0.0f, 0.0f, 0.0f, 0.0f};
-        }
+        issue_quads(x4, h4, chunk_of(s) * (kChunk / 4) + (s & 3) * kSubQuads + lane, ax, ah);
     };
     int64_t s = 0;
     if (chunk_of(0) < nfull) issue(0);             // in flight while b_lo is resolved
@@ -838,54 +856,9 @@ __global__ __launch_bounds__(kTPB) void compact_wave_kernel(Rows R, int64_t S, d
     auto sub = [&](int64_t s, float (&d)[4][4], const int (&n)[4]) {
         const int64_t c = chunk_of(s);
         const int u = (int)(s & 3);
-        uint32_t keep = 0, ex[4], wt[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            ex[j] = 0;
-            wt[j] = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const uint32_t key = key_of(d[j][e]);
-                const uint32_t dg = key >> kTopShift;
-                const bool f = e < n[j] && key >= fkey;
-                keep |= (f ? 1u : 0u) << (4 * j + e);
-                if constexpr (BAL) {
-                    const uint64_t b = __ballot(f);
-                    ex[j] += lanes_below(b);
-                    wt[j] += (uint32_t)__popcll(b);
-                } else {
-                    ex[j] += f;
-                }
-                if (f) atomicAdd(&h[dg], 1u);
-            }
-            if constexpr (!BAL) {
-                const uint32_t incl = wave_incl_scan(ex[j]);
-                wt[j] = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                ex[j] = incl - ex[j];
-            }
-        }
-        float* cv = v.cval + c * kCvLd;
-        uint16_t* cl = v.cloc + c * kClLd;
-        uint32_t base[4], pos = run;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            base[j] = pos + ex[j];
-            pos += wt[j];
-        }
-        for (uint32_t rem = keep; rem; rem &= rem - 1) {
-            const int b = __builtin_ctz(rem);
-            const int j = b >> 2;
-            float val = d[0][0];
-            uint32_t bj = base[0];
-#pragma unroll
-            for (int t = 1; t < 16; ++t) val = b == t ? d[t >> 2][t & 3] : val;
-#pragma unroll
-            for (int t = 1; t < 4; ++t) bj = j == t ? base[t] : bj;
-            const uint32_t p = bj + __popc(keep & ((1u << b) - 1) & (0xfu << (4 * j)));
-            cv[p] = val;
-            cl[p] = (uint16_t)(kSub * u + 4 * (64 * j + lane) + (b & 3));
-        }
-        run = pos;
+        uint32_t keep, ex[4], wt[4];
+        rank_quads<BAL>(d, n, fkey, h, keep, ex, wt);
+        run = store_kept(keep, run, ex, wt, d, v.cval + c * kCvLd, v.cloc + c * kClLd, u, lane);
         if (u == 3) {                              // the chunk is complete: its whole record
             if (lane < kRec) v.cnt[kRec * c + lane] = lane == 3 ? run : 0;
             kept += run;
@@ -895,10 +868,7 @@ __global__ __launch_bounds__(kTPB) void compact_wave_kernel(Rows R, int64_t S, d
     for (; chunk_of(s) < nfull; ++s) {
         float d[4][4];
         const int n[4] = {4, 4, 4, 4};
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) d[j][e] = h4 ? __fsub_rn(ax[j][e], ah[j][e]) : ax[j][e];
+        diff_quads(ax, ah, h4 != nullptr, d);
         if (chunk_of(s + 1) < nfull) issue(s + 1);
         sub(s, d, n);
     }
@@ -921,6 +891,8 @@ __global__ __launch_bounds__(kTPB) void compact_wave_kernel(Rows R, int64_t S, d
     }
 }
 
+constexpr TopkFn kCompactWave[2] = {compact_wave_kernel<false>, compact_wave_kernel<true>};   // [one row (BAL)]
+
 // Every block of this row's grid has arrived (rare path only: the fallback compaction inside the
 // first candidate pass).  Producers: every wave's stores drained and released at agent scope, then
 // one arrival per block on the row's counter; the poller's agent-scope acquire then covers the
@@ -929,16 +901,26 @@ __global__ __launch_bounds__(kTPB) void compact_wave_kernel(Rows R, int64_t S, d
 // (occupancy query x CUs; the margin leaves room for e.g. RCCL's kernels beside it, N > 1), and
 // the wait itself is BOUNDED: past kSpinTicks (~2.7 s) the row's sticky `err` word is set and the
 // block goes on (the row's output is then undefined, never a hang; mx_topk_check reports it).
-__device__ void row_grid_barrier(SelState* st, unsigned blocks) {
+// The one row barrier of this file: every wave's accesses drained, a workgroup barrier, one lane arrives
+// on the row's counter and polls it until `target` arrivals (bounded), a workgroup barrier.
+// FENCED (after plain stores: the fallback compaction in cand_hist<10> and in select_kernel) wraps the
+// arrival in the release / acquire pair described above; unfenced (select_kernel's two hand-offs, whose
+// published words are `sc1` stores read back by `sc1` loads) needs neither.
+template <bool FENCED>
+__device__ __forceinline__ void row_barrier(SelState* st, uint32_t target) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_fetch_add(&st->bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!wait_count(&st->bar, blocks)) st_sc1(&st->err, 1u);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (FENCED) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __hip_atomic_fetch_add((g_u32*)&st->bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!wait_count(&st->bar, target)) st_sc1(&st->err, 1u);
+        if constexpr (FENCED) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
     }
     __syncthreads();
 }
@@ -948,6 +930,22 @@ struct RegionPair {
     int64_t n1, n2;
     float a1, a2;
 };
+
+// regions c and c + stride, as far as they lie below `limit`: each one's count and its candidate `lane`
+// (the region is allocated whatever the count, lanes past it are ignored)
+__device__ __forceinline__ RegionPair load_regions(const RowView& v, int lane, int64_t c, int64_t stride,
+                                                   int64_t limit) {
+    RegionPair q{0, 0, 0.0f, 0.0f};
+    if (c < limit) {
+        q.n1 = v.cnt[kRec * c + 3];
+        q.a1 = v.cval[c * kCvLd + lane];
+    }
+    if (c + stride < limit) {
+        q.n2 = v.cnt[kRec * (c + stride) + 3];
+        q.a2 = v.cval[(c + stride) * kCvLd + lane];
+    }
+    return q;
+}
 
 // candidate histogram of the next digit (10 bits at 9, or 9 bits at 0) among candidates matching
 // the prefix resolved so far; one wave per chunk region; LDS histogram flushed once per block
@@ -961,7 +959,7 @@ __global__ __launch_bounds__(kTPB) void cand_hist(Rows R, int64_t S, double frac
     if constexpr (BITS == kMidBits) {
         if (S != 1 && v.st->cand_n < (unsigned long long)R.k) {    // block-uniform (sampled or hinted floor)
             compact_run<BAL, LOOP>(R, v, S, frac, 1, blockIdx.x, gridDim.x);
-            row_grid_barrier(v.st, gridDim.x);
+            row_barrier<true>(v.st, gridDim.x);
         }
     }
     constexpr int NB = 1 << BITS;
@@ -975,20 +973,8 @@ __global__ __launch_bounds__(kTPB) void cand_hist(Rows R, int64_t S, double frac
     // instead of a count -> candidates chain per region -- this pass reads them cold.  The first
     // step's loads fly while the histograms are resolved, each later step's during the one before.
     const int64_t stride = (int64_t)gridDim.x * kWaves;
-    auto load = [&](int64_t c) {
-        RegionPair q{0, 0, 0.0f, 0.0f};
-        if (c < nchunks) {
-            q.n1 = v.cnt[kRec * c + 3];
-            q.a1 = v.cval[c * kCvLd + lane];
-        }
-        if (c + stride < nchunks) {
-            q.n2 = v.cnt[kRec * (c + stride) + 3];
-            q.a2 = v.cval[(c + stride) * kCvLd + lane];
-        }
-        return q;
-    };
     int64_t c = (int64_t)blockIdx.x * kWaves + wave;
-    RegionPair cur = load(c);
+    RegionPair cur = load_regions(v, lane, c, stride, nchunks);
     const Resolved z = resolve(v, R.k, stages);
     for (int i = threadIdx.x; i < NB; i += kTPB) h[i] = 0;
     __syncthreads();
@@ -997,7 +983,7 @@ __global__ __launch_bounds__(kTPB) void cand_hist(Rows R, int64_t S, double frac
         if ((key & z.mask) == z.prefix) atomicAdd(&h[(key >> shift) & (NB - 1)], 1u);
     };
     for (; c < nchunks; c += 2 * stride) {
-        const RegionPair nx = load(c + 2 * stride);
+        const RegionPair nx = load_regions(v, lane, c + 2 * stride, stride, nchunks);
         const int64_t c2 = c + stride;
         if (lane < cur.n1) add(cur.a1);
         for (int64_t i = 64 + lane; i < cur.n1; i += 64) add(v.cval[c * kCvLd + i]);
@@ -1011,6 +997,10 @@ __global__ __launch_bounds__(kTPB) void cand_hist(Rows R, int64_t S, double frac
         if (h[i]) atomicAdd(&out[i], h[i]);
 }
 
+// the first candidate pass launched, its fallback compaction as the row's compaction: [one row][compact_store]
+constexpr TopkFn kHist10[2][2] = {{cand_hist<kMidBits, false, false>, cand_hist<kMidBits, false, true>},
+                                  {cand_hist<kMidBits, true, false>, cand_hist<kMidBits, true, true>}};
+
 // the exact threshold key T and how many of its ties to take; per chunk region (one wave each)
 // the counts of candidates > T and == T, written without atomics
 // Block j owns the contiguous chunks [j*G, (j+1)*G) and also writes its totals to bt[2j], bt[2j+1],
@@ -1021,19 +1011,8 @@ __global__ __launch_bounds__(kTPB) void cand_mark(Rows R, int64_t G) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t nchunks = n_chunks(R.P);
     const int64_t c0 = (int64_t)blockIdx.x * G, c1 = c0 + G < nchunks ? c0 + G : nchunks;
-    auto load = [&](int64_t c) {                 // two regions per step (as cand_hist), one step ahead
-        RegionPair q{0, 0, 0.0f, 0.0f};
-        if (c < c1) {
-            q.n1 = v.cnt[kRec * c + 3];
-            q.a1 = v.cval[c * kCvLd + lane];
-        }
-        if (c + kWaves < c1) {
-            q.n2 = v.cnt[kRec * (c + kWaves) + 3];
-            q.a2 = v.cval[(c + kWaves) * kCvLd + lane];
-        }
-        return q;
-    };
-    RegionPair cur = load(c0 + wave);            // in flight while the three histograms are resolved
+    // two regions per step (as cand_hist), one step ahead: in flight while the three histograms are resolved
+    RegionPair cur = load_regions(v, lane, c0 + wave, kWaves, c1);
     const Resolved z = resolve(v, R.k, 3);
     const uint32_t T = z.prefix;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -1062,7 +1041,7 @@ __global__ __launch_bounds__(kTPB) void cand_mark(Rows R, int64_t G) {
         if (lane < kRec) v.cnt[kRec * c + lane] = lane == 1 ? g : lane == 2 ? e : lane == 3 ? nc : 0;
     };
     for (int64_t c = c0 + wave; c < c1; c += 2 * kWaves) {
-        const RegionPair nx = load(c + 2 * kWaves);
+        const RegionPair nx = load_regions(v, lane, c + 2 * kWaves, kWaves, c1);
         count(c, cur.n1, cur.a1);
         if (c + kWaves < c1) count(c + kWaves, cur.n2, cur.a2);
         cur = nx;
@@ -1197,36 +1176,6 @@ __global__ __launch_bounds__(kTPB) void write_cand(Rows R, int64_t G) {
 constexpr int kSelTPB = 1024;
 constexpr int kSelWaves = kSelTPB / 64;
 constexpr int kSelRC = 8;                      // chunk regions per wave cached in LDS (128 candidates each)
-// thread 0: poll the row's arrival counter until `target` (bounded: the row's error word is set)
-__device__ __forceinline__ void spin_until(SelState* st, uint32_t target) {
-    if (!wait_count(&st->bar, target)) st_sc1(&st->err, 1u);
-}
-
-// after this block's `sc1` publishing stores: arrive, wait for the row's other blocks
-__device__ __forceinline__ void sel_barrier(SelState* st, uint32_t target) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add((g_u32*)&st->bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        spin_until(st, target);
-    }
-    __syncthreads();
-}
-
-// after plain stores (the fallback compaction): release, arrive, wait, acquire
-__device__ __forceinline__ void sel_barrier_fenced(SelState* st, uint32_t target) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __hip_atomic_fetch_add((g_u32*)&st->bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        spin_until(st, target);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-}
-
 // block-wide sum of one value per thread (all threads receive it)
 __device__ __forceinline__ int64_t sel_block_sum(int64_t x) {
     __shared__ int64_t part[kSelWaves];
@@ -1327,7 +1276,7 @@ __global__ __launch_bounds__(kSelTPB) void select_kernel(Rows R, int row0, int B
         for (int i = tid; i < kTopBins; i += kSelTPB)
             if (h[i]) atomicAdd(&v.h12f[i], h[i]);
         bar0 = (uint32_t)B;
-        sel_barrier_fenced(v.st, bar0);
+        row_barrier<true>(v.st, bar0);
         load_cache();
         load_bins<kTopBins, kSelTPB>(v.h12f, f12);
     }
@@ -1401,7 +1350,7 @@ __global__ __launch_bounds__(kSelTPB) void select_kernel(Rows R, int row0, int B
     __syncthreads();
     stamp(2);
     for (int i = tid; i < kPub10; i += kSelTPB) st_sc1(&pub10[b * kPub10 + i], h[i]);
-    sel_barrier(v.st, bar0 + B);
+    row_barrier<false>(v.st, bar0 + B);
     stamp(3);
     if (b == 0) {                                // nothing reads the 12-bit histograms or the
         for (int i = tid; i < 3 * kTopBins; i += kSelTPB) v.hs[i] = 0;   // candidate total any more
@@ -1446,7 +1395,7 @@ __global__ __launch_bounds__(kSelTPB) void select_kernel(Rows R, int row0, int B
     stamp(5);
     if (tid < (1 << kLowBits)) st_sc1(&pub9[b * kPub9 + tid], h[tid]);
     if (tid == 0) st_sc1(&pub9[b * kPub9 + (1 << kLowBits)], (uint32_t)gt_blk);
-    sel_barrier(v.st, bar0 + 2 * B);
+    row_barrier<false>(v.st, bar0 + 2 * B);
     stamp(6);
     int64_t base_gt, base_eq;
     {
@@ -1682,6 +1631,136 @@ __device__ __forceinline__ const int32_t* round_rec(const int32_t* rec, const in
     return r[0] ? r : nullptr;
 }
 
+// The launch arguments of the apply kernels.  The scalars travel as one record, passed by value as Rows
+// is to the top-k kernels.  The six arrays stay __restrict__ kernel parameters: a by-value record cannot
+// carry the qualifier, and without it the compiler cannot prove that the plan record, the slot table and
+// the messages' bounds are not overwritten behind a barrier, so their wave-uniform scalar loads become
+// vector loads queued with the tile stream (apply_kernel_pf: 66 -> 84 VGPRs, profiles/choco_refactor.md).
+struct ApplyDims {
+    int64_t ld, P;
+    int64_t msg_ld, kpad, k;
+    int64_t n_iters, words;    // round_rec's arguments, with rec_in and iter_dev
+    int n_local, M;
+    float alpha, g;
+};
+#define MX_APPLY_ARRAYS                                                                                        \
+    float *__restrict__ x, float *__restrict__ xh, float *__restrict__ s, const char *__restrict__ msgs,       \
+        const int32_t *__restrict__ rec_in, const int64_t *__restrict__ iter_dev
+// what the device functions take: the record and the arrays (msgs: the strided message buffer, or for the
+// slot-table kernels the int64 address table)
+struct ApplyArgs : ApplyDims {
+    float *x, *xh, *s;
+    const char* msgs;
+    const int32_t* rec_in;
+    const int64_t* iter_dev;
+};
+
+// What every apply kernel starts with: this round's plan record (none: the launch is a no-op), the pull
+// transport's acquire, and where the messages start -- the slot table (SP) or the strided buffer; then
+// body(rec, ms).
+template <bool SP, class F>
+__device__ __forceinline__ void apply_round(const ApplyArgs& a, F&& body) {
+    const int32_t* rec = round_rec(a.rec_in, a.iter_dev, a.n_iters, a.words);
+    if (!rec) return;
+    peer_acquire(rec[2]);
+    if constexpr (SP) body(rec, MsgTable{reinterpret_cast<const int64_t*>(a.msgs)});
+    else body(rec, MsgStride{a.msgs, a.msg_ld});
+}
+
+// the workgroup's staging of one tile: s and x_hat, and a dirty flag per granule of each
+struct TileLds {
+    float *ls, *lh;
+    uint8_t *ds, *dh;
+};
+
+// Row r's tile t: where it starts in x / s / x_hat, its first element and length, and whether it is a
+// whole tile of 16-byte-aligned rows (the vector paths)
+struct Tile {
+    float *xr, *sr, *hr;
+    int64_t t, t0;
+    int len;
+    bool vec;
+};
+
+__device__ __forceinline__ Tile tile_at(const ApplyArgs& a, int r, int64_t t) {
+    Tile T;
+    T.t = t;
+    T.t0 = t * kTile;
+    T.len = (int)(a.P - T.t0 < kTile ? a.P - T.t0 : kTile);
+    T.xr = a.x + (int64_t)r * a.ld + T.t0;
+    T.sr = a.s + (int64_t)r * a.ld + T.t0;
+    T.hr = a.xh + (int64_t)r * a.ld + T.t0;
+    T.vec = T.len == kTile && (((uintptr_t)T.xr | (uintptr_t)T.sr | (uintptr_t)T.hr) & 15) == 0;
+    return T;
+}
+
+constexpr int kQ = kTile / 4 / kTPB;           // quads per lane
+
+// message m's entries inside the tile: [lo, hi) of its bounds, clamped -- a received message is not
+// trusted to stay in range
+__device__ __forceinline__ void msg_range(const Msg& m, const Tile& T, int64_t k, int& lo, int& hi) {
+    lo = max(m.bnd[T.t], 0);
+    hi = min(m.bnd[T.t + 1], (int)k);
+}
+
+// One message entry applied to the staged tile: s += w * v and, for the row's own message, x_hat += v;
+// the granules it touches become dirty.  An index outside the tile is dropped (a received message is
+// not trusted to stay in range).
+template <int GRAN>
+__device__ __forceinline__ void upd(const TileLds& L, const Tile& T, bool own, float w, int64_t ix, float vq) {
+    const int c = (int)(ix - T.t0);
+    if ((unsigned)c >= (unsigned)T.len) return;
+    L.ls[c] = __fadd_rn(L.ls[c], __fmul_rn(w, vq));
+    L.ds[c / GRAN] = 1;
+    if (own) {
+        L.lh[c] = __fadd_rn(L.lh[c], vq);
+        L.dh[c / GRAN] = 1;
+    }
+}
+
+// entries [from, hi) of message m, one per thread and pass, loaded as they are applied
+template <int GRAN>
+__device__ __forceinline__ void apply_entries(const TileLds& L, const Tile& T, const Msg& m, int from, int hi,
+                                              bool own, float w) {
+    for (int q = from + (int)threadIdx.x; q < hi; q += kTPB) upd<GRAN>(L, T, own, w, m.ix[q], m.v[q]);
+}
+
+// the entries of message `slot` inside the tile, applied from memory: two round trips, bounds then entries
+template <int GRAN, class MS>
+__device__ __forceinline__ void apply_msg(const ApplyArgs& a, const MS& ms, int slot, bool own, float w,
+                                          const TileLds& L, const Tile& T) {
+    const Msg m = msg_at(ms, a.kpad, a.k, slot);
+    int lo, hi;
+    msg_range(m, T, a.k, lo, hi);
+    apply_entries<GRAN>(L, T, m, lo, hi, own, w);
+}
+
+// The dense update x = fma(-g, x_hat, fma(g, s, x)) and the write-back of the dirty granules of s / x_hat:
+// a whole aligned tile from the x already in registers, a partial or unaligned one element by element
+template <bool NT, int GRAN>
+__device__ __forceinline__ void dense_tail(const Tile& T, const TileLds& L, const f4 (&xv)[kQ], float g) {
+    if (T.vec) {
+#pragma unroll
+        for (int j = 0; j < kQ; ++j) {
+            const int q = j * kTPB + threadIdx.x;
+            f4 a = xv[j];
+            const f4 sv = reinterpret_cast<const f4*>(L.ls)[q];
+            const f4 hv = reinterpret_cast<const f4*>(L.lh)[q];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) a[c] = __builtin_fmaf(-g, hv[c], __builtin_fmaf(g, sv[c], a[c]));
+            st4<NT>(a, reinterpret_cast<f4*>(T.xr) + q);
+            if (L.ds[q / (GRAN / 4)]) st4<NT>(sv, reinterpret_cast<f4*>(T.sr) + q);
+            if (L.dh[q / (GRAN / 4)]) st4<NT>(hv, reinterpret_cast<f4*>(T.hr) + q);
+        }
+    } else {
+        for (int i = threadIdx.x; i < T.len; i += kTPB) {
+            T.xr[i] = __builtin_fmaf(-g, L.lh[i], __builtin_fmaf(g, L.ls[i], T.xr[i]));
+            if (L.ds[i / GRAN]) T.sr[i] = L.ls[i];
+            if (L.dh[i / GRAN]) T.hr[i] = L.lh[i];
+        }
+    }
+}
+
 // NT: non-temporal accesses.  Chosen by the row count (mx_topk_set "apply_nt", -1 = auto): with
 // several rows the streams are far larger than the Infinity Cache and the hints win (8 rows
 // 0.65 ms vs 0.80 ms with ordinary accesses); a single row (config 4's share of one GPU at N = 8)
@@ -1691,107 +1770,47 @@ __device__ __forceinline__ const int32_t* round_rec(const int32_t* rec, const in
 // granules measured 8 rows 639 -> 715 us per round (same-box A/B; partial non-temporal line writes),
 // one row unchanged
 template <bool NT, int GRAN, class MS>
-__device__ __forceinline__ void apply_tile(float* __restrict__ x, float* __restrict__ xh, float* __restrict__ s,
-                                           int64_t ld, int64_t P, const MS& ms, int64_t kpad, int64_t k,
-                                           const int32_t* __restrict__ rec, int n_local, int M, float alpha, float g,
-                                           float* ls, float* lh, uint8_t* ds, uint8_t* dh, int r, int64_t t) {
-    constexpr int kGran = GRAN;
-    const int64_t t0 = t * kTile;
-    const int len = (int)(P - t0 < kTile ? P - t0 : kTile);
-    float* xr = x + (int64_t)r * ld + t0;
-    float* sr = s + (int64_t)r * ld + t0;
-    float* hr = xh + (int64_t)r * ld + t0;
+__device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MS& ms, const int32_t* __restrict__ rec,
+                                           const TileLds& L, int r, int64_t t) {
+    const Tile T = tile_at(a, r, t);
     const int tid = threadIdx.x;
-    const bool vec = len == kTile && (((uintptr_t)xr | (uintptr_t)sr | (uintptr_t)hr) & 15) == 0;
-    constexpr int kQ = kTile / 4 / kTPB;       // quads per lane
     f4 xv[kQ];                                 // x is loaded up front: its stream overlaps the
-    if (vec) {                                 // message phase instead of following it
+    if (T.vec) {                               // message phase instead of following it
 #pragma unroll
         for (int j = 0; j < kQ; ++j) {
             const int q = j * kTPB + tid;
-            xv[j] = ld4<NT>(reinterpret_cast<const f4*>(xr) + q);
-            reinterpret_cast<f4*>(ls)[q] = ld4<NT>(reinterpret_cast<const f4*>(sr) + q);
-            reinterpret_cast<f4*>(lh)[q] = ld4<NT>(reinterpret_cast<const f4*>(hr) + q);
+            xv[j] = ld4<NT>(reinterpret_cast<const f4*>(T.xr) + q);
+            reinterpret_cast<f4*>(L.ls)[q] = ld4<NT>(reinterpret_cast<const f4*>(T.sr) + q);
+            reinterpret_cast<f4*>(L.lh)[q] = ld4<NT>(reinterpret_cast<const f4*>(T.hr) + q);
         }
     } else {
-        for (int i = tid; i < len; i += kTPB) {
-            ls[i] = sr[i];
-            lh[i] = hr[i];
+        for (int i = tid; i < T.len; i += kTPB) {
+            L.ls[i] = T.sr[i];
+            L.lh[i] = T.hr[i];
         }
     }
-    for (int i = tid; i < kTile / kGran; i += kTPB) ds[i] = dh[i] = 0;
+    for (int i = tid; i < kTile / GRAN; i += kTPB) L.ds[i] = L.dh[i] = 0;
     __syncthreads();
     const int32_t* deg = rec + mx::kPlanHeader;
     const int d = deg[r];
-    const int32_t* src = deg + 2 * n_local + r * M;
+    const int32_t* src = deg + 2 * a.n_local + r * a.M;
     for (int e = 0; e < d; ++e) {              // partners, ascending matching order
-        const Msg m = msg_at(ms, kpad, k, src[e]);
-        const int lo = max(m.bnd[t], 0), hi = min(m.bnd[t + 1], (int)k);   // clamped: a received
-        for (int q = lo + tid; q < hi; q += kTPB) {                        // message is not trusted
-            const int c = (int)(m.ix[q] - t0);                             // to stay in range
-            if ((unsigned)c >= (unsigned)len) continue;
-            ls[c] = __fadd_rn(ls[c], __fmul_rn(alpha, m.v[q]));
-            ds[c / kGran] = 1;
-        }
+        apply_msg<GRAN>(a, ms, src[e], false, a.alpha, L, T);
         __syncthreads();                       // a later message may touch the same element
     }
-    {                                          // own message
-        const float sw = __int_as_float(deg[n_local + r]);
-        const Msg m = msg_at(ms, kpad, k, r);
-        const int lo = max(m.bnd[t], 0), hi = min(m.bnd[t + 1], (int)k);
-        for (int q = lo + tid; q < hi; q += kTPB) {
-            const int c = (int)(m.ix[q] - t0);
-            if ((unsigned)c >= (unsigned)len) continue;
-            const float vq = m.v[q];
-            ls[c] = __fadd_rn(ls[c], __fmul_rn(sw, vq));
-            lh[c] = __fadd_rn(lh[c], vq);
-            ds[c / kGran] = 1;
-            dh[c / kGran] = 1;
-        }
-    }
+    apply_msg<GRAN>(a, ms, r, true, __int_as_float(deg[a.n_local + r]), L, T);   // own message
     __syncthreads();
-    if (vec) {
-#pragma unroll
-        for (int j = 0; j < kQ; ++j) {
-            const int q = j * kTPB + tid;
-            f4 a = xv[j];
-            const f4 sv = reinterpret_cast<const f4*>(ls)[q];
-            const f4 hv = reinterpret_cast<const f4*>(lh)[q];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) a[c] = __builtin_fmaf(-g, hv[c], __builtin_fmaf(g, sv[c], a[c]));
-            st4<NT>(a, reinterpret_cast<f4*>(xr) + q);
-            if (ds[q / (kGran / 4)]) st4<NT>(sv, reinterpret_cast<f4*>(sr) + q);
-            if (dh[q / (kGran / 4)]) st4<NT>(hv, reinterpret_cast<f4*>(hr) + q);
-        }
-    } else {
-        for (int i = tid; i < len; i += kTPB) {
-            xr[i] = __builtin_fmaf(-g, lh[i], __builtin_fmaf(g, ls[i], xr[i]));
-            if (ds[i / kGran]) sr[i] = ls[i];
-            if (dh[i / kGran]) hr[i] = lh[i];
-        }
-    }
+    dense_tail<NT, GRAN>(T, L, xv, a.g);
 }
 
 template <bool NT, int GRAN, bool SP>
-__global__ __launch_bounds__(kTPB) void apply_kernel(float* __restrict__ x, float* __restrict__ xh,
-                                                     float* __restrict__ s, int64_t ld, int64_t P,
-                                                     const char* __restrict__ msgs, int64_t msg_ld,
-                                                     int64_t kpad, int64_t k,
-                                                     const int32_t* __restrict__ rec_in,
-                                                     const int64_t* __restrict__ iter_dev, int64_t n_iters,
-                                                     int64_t words, int n_local, int M,
-                                                     float alpha, float g) {
-    const int32_t* rec = round_rec(rec_in, iter_dev, n_iters, words);
-    if (!rec) return;
-    peer_acquire(rec[2]);
+__global__ __launch_bounds__(kTPB) void apply_kernel(MX_APPLY_ARRAYS, ApplyDims dims) {
+    const ApplyArgs a{dims, x, xh, s, msgs, rec_in, iter_dev};
     __shared__ float ls[kTile], lh[kTile];
     __shared__ uint8_t ds[kTile / GRAN], dh[kTile / GRAN];
-    if constexpr (SP)
-        apply_tile<NT, GRAN>(x, xh, s, ld, P, MsgTable{reinterpret_cast<const int64_t*>(msgs)}, kpad, k, rec, n_local,
-                             M, alpha, g, ls, lh, ds, dh, blockIdx.y, blockIdx.x);
-    else
-        apply_tile<NT, GRAN>(x, xh, s, ld, P, MsgStride{msgs, msg_ld}, kpad, k, rec, n_local, M, alpha, g, ls, lh,
-                             ds, dh, blockIdx.y, blockIdx.x);
+    apply_round<SP>(a, [&](const int32_t* rec, const auto& ms) {
+        apply_tile<NT, GRAN>(a, ms, rec, TileLds{ls, lh, ds, dh}, blockIdx.y, blockIdx.x);
+    });
 }
 
 // The same pass with the message phase's global reads moved under the tile's stream: the plan
@@ -1804,30 +1823,22 @@ __global__ __launch_bounds__(kTPB) void apply_kernel(float* __restrict__ x, floa
 constexpr int kPfMsgs = 8;
 
 template <bool NT, class MS>
-__device__ __forceinline__ void apply_pf_tile(float* __restrict__ x, float* __restrict__ xh, float* __restrict__ s,
-                                              int64_t ld, int64_t P, const MS& ms, int64_t kpad, int64_t k,
-                                              const int32_t* __restrict__ rec, int n_local, int M, float alpha,
-                                              float g, float* ls, float* lh, uint8_t* ds, uint8_t* dh, int r,
-                                              int64_t t) {
+__device__ __forceinline__ void apply_pf_tile(const ApplyArgs& a, const MS& ms, const int32_t* __restrict__ rec,
+                                              const TileLds& L, int r, int64_t t) {
     constexpr int kGran = 16;
-    const int64_t t0 = t * kTile;
-    const int len = (int)(P - t0 < kTile ? P - t0 : kTile);
-    float* xr = x + (int64_t)r * ld + t0;
-    float* sr = s + (int64_t)r * ld + t0;
-    float* hr = xh + (int64_t)r * ld + t0;
-    if (!(len == kTile && (((uintptr_t)xr | (uintptr_t)sr | (uintptr_t)hr) & 15) == 0)) {   // partial /
-        apply_tile<NT, 16>(x, xh, s, ld, P, ms, kpad, k, rec, n_local, M, alpha, g, ls, lh, ds, dh, r, t);
-        return;                                                                         // unaligned tile
+    const Tile T = tile_at(a, r, t);
+    if (!T.vec) {                              // partial / unaligned tile
+        apply_tile<NT, kGran>(a, ms, rec, L, r, t);
+        return;
     }
     // from here on the whole-tile path is branch-free up to the message phase, so the waitcnt pass
     // can count the loads in flight exactly (a merge of two paths makes it wait for all of them)
     const int tid = threadIdx.x;
-    constexpr int kQ = kTile / 4 / kTPB;       // quads per lane
     const int32_t* deg = rec + mx::kPlanHeader;
     const int d = deg[r];
     const int nm = d + 1;                      // partners in matching order, then the own message
-    const int32_t* src = deg + 2 * n_local + r * M;
-    const float sw = __int_as_float(deg[n_local + r]);
+    const int32_t* src = deg + 2 * a.n_local + r * a.M;
+    const float sw = __int_as_float(deg[a.n_local + r]);
     // lane e < kPfMsgs of every wave: message e's slot, then its bounds in this tile -- two small
     // vector loads issued BEFORE the tile stream (vector loads return in order), so the entry
     // loads that need them can be issued right behind the stream
@@ -1837,19 +1848,16 @@ __device__ __forceinline__ void apply_pf_tile(float* __restrict__ x, float* __re
         const int e = lane < kPfMsgs ? lane : 0;
         const int sl = lane < kPfMsgs && e < d ? src[e] : r;
         my_sl = sl;
-        const Msg m = msg_at(ms, kpad, k, sl);
-        if (lane < kPfMsgs && e < nm) {
-            my_lo = max(m.bnd[t], 0);              // clamped: a received message is not trusted
-            my_hi = min(m.bnd[t + 1], (int)k);     // to stay in range
-        }
+        const Msg m = msg_at(ms, a.kpad, a.k, sl);
+        if (lane < kPfMsgs && e < nm) msg_range(m, T, a.k, my_lo, my_hi);
     }
     f4 xv[kQ], sv[kQ], hv[kQ];
 #pragma unroll
     for (int j = 0; j < kQ; ++j) {
         const int q = j * kTPB + tid;
-        xv[j] = ld4<NT>(reinterpret_cast<const f4*>(xr) + q);
-        sv[j] = ld4<NT>(reinterpret_cast<const f4*>(sr) + q);
-        hv[j] = ld4<NT>(reinterpret_cast<const f4*>(hr) + q);
+        xv[j] = ld4<NT>(reinterpret_cast<const f4*>(T.xr) + q);
+        sv[j] = ld4<NT>(reinterpret_cast<const f4*>(T.sr) + q);
+        hv[j] = ld4<NT>(reinterpret_cast<const f4*>(T.hr) + q);
     }
     int plo[kPfMsgs], phi[kPfMsgs];
     int64_t pix[kPfMsgs];
@@ -1859,81 +1867,54 @@ __device__ __forceinline__ void apply_pf_tile(float* __restrict__ x, float* __re
         plo[e] = __builtin_amdgcn_readlane(my_lo, e);
         phi[e] = __builtin_amdgcn_readlane(my_hi, e);
         const int q = plo[e] + tid < phi[e] ? plo[e] + tid : 0;     // clamped: loads stay unconditional
-        const Msg m = msg_at(ms, kpad, k, __builtin_amdgcn_readlane(my_sl, e));
+        const Msg m = msg_at(ms, a.kpad, a.k, __builtin_amdgcn_readlane(my_sl, e));
         pix[e] = m.ix[q];
         pv[e] = m.v[q];
     }
 #pragma unroll
     for (int j = 0; j < kQ; ++j) {
         const int q = j * kTPB + tid;
-        reinterpret_cast<f4*>(ls)[q] = sv[j];
-        reinterpret_cast<f4*>(lh)[q] = hv[j];
+        reinterpret_cast<f4*>(L.ls)[q] = sv[j];
+        reinterpret_cast<f4*>(L.lh)[q] = hv[j];
     }
-    for (int i = tid; i < kTile / kGran; i += kTPB) ds[i] = dh[i] = 0;
+    for (int i = tid; i < kTile / kGran; i += kTPB) L.ds[i] = L.dh[i] = 0;
     __syncthreads();
-    auto upd = [&](bool own, int64_t ix, float vq) {
-        const int c = (int)(ix - t0);
-        if ((unsigned)c >= (unsigned)len) return;
-        ls[c] = __fadd_rn(ls[c], __fmul_rn(own ? sw : alpha, vq));
-        ds[c / kGran] = 1;
-        if (own) {
-            lh[c] = __fadd_rn(lh[c], vq);
-            dh[c / kGran] = 1;
-        }
-    };
 #pragma unroll
     for (int e = 0; e < kPfMsgs; ++e) {
         if (e >= nm) break;
         const bool own = e == d;
-        if (plo[e] + tid < phi[e]) upd(own, pix[e], pv[e]);
-        if (phi[e] - plo[e] > kTPB) {
-            const Msg m = msg_at(ms, kpad, k, __builtin_amdgcn_readlane(my_sl, e));
-            for (int q = plo[e] + kTPB + tid; q < phi[e]; q += kTPB) upd(own, m.ix[q], m.v[q]);
-        }
+        const float w = own ? sw : a.alpha;
+        if (plo[e] + tid < phi[e]) upd<kGran>(L, T, own, w, pix[e], pv[e]);
+        if (phi[e] - plo[e] > kTPB)
+            apply_entries<kGran>(L, T, msg_at(ms, a.kpad, a.k, __builtin_amdgcn_readlane(my_sl, e)), plo[e] + kTPB,
+                                 phi[e], own, w);
         __syncthreads();                       // a later message may touch the same element
     }
     for (int e = kPfMsgs; e < nm; ++e) {
         const bool own = e == d;
-        const Msg m = msg_at(ms, kpad, k, own ? r : src[e]);
-        const int lo = max(m.bnd[t], 0), hi = min(m.bnd[t + 1], (int)k);
-        for (int q = lo + tid; q < hi; q += kTPB) upd(own, m.ix[q], m.v[q]);
+        apply_msg<kGran>(a, ms, own ? r : src[e], own, own ? sw : a.alpha, L, T);
         __syncthreads();
     }
-#pragma unroll
-    for (int j = 0; j < kQ; ++j) {
-        const int q = j * kTPB + tid;
-        f4 a = xv[j];
-        const f4 s4 = reinterpret_cast<const f4*>(ls)[q];
-        const f4 h4 = reinterpret_cast<const f4*>(lh)[q];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) a[c] = __builtin_fmaf(-g, h4[c], __builtin_fmaf(g, s4[c], a[c]));
-        st4<NT>(a, reinterpret_cast<f4*>(xr) + q);
-        if (ds[q / (kGran / 4)]) st4<NT>(s4, reinterpret_cast<f4*>(sr) + q);
-        if (dh[q / (kGran / 4)]) st4<NT>(h4, reinterpret_cast<f4*>(hr) + q);
-    }
+    dense_tail<NT, kGran>(T, L, xv, a.g);
 }
 
 template <bool NT, bool SP>
-__global__ __launch_bounds__(kTPB) void apply_kernel_pf(float* __restrict__ x, float* __restrict__ xh,
-                                                        float* __restrict__ s, int64_t ld, int64_t P,
-                                                        const char* __restrict__ msgs, int64_t msg_ld,
-                                                        int64_t kpad, int64_t k,
-                                                        const int32_t* __restrict__ rec_in,
-                                                        const int64_t* __restrict__ iter_dev, int64_t n_iters,
-                                                        int64_t words, int n_local, int M,
-                                                        float alpha, float g) {
-    const int32_t* rec = round_rec(rec_in, iter_dev, n_iters, words);
-    if (!rec) return;
-    peer_acquire(rec[2]);
+__global__ __launch_bounds__(kTPB) void apply_kernel_pf(MX_APPLY_ARRAYS, ApplyDims dims) {
+    const ApplyArgs a{dims, x, xh, s, msgs, rec_in, iter_dev};
     __shared__ float ls[kTile], lh[kTile];
     __shared__ uint8_t ds[kTile / 16], dh[kTile / 16];
-    if constexpr (SP)
-        apply_pf_tile<NT>(x, xh, s, ld, P, MsgTable{reinterpret_cast<const int64_t*>(msgs)}, kpad, k, rec, n_local,
-                          M, alpha, g, ls, lh, ds, dh, blockIdx.y, blockIdx.x);
-    else
-        apply_pf_tile<NT>(x, xh, s, ld, P, MsgStride{msgs, msg_ld}, kpad, k, rec, n_local, M, alpha, g, ls, lh, ds,
-                          dh, blockIdx.y, blockIdx.x);
+    apply_round<SP>(a, [&](const int32_t* rec, const auto& ms) {
+        apply_pf_tile<NT>(a, ms, rec, TileLds{ls, lh, ds, dh}, blockIdx.y, blockIdx.x);
+    });
 }
+
+// the per-tile apply kernels: [form: 0 plain, 1 message entries prefetched][non-temporal][slot table]
+using ApplyFn = void (*)(MX_APPLY_ARRAYS, ApplyDims);
+constexpr ApplyFn kApply[2][2][2] = {
+    {{apply_kernel<false, 16, false>, apply_kernel<false, 16, true>},
+     {apply_kernel<true, 16, false>, apply_kernel<true, 16, true>}},
+    {{apply_kernel_pf<false, false>, apply_kernel_pf<false, true>},
+     {apply_kernel_pf<true, false>, apply_kernel_pf<true, true>}}};
 
 // Persistent form (a grid of about the co-resident workgroups, each looping over the tiles
 // blockIdx.x, + gridDim.x, ... of row blockIdx.y): per workgroup, not per tile, the pull
@@ -1942,29 +1923,27 @@ __global__ __launch_bounds__(kTPB) void apply_kernel_pf(float* __restrict__ x, f
 constexpr int kLdsSlots = 256;
 
 template <bool NT, bool SP>
-__global__ __launch_bounds__(kTPB) void apply_kernel_persist(float* __restrict__ x, float* __restrict__ xh,
-                                                             float* __restrict__ s, int64_t ld, int64_t P,
-                                                             const char* __restrict__ msgs, int64_t msg_ld,
-                                                             int64_t kpad, int64_t k,
-                                                             const int32_t* __restrict__ rec_in,
-                                                             const int64_t* __restrict__ iter_dev, int64_t n_iters,
-                                                             int64_t words, int n_local, int M,
-                                                             float alpha, float g, int n_slots, int64_t ntiles) {
-    const int32_t* rec = round_rec(rec_in, iter_dev, n_iters, words);
-    if (!rec) return;
-    peer_acquire(rec[2]);
+__global__ __launch_bounds__(kTPB) void apply_kernel_persist(MX_APPLY_ARRAYS, ApplyDims dims, int n_slots, int64_t ntiles) {
+    const ApplyArgs a{dims, x, xh, s, msgs, rec_in, iter_dev};
     __shared__ float ls[kTile], lh[kTile];
     __shared__ uint8_t ds[kTile / 16], dh[kTile / 16];
     __shared__ int64_t ltab[kLdsSlots];
-    for (int i = threadIdx.x; i < n_slots; i += kTPB)
-        ltab[i] = SP ? reinterpret_cast<const int64_t*>(msgs)[i] : (int64_t)(msgs + (int64_t)i * msg_ld);
-    __syncthreads();
-    const MsgTable ms{ltab};
-    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        apply_pf_tile<NT>(x, xh, s, ld, P, ms, kpad, k, rec, n_local, M, alpha, g, ls, lh, ds, dh, blockIdx.y, t);
-        __syncthreads();                       // the next tile restages ls / lh / ds / dh
-    }
+    apply_round<SP>(a, [&](const int32_t* rec, const auto& ms) {
+        for (int i = threadIdx.x; i < n_slots; i += kTPB) ltab[i] = reinterpret_cast<int64_t>(ms.base(i));
+        __syncthreads();
+        const MsgTable lt{ltab};
+        for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+            apply_pf_tile<NT>(a, lt, rec, TileLds{ls, lh, ds, dh}, blockIdx.y, t);
+            __syncthreads();                   // the next tile restages ls / lh / ds / dh
+        }
+    });
 }
+
+using ApplyPersistFn = void (*)(MX_APPLY_ARRAYS, ApplyDims, int, int64_t);
+constexpr ApplyPersistFn kApplyPersist[2][2] = {      // [non-temporal][slot table]
+    {apply_kernel_persist<false, false>, apply_kernel_persist<false, true>},
+    {apply_kernel_persist<true, false>, apply_kernel_persist<true, true>}};
+#undef MX_APPLY_ARRAYS
 
 unsigned clamp_grid(int64_t n, int64_t per, int64_t cap) {
     int64_t g = (n + per - 1) / per;
@@ -2014,8 +1993,8 @@ int g_fine_floor = 1;          // 1: the sampled floor refined to 1/64 of a top 
                                // round with and without drift; one row neutral (102.0-103.2 us)
 int g_floor_hint = -1;         // >= 0: candidate floor from the previous call's k-th key minus this many
                                // 12-bit bins (adaptive per row), no sampling launch; -1: sampled floor
-unsigned g_hist_grid = 0;      // the last call's cand_hist<10> grid per row, and the co-resident cap it
-unsigned g_hist_capacity = 0;  // was held to (blocks of that instantiation the chip holds, x 7/8): mx_topk_get
+int g_hist_grid = 0;           // the last call's cand_hist<10> grid per row, and the co-resident cap it
+int g_hist_capacity = 0;       // was held to (blocks of that instantiation the chip holds, x 7/8): mx_topk_get
 
 int g_select = 0;             // selection after the compaction: 0 = the four passes (cand_hist<10>,
                               // cand_hist<9>, cand_mark, write_cand), 1 = one launch (select_kernel; same-box
@@ -2079,77 +2058,31 @@ extern "C" int64_t mx_choco_msg_bytes(int64_t P, int64_t k) {
     return 4 * ((k + 1) / 2 * 2) + 8 * k + 4 * (n_chunks(P) + 1);
 }
 
+// mx_topk_set / mx_topk_get: the host-side knobs.  The two device-side ones (spin_ticks, compact_trace) are
+// per device and write a device symbol: handled ahead of the table.
+const mx::Knob kKnobs[] = {
+    mx::knob_range("sample_stride", &g_sample_stride, 0, INT_MAX),
+    mx::knob_range("compact_blocks", &g_compact_blocks, 0, 1 << 20),
+    mx::knob_range("cand_chunks", &g_cand_chunks, 0, 4096),
+    mx::knob_range("apply_nt", &g_apply_nt, -1, 1),
+    mx::knob_range("apply_persist", &g_apply_persist, -1, 1),
+    mx::knob_range("apply_pf", &g_apply_pf, 0, 1),
+    mx::knob_range("compact_store", &g_compact_store, 0, 1),
+    mx::knob_range("compact_wave", &g_compact_wave, 0, 1024),
+    mx::knob_range("compact_pf2", &g_compact_pf2, 0, 1),
+    mx::knob_range("select", &g_select, 0, 1),
+    mx::knob_range("fine_floor", &g_fine_floor, 0, 1),
+    mx::knob_range("floor_hint", &g_floor_hint, -1, 64),       // -1 off, 0..64 bins
+    mx::knob_bool("select_trace", &g_select_trace),
+    mx::knob_range("select_blocks", &g_select_blocks, 0, kSelMaxB),
+    mx::knob_range("sample_pieces", &g_sample_pieces, 1, 1024),
+    mx::knob_read_only("hist_grid", &g_hist_grid),
+    mx::knob_read_only("hist_capacity", &g_hist_capacity),
+};
+constexpr int kNumKnobs = sizeof(kKnobs) / sizeof(kKnobs[0]);
+
 extern "C" int mx_topk_set(const char* key, int64_t value) {
     MX_CHECK(key, "mx_topk_set: null key");
-    if (!strcmp(key, "sample_stride")) {
-        MX_CHECK(value >= 0, "mx_topk_set: sample_stride %lld", (long long)value);
-        g_sample_stride = (int)value;
-        return MX_OK;
-    }
-    if (!strcmp(key, "compact_blocks")) {
-        MX_CHECK(value >= 0 && value <= (1 << 20), "mx_topk_set: compact_blocks %lld", (long long)value);
-        g_compact_blocks = (int)value;
-        return MX_OK;
-    }
-    if (!strcmp(key, "cand_chunks")) {
-        MX_CHECK(value >= 0 && value <= 4096, "mx_topk_set: cand_chunks %lld", (long long)value);
-        g_cand_chunks = (int)value;
-        return MX_OK;
-    }
-    if (!strcmp(key, "apply_nt")) {
-        MX_CHECK(value >= -1 && value <= 1, "mx_topk_set: apply_nt %lld", (long long)value);
-        g_apply_nt = (int)value;
-        return MX_OK;
-    }
-    if (!strcmp(key, "apply_persist")) {
-        MX_CHECK(value >= -1 && value <= 1, "mx_topk_set: apply_persist %lld", (long long)value);
-        g_apply_persist = (int)value;
-        return MX_OK;
-    }
-    if (!strcmp(key, "apply_pf")) {
-        MX_CHECK(value == 0 || value == 1, "mx_topk_set: apply_pf %lld", (long long)value);
-        g_apply_pf = (int)value;
-        return MX_OK;
-    }
-    if (!strcmp(key, "compact_store")) {
-        MX_CHECK(value == 0 || value == 1, "mx_topk_set: compact_store %lld", (long long)value);
-        g_compact_store = (int)value;
-        return MX_OK;
-    }
-    if (!strcmp(key, "compact_wave")) {
-        MX_CHECK(value >= 0 && value <= 1024, "mx_topk_set: compact_wave %lld", (long long)value);
-        g_compact_wave = (int)value;
-        return MX_OK;
-    }
-    if (!strcmp(key, "compact_pf2")) {
-        MX_CHECK(value == 0 || value == 1, "mx_topk_set: compact_pf2 %lld", (long long)value);
-        g_compact_pf2 = (int)value;
-        return MX_OK;
-    }
-    if (!strcmp(key, "select")) {
-        MX_CHECK(value == 0 || value == 1, "mx_topk_set: select %lld", (long long)value);
-        g_select = (int)value;
-        return MX_OK;
-    }
-    if (!strcmp(key, "fine_floor")) {
-        MX_CHECK(value == 0 || value == 1, "mx_topk_set: fine_floor %lld", (long long)value);
-        g_fine_floor = (int)value;
-        return MX_OK;
-    }
-    if (!strcmp(key, "floor_hint")) {
-        MX_CHECK(value >= -1 && value <= 64, "mx_topk_set: floor_hint %lld (-1 off, 0..64 bins)", (long long)value);
-        g_floor_hint = (int)value;
-        return MX_OK;
-    }
-    if (!strcmp(key, "select_trace")) {
-        g_select_trace = value != 0;
-        return MX_OK;
-    }
-    if (!strcmp(key, "select_blocks")) {
-        MX_CHECK(value >= 0 && value <= kSelMaxB, "mx_topk_set: select_blocks %lld", (long long)value);
-        g_select_blocks = (int)value;
-        return MX_OK;
-    }
     if (!strcmp(key, "compact_trace")) {
         const int on = value != 0;
         MX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_ctrace_on), &on, sizeof(on)));
@@ -2163,12 +2096,9 @@ extern "C" int mx_topk_set(const char* key, int64_t value) {
         g_spin_ticks_host[cur_dev()] = v + 1;        // stored + 1: 0 marks "never set"
         return MX_OK;
     }
-    if (!strcmp(key, "sample_pieces")) {
-        MX_CHECK(value >= 1 && value <= 1024, "mx_topk_set: sample_pieces %lld", (long long)value);
-        g_sample_pieces = (int)value;
-        return MX_OK;
-    }
-    MX_CHECK(false, "mx_topk_set: unknown key '%s'", key);
+    // the table's knobs are ints: a value that would not survive the narrowing is refused, not truncated
+    MX_CHECK(value >= INT_MIN && value <= INT_MAX, "mx_topk_set: %s %lld", key, (long long)value);
+    return mx::knob_set("mx_topk_set", kKnobs, kNumKnobs, key, (int)value);
 }
 
 extern "C" int64_t mx_topk_get(const char* key) {
@@ -2177,25 +2107,7 @@ extern "C" int64_t mx_topk_get(const char* key) {
         return (int64_t)(v ? v - 1 : kSpinTicks);
     }
     if (key && !strcmp(key, "compact_trace")) return g_compact_trace[cur_dev()];
-    if (key && !strcmp(key, "sample_stride")) return g_sample_stride;
-    if (key && !strcmp(key, "compact_blocks")) return g_compact_blocks;
-    if (key && !strcmp(key, "sample_pieces")) return g_sample_pieces;
-    if (key && !strcmp(key, "cand_chunks")) return g_cand_chunks;
-    if (key && !strcmp(key, "apply_nt")) return g_apply_nt;
-    if (key && !strcmp(key, "compact_store")) return g_compact_store;
-    if (key && !strcmp(key, "apply_pf")) return g_apply_pf;
-    if (key && !strcmp(key, "apply_persist")) return g_apply_persist;
-    if (key && !strcmp(key, "compact_pf2")) return g_compact_pf2;
-    if (key && !strcmp(key, "compact_wave")) return g_compact_wave;
-    if (key && !strcmp(key, "select")) return g_select;
-    if (key && !strcmp(key, "select_blocks")) return g_select_blocks;
-    if (key && !strcmp(key, "select_trace")) return g_select_trace;
-    if (key && !strcmp(key, "hist_grid")) return g_hist_grid;
-    if (key && !strcmp(key, "floor_hint")) return g_floor_hint;
-    if (key && !strcmp(key, "fine_floor")) return g_fine_floor;
-    if (key && !strcmp(key, "hist_capacity")) return g_hist_capacity;
-    mx::set_error("mx_topk_get: unknown key '%s'", key ? key : "(null)");
-    return MX_ERR_INVALID;
+    return mx::knob_get("mx_topk_get", kKnobs, kNumKnobs, key);
 }
 
 extern "C" int mx_topk_abs_diff_rows(const float* x, const float* x_hat, int64_t ld, int nrows, int64_t P,
@@ -2242,18 +2154,14 @@ extern "C" int mx_topk_abs_diff_rows(const float* x, const float* x_hat, int64_t
     hipLaunchKernelGGL(kern, grid, dim3(tpb), 0, st, R, ##__VA_ARGS__);            \
     MX_LAUNCH_CHECK()
     if (S > 0) MX_L(sample_kernel, dim3(sgrid, nrows), kTPB, S);
-    auto ck = nrows == 1 ? (g_compact_store ? (g_compact_pf2 ? compact_kernel<true, true, true> : compact_kernel<true, true>)
-                                            : compact_kernel<true, false>)
-                         : (g_compact_store ? (g_compact_pf2 ? compact_kernel<false, true, true> : compact_kernel<false, true>)
-                                            : compact_kernel<false, false>);
+    const int one_row = nrows == 1;
     if (g_compact_wave) {
         // wave-owned chunks: about g_compact_wave chunks per wave (1 = one chunk each)
         const int64_t waves = (nc + g_compact_wave - 1) / g_compact_wave;
         const unsigned wg = clamp_grid(waves, kWaves, 65535);
-        auto cw = nrows == 1 ? compact_wave_kernel<true> : compact_wave_kernel<false>;
-        MX_L(cw, dim3(wg, nrows), kTPB, S, frac);
+        MX_L(kCompactWave[one_row], dim3(wg, nrows), kTPB, S, frac);
     } else {
-        MX_L(ck, dim3(bgrid, nrows), kTPB, S, frac);
+        MX_L(kCompact[one_row][g_compact_store][g_compact_pf2], dim3(bgrid, nrows), kTPB, S, frac);
     }
     if (g_select) {
         // the fallback compaction (S > 1, rare) runs inside select_kernel; rows in batches of at
@@ -2275,19 +2183,18 @@ extern "C" int mx_topk_abs_diff_rows(const float* x, const float* x_hat, int64_t
     // the fallback compaction (S > 1, rare) runs inside the first candidate pass, behind a row grid
     // barrier: that pass's blocks (every row's) must all be resident at once, so with sampling its
     // grid is capped at 7/8 of the chip's capacity for the instantiation (occupancy query, cached)
-    auto h10 = nrows == 1 ? (g_compact_store ? cand_hist<kMidBits, true, true> : cand_hist<kMidBits, true, false>)
-                          : (g_compact_store ? cand_hist<kMidBits, false, true> : cand_hist<kMidBits, false, false>);
+    const TopkFn h10 = kHist10[one_row][g_compact_store];
     unsigned hgrid = cgrid;
     if (S != 1) {
         const int64_t cap = hist_capacity(reinterpret_cast<const void*>(h10));
         MX_CHECK(cap >= nrows, "mx_topk_abs_diff_rows: %d rows exceed the %lld co-resident blocks of the candidate "
                  "pass (its sampled-floor fallback needs every block of a row resident)", nrows, (long long)cap);
         if ((int64_t)hgrid * nrows > cap) hgrid = (unsigned)(cap / nrows);
-        g_hist_capacity = (unsigned)cap;
+        g_hist_capacity = (int)cap;
     } else {
         g_hist_capacity = 0;
     }
-    g_hist_grid = hgrid;
+    g_hist_grid = (int)hgrid;
     MX_L(h10, dim3(hgrid, nrows), kTPB, S, frac);
     MX_L((cand_hist<kLowBits, false, false>), dim3(cgrid, nrows), kTPB, S, frac);
     const int64_t G = (nc + cgrid - 1) / cgrid;    // chunks per cand_mark block
@@ -2462,25 +2369,19 @@ int choco_apply(float* x, float* xhat, float* s, int64_t ld, int64_t P, int64_t 
     // tools/choco_slots_ab.py, profiles/r05p2_apply_forms_ab.log)
     const bool persist = n_slots <= kLdsSlots &&
                          (g_apply_persist > 0 || (g_apply_persist < 0 && slot_table && n_local == 1));
+    const ApplyDims dims{ld, P, msg_ld_bytes, kpad, k, iter, words, n_local, M, alpha, gamma};
     if (persist) {
-        auto kern = slot_table ? (nt_hint ? apply_kernel_persist<true, true> : apply_kernel_persist<false, true>)
-                               : (nt_hint ? apply_kernel_persist<true, false> : apply_kernel_persist<false, false>);
+        const ApplyPersistFn kern = kApplyPersist[nt_hint][slot_table];
         // about the co-resident workgroups over the rows, an equal tile count each
         const int64_t cap = persist_capacity(reinterpret_cast<const void*>(kern)) / n_local;
         const int64_t per = (nt + (cap > 0 ? cap : 1) - 1) / (cap > 0 ? cap : 1);
         const int64_t gx = (nt + per - 1) / per;
-        hipLaunchKernelGGL(kern, dim3((unsigned)gx, n_local), dim3(kTPB), 0, st, x, xhat, s, ld, P, m, msg_ld_bytes,
-                           kpad, k, rec, iter_dev, iter, words, n_local, M, alpha, gamma, n_slots, nt);
+        hipLaunchKernelGGL(kern, dim3((unsigned)gx, n_local), dim3(kTPB), 0, st, x, xhat, s, m, rec, iter_dev, dims, n_slots, nt);
         MX_LAUNCH_CHECK();
         return MX_OK;
     }
-    auto kern = slot_table ? (g_apply_pf ? (nt_hint ? apply_kernel_pf<true, true> : apply_kernel_pf<false, true>)
-                                         : (nt_hint ? apply_kernel<true, 16, true> : apply_kernel<false, 16, true>))
-                           : (g_apply_pf ? (nt_hint ? apply_kernel_pf<true, false> : apply_kernel_pf<false, false>)
-                                         : (nt_hint ? apply_kernel<true, 16, false> : apply_kernel<false, 16, false>));
-    hipLaunchKernelGGL(kern, dim3((unsigned)nt, n_local), dim3(kTPB),
-                       0, st, x, xhat, s, ld, P, m,
-                       msg_ld_bytes, kpad, k, rec, iter_dev, iter, words, n_local, M, alpha, gamma);
+    hipLaunchKernelGGL(kApply[g_apply_pf][nt_hint][slot_table], dim3((unsigned)nt, n_local), dim3(kTPB), 0, st, x, xhat, s, m, rec,
+                       iter_dev, dims);
     MX_LAUNCH_CHECK();
     return MX_OK;
 }

@@ -202,6 +202,75 @@ def test_mix_knobs_defaults_ranges_and_refusals(pkg):
             put(k, v)
 
 
+# mx_topk_set's table knobs: key -> (default, lowest accepted, highest accepted).  spin_ticks and compact_trace
+# write a device symbol (they need a GPU) and are not in the table.
+_INT_MAX = 2 ** 31 - 1
+TOPK_KNOBS = {
+    "sample_stride": (0, 0, _INT_MAX),
+    "compact_blocks": (0, 0, 1 << 20),
+    "cand_chunks": (0, 0, 4096),
+    "apply_nt": (-1, -1, 1),
+    "apply_persist": (-1, -1, 1),
+    "apply_pf": (1, 0, 1),
+    "compact_store": (1, 0, 1),
+    "compact_wave": (0, 0, 1024),
+    "compact_pf2": (0, 0, 1),
+    "select": (0, 0, 1),
+    "fine_floor": (1, 0, 1),
+    "floor_hint": (-1, -1, 64),
+    "select_blocks": (0, 0, 32),
+    "sample_pieces": (1, 1, 1024),
+}
+
+
+def test_topk_knobs_defaults_ranges_and_refusals(pkg):
+    """mx_topk_set / mx_topk_get, every host-side knob: the default, both bounds read back as stored, one value
+    past each bound refused (-1, the knob left as it was, key and value in mx_last_error); select_trace
+    normalised to 0 / 1; hist_grid and hist_capacity read and are unknown to set; unknown and null keys; a
+    value outside the int range (sample_stride = 2^32 would narrow to 0) refused."""
+    L = pkg.lib
+    INV = pkg._lib.MX_ERR_INVALID
+
+    def get(k):
+        return L.mx_topk_get(k.encode())
+
+    def put(k, v):
+        return L.mx_topk_set(k.encode(), v)
+
+    keys = list(TOPK_KNOBS) + ["select_trace"]
+    saved = {k: get(k) for k in keys}
+    try:
+        assert saved == {**{k: d for k, (d, _, _) in TOPK_KNOBS.items()}, "select_trace": 0}
+        for k, (default, lo, hi) in TOPK_KNOBS.items():
+            for v in (lo, hi):
+                assert put(k, v) == 0 and get(k) == v, (k, v)
+            for v in (lo - 1, hi + 1):
+                assert put(k, v) == INV, (k, v)
+                assert get(k) == hi, (k, v)
+                if -_INT_MAX - 1 <= v <= _INT_MAX:
+                    err = L.mx_last_error()
+                    assert err == f"mx_topk_set: {k} {v}".encode() or \
+                        (k == "floor_hint" and err.startswith(f"mx_topk_set: {k} {v} ".encode())), (k, v, err)
+            assert put(k, default) == 0 and get(k) == default, k
+        for v, back in ((1, 1), (0, 0), (7, 1), (-1, 1), (0, 0)):
+            assert put("select_trace", v) == 0 and get("select_trace") == back, v
+        for k in ("hist_grid", "hist_capacity"):
+            n = get(k)
+            assert n >= 0
+            assert put(k, 0) == INV and L.mx_last_error() == f"mx_topk_set: unknown key '{k}'".encode()
+            assert get(k) == n
+        assert put("no_such_knob", 1) == INV and L.mx_last_error() == b"mx_topk_set: unknown key 'no_such_knob'"
+        assert get("no_such_knob") == INV and L.mx_last_error() == b"mx_topk_get: unknown key 'no_such_knob'"
+        assert L.mx_topk_set(None, 1) == INV and b"null key" in L.mx_last_error()
+        assert L.mx_topk_get(None) == INV
+        for k in TOPK_KNOBS:                       # no silent narrowing: 2^32 is not 0, 2^32 + 1 is not 1
+            for v in (2 ** 32, 2 ** 32 + 1, -2 ** 32, 2 ** 31, -2 ** 31 - 1):
+                assert put(k, v) == INV and get(k) == TOPK_KNOBS[k][0], (k, v)
+    finally:
+        for k, v in saved.items():
+            put(k, v)
+
+
 def test_mean_rows_to_refuses_partial_overlap_and_names_kernels(pkg):
     """a destination overlapping the rows at a column offset is refused before any
     launch (host-side validation, fake device addresses); whole-row aliasing passes validation.
