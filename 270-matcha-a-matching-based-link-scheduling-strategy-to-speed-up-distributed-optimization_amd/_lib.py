@@ -124,7 +124,8 @@ def _fused_signatures(base, step):
 
 
 for _base, _step in (("mx_sgd_mix", 0), ("mx_sgd_mix_bf16", 0), ("mx_adamw_mix", 1), ("mx_adamw_mix_bf16", 1),
-                     ("mx_lion_mix", 0), ("mx_lion_mix_bf16", 0), ("mx_qgm_mix", 0), ("mx_qgm_mix_bf16", 0)):
+                     ("mx_lion_mix", 0), ("mx_lion_mix_bf16", 0), ("mx_qgm_mix", 0), ("mx_qgm_mix_bf16", 0),
+                     ("mx_gt_track", 0), ("mx_gt_track_bf16", 0), ("mx_gt_step_bf16", 0)):
     SIGNATURES.update(_fused_signatures(_base, _step))
 
 

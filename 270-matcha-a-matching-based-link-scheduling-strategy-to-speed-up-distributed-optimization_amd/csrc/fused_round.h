@@ -26,8 +26,8 @@
 // Policies without the flag compile to exactly what they did without the hook.
 //
 // An optimizer's two families (fp32 rows; bf16 rows over fp32 masters) differ only in storage, so each
-// optimizer writes ONE policy template over a storage form (Fp32Form, Bf16Form: at the end of this file) in
-// its *_update.h, beside its arithmetic and its one host function template.  A form supplies
+// optimizer writes ONE policy template over a storage form (Fp32Form, Bf16Form, and gradient tracking's
+// Bf16GradForm and Fp32GradForm: at the end of this file) in its *_update.h, beside its arithmetic and its one host function template.  A form supplies
 //     GT, GC                the gradient's element and chunk type (float / F4, uint16_t / U2)
 //     PTab                  the type of the last member `p` of every Tabs: the bf16 model rows' table (fp32: empty)
 //     zero()                the chunk stored over g
@@ -499,6 +499,66 @@ struct Bf16Form {
     template <class Tabs>
     static __device__ __forceinline__ bool al(const Tabs& tb, const Geo& gq, int k) {
         return al8(tb.g[gq.base + k]) && al8(tb.p[gq.base + k]);
+    }
+    template <int SP, class Tabs>
+    static __device__ __forceinline__ void store(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
+                                                 const F4& acc) {
+        store_chunk<SP>(tb.x[gq.base + k], c, gq.lim, vec, acc);
+        store_chunk<SP>(tb.p[gq.base + k], c, gq.lim, vec, pack4(acc));         // the model row: bf16 of the stored w
+    }
+    template <class Call>
+    static bool tables(const Call* c) {
+        return c->w_ptrs_dev && c->g_ptrs_dev && c->p_ptrs_dev;
+    }
+    template <class Update, class Call, class... S>
+    static int run(const Tune& tune, const Round& r, int bpe, const typename Update::Hyper& h, const mx_param_runs* runs,
+                   const Call* c, S... state) {
+        return dispatch<Update>(tune, r, bpe, h, runs, c->w_ptrs_dev, c->g_ptrs_dev, state..., c->p_ptrs_dev);
+    }
+};
+
+// The two forms of gradient tracking (gt_update.h), whose second gossiped array is an fp32 row that is no
+// model: its track launch mixes the tracker (no bf16 image to write), its mixed-precision step launch reads
+// the tracker where the others read a bf16 gradient.
+
+// fp32 mixed row with no model row, bf16 gradient in 8-byte accesses: Fp32Form's tables and store, Bf16Form's g
+struct Bf16GradForm {
+    using GT = uint16_t;
+    using GC = U2;
+    using PTab = NoTable;
+    static constexpr int kBytes = 10;      // x read + written, g read
+    static __device__ __forceinline__ GC zero() { return U2{0u, 0u}; }
+    template <class Tabs>
+    static __device__ __forceinline__ bool al(const Tabs& tb, const Geo& gq, int k) {
+        return al8(tb.g[gq.base + k]);
+    }
+    template <int SP, class Tabs>
+    static __device__ __forceinline__ void store(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,
+                                                 const F4& acc) {
+        store_chunk<SP>(tb.x[gq.base + k], c, gq.lim, vec, acc);
+    }
+    template <class Call>
+    static bool tables(const Call* c) {
+        return c->x_ptrs_dev && c->g_ptrs_dev;
+    }
+    template <class Update, class Call, class... S>
+    static int run(const Tune& tune, const Round& r, int bpe, const typename Update::Hyper& h, const mx_param_runs* runs,
+                   const Call* c, S... state) {
+        return dispatch<Update>(tune, r, bpe, h, runs, c->x_ptrs_dev, c->g_ptrs_dev, state...);
+    }
+};
+
+// bf16 rows over fp32 masters with an fp32 "gradient" in 16-byte accesses: Bf16Form's tables and store,
+// Fp32Form's g
+struct Fp32GradForm {
+    using GT = float;
+    using GC = F4;
+    using PTab = uint16_t* const*;
+    static constexpr int kBytes = 14;      // w read + written, g read, p written
+    static __device__ __forceinline__ GC zero() { return F4{0.0f, 0.0f, 0.0f, 0.0f}; }
+    template <class Tabs>
+    static __device__ __forceinline__ bool al(const Tabs& tb, const Geo& gq, int k) {
+        return al16(tb.g[gq.base + k]) && al8(tb.p[gq.base + k]);
     }
     template <int SP, class Tabs>
     static __device__ __forceinline__ void store(const Tabs& tb, const Geo& gq, int k, int64_t c, bool vec,

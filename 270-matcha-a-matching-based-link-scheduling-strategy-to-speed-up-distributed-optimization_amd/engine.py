@@ -753,6 +753,27 @@ class QgmBf16Call(ctypes.Structure):
                 ("omu", ctypes.c_float), ("nesterov", ctypes.c_int32), ("zero_grads", ctypes.c_int32)]
 
 
+class GtTrackCall(ctypes.Structure):
+    """mx_gt_track_call (include/matcha_gossip.h): the gradient-tracking track launch's arguments, packed once.
+    x_ptrs_dev is the tracker's table (the row the round mixes), gp_ptrs_dev the previous gradient's."""
+    _fields_ = [("x_ptrs_dev", ctypes.c_void_p), ("g_ptrs_dev", ctypes.c_void_p), ("gp_ptrs_dev", ctypes.c_void_p),
+                ("seg_len_dev", ctypes.c_void_p), ("tile_off_dev", ctypes.c_void_p), ("plan_dev", ctypes.c_void_p),
+                ("total_tiles", ctypes.c_int64), ("nseg", ctypes.c_int32), ("n_slots", ctypes.c_int32),
+                ("n_local", ctypes.c_int32), ("M", ctypes.c_int32), ("alpha", ctypes.c_float),
+                ("zero_grads", ctypes.c_int32)]
+
+
+class GtTrackBf16Call(ctypes.Structure):
+    """mx_gt_track_bf16_call (include/matcha_gossip.h): the track launch's arguments with bfloat16 gradients."""
+    _fields_ = list(GtTrackCall._fields_)
+
+
+class GtStepBf16Call(ctypes.Structure):
+    """mx_gt_step_bf16_call (include/matcha_gossip.h): the mixed-precision gradient-tracking step launch's
+    arguments: mx_sgd_mix_bf16_call's fields, g_ptrs_dev being the fp32 tracker's table."""
+    _fields_ = list(SgdBf16Call._fields_)
+
+
 SGD_TUNE_KEYS = ("nontemporal", "wgpc", "blocks_per_cu", "flat_small", "grid")
 # the QG-momentum families' own knob on top: x and mh staged with plain loads (include/matcha_gossip.h)
 QGM_TUNE_KEYS = SGD_TUNE_KEYS + ("stage_plain",)
@@ -791,6 +812,13 @@ FAMILIES = {
     ("qgm", False): _family("mx_qgm_mix", QgmMixCall, "x g m", None, False, "fused quasi-global momentum + mixing"),
     ("qgm", True): _family("mx_qgm_mix_bf16", QgmBf16Call, "w g m p", None, False,
                            "mixed-precision fused quasi-global momentum + mixing"),
+    # gradient tracking: the track launch in both gradient storages, and the mixed-precision step launch (the
+    # fp32 step launch is the ("sgd", False) family over the tracker's table)
+    ("gt", False): _family("mx_gt_track", GtTrackCall, "x g gp", None, False, "gradient-tracking track + mixing"),
+    ("gt", True): _family("mx_gt_track_bf16", GtTrackBf16Call, "x g gp", None, False,
+                          "gradient-tracking track + mixing over bfloat16 gradients"),
+    ("gt_step", True): _family("mx_gt_step_bf16", GtStepBf16Call, "w g m p", "m", False,
+                               "mixed-precision gradient-tracking step + mixing"),
 }
 
 
@@ -819,6 +847,9 @@ lion_mix_tuning, set_lion_mix_tuning = _tuning_pair(FAMILIES["lion", False])
 lion_mix_bf16_tuning, set_lion_mix_bf16_tuning = _tuning_pair(FAMILIES["lion", True])
 qgm_mix_tuning, set_qgm_mix_tuning = _tuning_pair(FAMILIES["qgm", False], QGM_TUNE_KEYS)
 qgm_mix_bf16_tuning, set_qgm_mix_bf16_tuning = _tuning_pair(FAMILIES["qgm", True], QGM_TUNE_KEYS)
+gt_track_tuning, set_gt_track_tuning = _tuning_pair(FAMILIES["gt", False])
+gt_track_bf16_tuning, set_gt_track_bf16_tuning = _tuning_pair(FAMILIES["gt", True])
+gt_step_bf16_tuning, set_gt_step_bf16_tuning = _tuning_pair(FAMILIES["gt_step", True])
 
 
 def _f32(v):
@@ -885,6 +916,24 @@ def qgm_arguments(momentum, mu, weight_decay):
     if not weight_decay >= 0.0:
         raise ValueError("attach_qgm: weight_decay must not be negative")
     return momentum, mu, weight_decay
+
+
+def gt_track_hyper(zero_grads):
+    """The track records' one word after alpha: zero_grads."""
+    return (int(bool(zero_grads)),)
+
+
+def gt_arguments(momentum, weight_decay, nesterov):
+    """attach_gt's own argument checks, a pure host function: (momentum, weight_decay, nesterov).  ValueError for
+    a momentum outside [0, 1), a negative weight decay and Nesterov without momentum."""
+    momentum, weight_decay, nesterov = float(momentum), float(weight_decay), bool(nesterov)
+    if not 0.0 <= momentum < 1.0:
+        raise ValueError(f"attach_gt: momentum {momentum} outside [0, 1)")
+    if not weight_decay >= 0.0:
+        raise ValueError("attach_gt: weight_decay must not be negative")
+    if nesterov and momentum == 0.0:
+        raise ValueError("attach_gt: Nesterov momentum requires a momentum")
+    return momentum, weight_decay, nesterov
 
 
 def pack_call(fam, tables, seg_len, tile_off, plan, bias, total_tiles, n_bias, nseg, n_slots, n_local, M, alpha32,
@@ -1042,10 +1091,51 @@ class QgmBf16Layout(FusedLayout):
     call = QgmLayout.call
 
 
+class GtTrackLayout(FusedLayout):
+    """csrc/gt_track.hip: row r's tracker of segment s (the `x` table: the row the round mixes), its gradient
+    and its previous gradient, fp32, lengths in floats."""
+    family = FAMILIES["gt", False]
+
+    def __init__(self, seg_lens, x_ptrs, g_ptrs, gp_ptrs, n_local):
+        super().__init__(seg_lens, (x_ptrs, g_ptrs, gp_ptrs), n_local)
+
+    def call(self, engine, zero_grads):
+        return self._pack(engine, gt_track_hyper(zero_grads))
+
+
+class GtTrackBf16Layout(FusedLayout):
+    """csrc/gt_track_bf16.hip: row r's fp32 tracker of segment s, its bfloat16 gradient and its fp32 previous
+    gradient, lengths in elements."""
+    family = FAMILIES["gt", True]
+
+    def __init__(self, seg_lens, x_ptrs, g_ptrs, gp_ptrs, n_local):
+        super().__init__(seg_lens, (x_ptrs, g_ptrs, gp_ptrs), n_local)
+
+    call = GtTrackLayout.call
+
+
+class GtStepBf16Layout(FusedLayout):
+    """csrc/gt_step_bf16.hip: row r's fp32 master of segment s, its fp32 tracker (the `g` table, read only), its
+    fp32 momentum buffer (m_ptrs None without momentum) and its bfloat16 model row, lengths in elements."""
+    family = FAMILIES["gt_step", True]
+
+    def __init__(self, seg_lens, w_ptrs, g_ptrs, m_ptrs, p_ptrs, n_local):
+        super().__init__(seg_lens, (w_ptrs, g_ptrs, m_ptrs, p_ptrs), n_local)
+
+    def call(self, engine, wd, mom, nesterov):
+        """no zero_grads: the step launch never writes the tracker (the record refuses the flag)"""
+        return self._pack(engine, sgd_hyper(wd, mom, nesterov, False))
+
+
 FUSED_LAYOUTS = {("sgd", False): SgdLayout, ("sgd", True): SgdBf16Layout,          # keyed as FAMILIES
                  ("adamw", False): AdamwLayout, ("adamw", True): AdamwBf16Layout,
                  ("lion", False): LionLayout, ("lion", True): LionBf16Layout,
-                 ("qgm", False): QgmLayout, ("qgm", True): QgmBf16Layout}
+                 ("qgm", False): QgmLayout, ("qgm", True): QgmBf16Layout,
+                 ("gt", False): GtTrackLayout, ("gt", True): GtTrackBf16Layout,
+                 ("gt_step", False): SgdLayout, ("gt_step", True): GtStepBf16Layout}
+
+# what attach_gt holds in _gt: the FusedState of its track launch and of its step launch
+GtState = collections.namedtuple("GtState", "track step")
 
 # what attach_sgd / attach_adamw / attach_lion hold in _sgd / _adamw / _lion: the layout, the packed call record and its address,
 # then the family's own fields side by side, so that a step reads its launch functions in one lookup
@@ -1064,10 +1154,16 @@ _FUSED_WORDS = {**_OPTIMIZER_WORDS,
                 "qgm": ("QGM", "sgd", "bfloat16 groups need fp32 master weights under quasi-global momentum")}
 
 
+# ... and gradient tracking, whose slot (_gt) holds a launch PAIR; it comes last in the others' conflict check.
+# _FUSED_WORDS keeps its four entries: they are the optimizers whose slot is one FusedState
+_GROUP_WORDS = {**_FUSED_WORDS,
+                "gt": ("gradient-tracking", "sgd", "bfloat16 groups need fp32 master weights under gradient tracking")}
+
+
 def _attached(state, opt):
-    """The FusedState in a group's _sgd / _adamw / _lion / _qgm slot, or the error of a group without one."""
+    """The state in a group's _sgd / _adamw / _lion / _qgm / _gt slot, or the error of a group without one."""
     if state is None:
-        raise MXError(f"no {_FUSED_WORDS[opt][0]} state: call attach_{opt}() first")
+        raise MXError(f"no {_GROUP_WORDS[opt][0]} state: call attach_{opt}() first")
     return state
 
 
@@ -1439,6 +1535,7 @@ class VirtualWorkerGroup:
         self._adamw = None                   # attach_adamw: the fused AdamW + mixing launch's state
         self._lion = None                    # attach_lion: the fused Lion + mixing launch's state
         self._qgm = None                     # attach_qgm: the fused quasi-global-momentum launch's state
+        self._gt = None                      # attach_gt: the gradient-tracking launch pair's state (GtState)
         self._clip = None                    # attach_*(clip_grad_norm=...): the norm launch's state (GradNorm)
         self._runs = None                    # attach_*(param_groups=...): the run tables (ParamRuns)
         self.param_runs = None               # ... and the merged run list [(start, end, weight_decay, lr_scale)]
@@ -1680,18 +1777,24 @@ class VirtualWorkerGroup:
         (fp32 CUDA [2]) then holds the consensus distance sqrt(mean_r dist[r]^2) and the norm of the mean
         row.  of=None measures the fp32 masters where master weights are attached and the group's rows
         (fp32 or bfloat16) otherwise; of="rows" the model rows; of="masters" the masters (MXError
-        without them).  The state is built on first use, per source; every source writes the same two
+        without them); of="tracker" the gradient trackers of attach_gt (MXError without them): the norm of the
+        mean row is then the norm of the mean tracker, which equals the norm of the workers' mean gradient --
+        the quantity that goes to zero at a stationary point of the average loss.  The state is built on first use, per source; every source writes the same two
         output tensors.  One GPU only: the mean needs every worker's rows on this GPU."""
         if not self._one_gpu:
             raise NotImplementedError("consensus_distance: the mean needs every worker's rows on this GPU "
                                       "(nranks = 1, no transport); a cross-GPU consensus distance is not built")
-        if of not in (None, "rows", "masters"):
-            raise ValueError(f"consensus_distance: of is None, 'rows' or 'masters', not {of!r}")
+        if of not in (None, "rows", "masters", "tracker"):
+            raise ValueError(f"consensus_distance: of is None, 'rows', 'masters' or 'tracker', not {of!r}")
+        if of == "tracker" and self._gt is None:
+            raise MXError("consensus_distance: no tracker: attach_gt() first")
         if of == "masters" and self.master_arena is None:
             raise MXError("consensus_distance: no master weights: attach_sgd / attach_adamw / attach_lion with "
                           "master_weights=True")
         masters = of == "masters" or (of is None and self.master_arena is not None)
         arena = self.master_arena if masters else self.arena
+        if of == "tracker":
+            masters, arena = "tracker", self.gt_tracker_arena
         if self.consensus_dists is None:
             self.consensus_dists = torch.zeros(self.n_local, dtype=torch.float32, device="cuda")
             self.consensus_stats = torch.zeros(2, dtype=torch.float32, device="cuda")
@@ -1707,13 +1810,13 @@ class VirtualWorkerGroup:
         """What attach_sgd / attach_adamw refuse alike, before anything is allocated; returns the layout
         class of (opt, mixed precision) and the checked clip norm."""
         who = "attach_" + opt
-        name, other, needs_master = _FUSED_WORDS[opt]
+        name, other, needs_master = _GROUP_WORDS[opt]
         clip = clip_value(clip_grad_norm, who)
         if getattr(self, "_" + opt) is not None:
             raise RuntimeError(f"{who}: already attached")
-        for o in [other] + [k for k in _FUSED_WORDS if k not in (opt, other)]:
+        for o in [other] + [k for k in _GROUP_WORDS if k not in (opt, other)]:
             if getattr(self, "_" + o) is not None:
-                raise RuntimeError(f"{who}: the group already carries {_FUSED_WORDS[o][0]} state (attach_{o})")
+                raise RuntimeError(f"{who}: the group already carries {_GROUP_WORDS[o][0]} state (attach_{o})")
         if master_weights and self.dtype != torch.bfloat16:
             raise ValueError(f"{who}: master_weights=True is for bfloat16 groups; fp32 rows are their own masters")
         if self.dtype != torch.float32 and not master_weights:
@@ -1733,19 +1836,20 @@ class VirtualWorkerGroup:
     def _state_arena(self, dtype=torch.float32):
         return torch.zeros((self.n_local, self.ld), dtype=dtype, device="cuda")
 
-    def _attach_fused(self, checked, param_groups, state, bias, hyper, call_args):
+    def _attach_fused(self, checked, param_groups, state, bias, hyper, call_args, mixed_row=None):
         """What attach_sgd / attach_adamw build alike once their own hyperparameters are checked (`checked`
         is what _fused_family returned): the gradient arena, the masters of a mixed-precision group, the
         layout over them and the optimizer's `state` arenas ({table name: arena or None}), the parameter
         groups, the call record (layout.call(engine, *call_args)), the adopted parameters' .grad views,
-        lr_dev and the clip state.  Returns the FusedState for _sgd / _adamw."""
+        lr_dev and the clip state.  Returns the FusedState for _sgd / _adamw.  mixed_row: the arena in the `x`
+        table's place where the launch mixes something other than the group's rows (attach_gt's tracker)."""
         who, cls, clip = checked
         fam = cls.family
         self.grad_arena = torch.zeros((self.n_local, self.ld), dtype=self.dtype, device="cuda")
         self.grads = self.grad_arena[:, :self.numel]
         self.master_arena = self.master_rows = None
         # x: the fp32 group's rows, their own masters; w / p: a bfloat16 group's fp32 masters and its rows
-        arenas = dict(state, g=self.grad_arena, x=self.arena, p=self.arena)
+        arenas = dict(state, g=self.grad_arena, x=self.arena if mixed_row is None else mixed_row, p=self.arena)
         if "w" in fam.tables:
             self.master_arena = self.arena.to(torch.float32)          # the exact widening, tails (zeros) included
             self.master_rows = self.master_arena[:, :self.numel]
@@ -2090,14 +2194,124 @@ class VirtualWorkerGroup:
         iteration counter, as one launch; returns seconds like communicate()."""
         return self._fused_communicate(self.qgm_step, lr)
 
+    # ------------------------------------------------------------------ gradient tracking: track + step launches
+    def attach_gt(self, momentum=0.0, weight_decay=0.0, nesterov=False, zero_grads=True, master_weights=False,
+                  clip_grad_norm=None, param_groups=None):
+        """Give the group gradient tracking (GT-DSGD, also DIGing / DSGT: Di Lorenzo & Scutari 2016; Nedic,
+        Olshevsky & Shi 2017; Pu & Nedic 2021): every worker keeps a tracker y of the network's mean gradient
+        and steps along it instead of along its own gradient, which removes the stationary error
+        (proportional to lr x gradient heterogeneity / spectral gap) that D-PSGD keeps at a constant learning
+        rate on heterogeneous shards.  The trackers are gossiped with the round's own matrix, so an iteration
+        is TWO launches on the same round: the track launch (csrc/gt_track.hip: y += g - g_prev, g_prev = g,
+        the zeros over g, the round on y) and the step launch, torch.optim.SGD's update with y in the
+        gradient's place and the round on the weights (for fp32 rows the fused SGD kernel itself over the
+        tracker arena).  mean_i y_i equals mean_i g_i after every round of any MATCHA schedule.
+
+        Allocates `grad_arena` / `grads` as attach_sgd does (adopted parameters' .grad become views of it; see
+        attach_sgd on zero_grad), `gt_tracker_arena` / `gt_tracker_rows` and `gt_prev_grad_arena` /
+        `gt_prev_grad_rows` (fp32 zeros: the first step's tracker is the gradient itself) and, with momentum,
+        `mom_arena` / `momentum_rows`.  momentum, nesterov and weight_decay are attach_sgd's and act in the
+        step launch: the weight decay is local (it is not part of the tracked gradient, so the track launch
+        never reads the weights).  zero_grads is the track launch's.  One GPU only.
+
+        master_weights=True is the bfloat16 group's form (csrc/gt_track_bf16.hip, csrc/gt_step_bf16.hip; a
+        ValueError on an fp32 group, and a bfloat16 group refuses to attach without it), as attach_sgd's: the
+        gradient arena is bfloat16, tracker, previous gradient, momentum and masters fp32, and the step launch
+        rewrites `rows` as bf16(master).
+
+        clip_grad_norm is attach_sgd's; the clip factor enters the tracked gradient (and `gt_prev_grad_rows`
+        hold the clipped values), never the step.  param_groups are attach_sgd's and change only the step
+        launch: a group of lr_scale 0 freezes its weights while its tracker still moves."""
+        checked = self._fused_family("gt", master_weights, clip_grad_norm)
+        momentum, weight_decay, nesterov = gt_arguments(momentum, weight_decay, nesterov)
+        who, track_cls, clip = checked
+        mixed = bool(master_weights)
+        step_cls = FUSED_LAYOUTS["gt_step", mixed]
+        self.gt_tracker_arena, self.gt_prev_grad_arena = self._state_arena(), self._state_arena()
+        self.gt_tracker_rows = self.gt_tracker_arena[:, :self.numel]
+        self.gt_prev_grad_rows = self.gt_prev_grad_arena[:, :self.numel]
+        self.mom_arena = self.momentum_rows = None
+        if momentum != 0.0:
+            self.mom_arena = self._state_arena()
+            self.momentum_rows = self.mom_arena[:, :self.numel]
+        self.gt_hyper = {"momentum": momentum, "weight_decay": weight_decay, "nesterov": nesterov,
+                         "zero_grads": bool(zero_grads)}
+        # the track launch: _attach_fused with the tracker in the mixed row's place.  It also builds the
+        # gradient arena, the masters of a mixed-precision group, the parameter runs, lr_dev and the clip state
+        track = self._attach_fused(checked, param_groups, {"gp": self.gt_prev_grad_arena}, None, self.gt_hyper,
+                                   (zero_grads,), mixed_row=self.gt_tracker_arena)
+        if mixed:
+            self.master_arena = self.arena.to(torch.float32)          # the exact widening, tails (zeros) included
+            self.master_rows = self.master_arena[:, :self.numel]
+        # the step launch: the SGD family's record with the tracker arena as its gradient table, no zeros over it
+        arenas = {"x": self.arena, "w": self.master_arena, "g": self.gt_tracker_arena, "m": self.mom_arena,
+                  "p": self.arena}
+        tables = [arenas[t] for t in step_cls.family.tables]
+        tables = [None if a is None else [[a[r].data_ptr()] for r in range(self.n_local)] for a in tables]
+        lay = step_cls([self.numel], *tables, self.n_local)
+        call = lay.call(self.engine, weight_decay, momentum, nesterov, *(() if mixed else (False,)))
+        self._gt = GtState(track, FusedState(lay, call, ctypes.addressof(call), *step_cls.family))
+
+    def gt_step(self, it, lr, stream=None):
+        """Enqueue one gradient-tracking iteration at learning rate `lr` on round `it`: the norm launches of a
+        clipping group, the track launch (through _scaled with the clip factors) and the step launch (through
+        _grouped with parameter groups).  Always launches -- on an all-zero round the trackers take in the
+        gradients' change and the weights step, unmixed -- and returns whether the round mixed."""
+        gt = _attached(self._gt, "gt")
+        it = self.engine.round_index(it)
+        s = stream_ptr(stream)
+        track, step = gt.track, gt.step
+        clip = self._clip
+        if clip is not None:
+            clip.enqueue(s)
+            rc = track.scaled(track.addr, clip.scale_ptr, it, lr, None, s)
+        else:
+            rc = track.run(track.addr, it, lr, None, s)
+        if rc:
+            check(rc, track.base)
+        if self._runs is not None:
+            rc = step.grouped(step.addr, self._runs.addr, None, it, lr, None, s)
+        else:
+            rc = step.run(step.addr, it, lr, None, s)
+        if rc:
+            check(rc, step.base)
+        return bool(self.engine.any_active[it])
+
+    def gt_device_round(self, stream=None):
+        """Graph-replayable gt_step: both launches read the round from `self.iter_dev` (the SAME round) and the
+        step launch the learning rate from `self.lr_dev` when the kernels run, then the counter is advanced
+        once.  A counter outside the schedule makes both launches no-ops."""
+        gt = _attached(self._gt, "gt")
+        s = stream_ptr(stream)
+        it = self.iter_dev.data_ptr()
+        args = (it, self.engine.T, 0.0, self.lr_dev.data_ptr(), s)
+        track, step = gt.track, gt.step
+        clip = self._clip
+        if clip is not None:
+            clip.enqueue(s)
+            check(track.scaled_at(track.addr, clip.scale_ptr, *args), track.base + "_scaled_at")
+        else:
+            check(track.run_at(track.addr, *args), track.base + "_at")
+        if self._runs is not None:
+            check(step.grouped_at(step.addr, self._runs.addr, None, *args), step.base + "_grouped_at")
+        else:
+            check(step.run_at(step.addr, *args), step.base + "_at")
+        check(lib.mx_iter_advance(it, 1, s), "mx_iter_advance")
+
+    def gt_communicate(self, lr):
+        """optimizer.step() + zero_grad() + communicate() of every worker under gradient tracking at the
+        group's own iteration counter, as the launch pair; returns seconds like communicate()."""
+        return self._fused_communicate(self.gt_step, lr)
+
     def state_dict(self):
         """Checkpoint: the workers' rows and the iteration counter (resume on the same schedule);
         with attach_sgd(momentum != 0) the momentum rows too, with master_weights=True the fp32
         master rows, with attach_adamw the exp_avg / exp_avg_sq rows and the step count, and with
-        attach_lion the lion_exp_avg rows (in the arena's dtype), with attach_qgm the qgm_buffer rows."""
+        attach_lion the lion_exp_avg rows (in the arena's dtype), with attach_qgm the qgm_buffer rows, with
+        attach_gt the gt_tracker and gt_prev_grad rows (and the momentum rows)."""
         state = {"kind": "decen", "iter": int(self.iter), "row_base": int(self.row_base),
                  "workers": list(self.workers), "rows": self.rows.detach().clone()}
-        if self._sgd is not None and self.momentum_rows is not None:
+        if (self._sgd is not None or self._gt is not None) and self.momentum_rows is not None:
             state["momentum_rows"] = self.momentum_rows.detach().clone()
         if self.master_rows is not None:
             state["master_rows"] = self.master_rows.detach().clone()
@@ -2109,6 +2323,9 @@ class VirtualWorkerGroup:
             state["lion_exp_avg_rows"] = self.lion_exp_avg_rows.detach().clone()
         if self._qgm is not None:
             state["qgm_buffer_rows"] = self.qgm_buffer_rows.detach().clone()
+        if self._gt is not None:
+            state["gt_tracker_rows"] = self.gt_tracker_rows.detach().clone()
+            state["gt_prev_grad_rows"] = self.gt_prev_grad_rows.detach().clone()
         return state
 
     def load_state_dict(self, state):
@@ -2117,7 +2334,7 @@ class VirtualWorkerGroup:
                 tuple(state["rows"].shape) != tuple(self.rows.shape):
             raise ValueError("checkpoint does not match this worker group")
         mom = state.get("momentum_rows")
-        have = self._sgd is not None and self.momentum_rows is not None
+        have = (self._sgd is not None or self._gt is not None) and self.momentum_rows is not None
         if mom is not None and (not have or tuple(mom.shape) != tuple(self.momentum_rows.shape)):
             raise ValueError("checkpoint carries momentum rows: attach_sgd(momentum=...) before loading it")
         master = state.get("master_rows")
@@ -2137,8 +2354,21 @@ class VirtualWorkerGroup:
         if qgm is not None and (self._qgm is None or tuple(qgm.shape) != tuple(self.qgm_buffer_rows.shape)):
             raise ValueError("checkpoint carries quasi-global momentum state (qgm_buffer rows): attach_qgm() on a "
                              "group of the same shape before loading it")
+        gt = [state.get(k) for k in ("gt_tracker_rows", "gt_prev_grad_rows")]
+        if any(a is not None for a in gt):
+            # the tracker is the running sum of the gradients' differences: without the gradient it last took in
+            # (or the other way round) the next difference is wrong for ever
+            if any(a is None for a in gt):
+                raise ValueError("checkpoint carries half of the gradient-tracking state: gt_tracker_rows and "
+                                 "gt_prev_grad_rows are only valid together")
+            if self._gt is None or any(tuple(a.shape) != tuple(self.gt_tracker_rows.shape) for a in gt):
+                raise ValueError("checkpoint carries gradient-tracking state (gt_tracker rows): attach_gt() on a "
+                                 "group of the same shape before loading it")
         with torch.no_grad():
             self.rows.copy_(state["rows"])
+            if self._gt is not None:             # a checkpoint without them: tracker and previous gradient zeros
+                for rows, a in zip((self.gt_tracker_rows, self.gt_prev_grad_rows), gt):
+                    rows.zero_() if a is None else rows.copy_(a)
             if self._qgm is not None:            # a checkpoint without them: the buffer starts as zeros
                 self.qgm_buffer_rows.zero_() if qgm is None else self.qgm_buffer_rows.copy_(qgm)
             if self._lion is not None:           # a checkpoint without them: the buffer starts as zeros

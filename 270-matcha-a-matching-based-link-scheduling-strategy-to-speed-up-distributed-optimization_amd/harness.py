@@ -198,7 +198,7 @@ class VirtualTrainer:
 
     def __init__(self, args, model_fn, n_batches, device="cuda", batched=False, graph=False, fused_sgd=False,
                  fused_adamw=False, adamw_hyper=None, clip_grad_norm=None, param_groups=None, fused_lion=False,
-                 lion_hyper=None, consensus_every=None, fused_qgm=False, qgm_hyper=None):
+                 lion_hyper=None, consensus_every=None, fused_qgm=False, qgm_hyper=None, fused_gt=False, gt_hyper=None):
         """fused_sgd=True (non-batched, uncompressed): the workers' optimizer.step() /
         zero_grad() and the gossip round run as ONE launch (VirtualWorkerGroup.attach_sgd /
         sgd_communicate, csrc/sgd_mix.hip): backward() accumulates into the group's gradient arena,
@@ -226,6 +226,13 @@ class VirtualTrainer:
         mixed precision, csrc/qgm_mix_bf16.hip): the harness's momentum, nesterov flag and weight decay 5e-4
         with mu = momentum, or what qgm_hyper (attach_qgm's keyword arguments) overrides; clip_grad_norm and
         param_groups are honoured as below; checkpoints save the qgm_buffer rows.
+
+        fused_gt=True (same conditions, not together with the other four): gradient tracking (GT-DSGD) as a
+        launch pair per iteration (VirtualWorkerGroup.attach_gt / gt_communicate, csrc/gt_track.hip and the
+        fused SGD kernel over the trackers; all-bfloat16 models in mixed precision, csrc/gt_track_bf16.hip and
+        csrc/gt_step_bf16.hip): the harness's momentum, nesterov flag and weight decay 5e-4, or what gt_hyper
+        (attach_gt's keyword arguments) overrides; clip_grad_norm and param_groups are honoured as below;
+        checkpoints save the tracker, previous-gradient and momentum rows.
 
         clip_grad_norm=X (with fused_sgd, fused_adamw or fused_lion): torch.nn.utils.clip_grad_norm_(model.parameters(),
         X) per worker inside the fused step (attach_sgd / attach_adamw's keyword: one extra read of the
@@ -280,7 +287,14 @@ class VirtualTrainer:
         if self.fused_qgm and (batched or args.compress):
             raise ValueError("fused_qgm needs per-worker (non-batched), uncompressed training: the vmap path's "
                              "gradients are fresh tensors every iteration and ChocoSGD mixes compressed messages")
-        self.fused = self.fused_sgd or self.fused_adamw or self.fused_lion or self.fused_qgm
+        self.fused_gt = bool(fused_gt)
+        if self.fused_gt and (self.fused_sgd or self.fused_adamw or self.fused_lion or self.fused_qgm):
+            raise ValueError("fused_gt, fused_qgm, fused_lion, fused_adamw and fused_sgd are mutually exclusive: the "
+                             "group carries one optimizer")
+        if self.fused_gt and (batched or args.compress):
+            raise ValueError("fused_gt needs per-worker (non-batched), uncompressed training: the vmap path's "
+                             "gradients are fresh tensors every iteration and ChocoSGD mixes compressed messages")
+        self.fused = self.fused_sgd or self.fused_adamw or self.fused_lion or self.fused_qgm or self.fused_gt
         self.clip_grad_norm = clip_grad_norm
         if clip_grad_norm is not None and not self.fused:
             raise ValueError("clip_grad_norm is honoured by the fused optimizer steps only (fused_sgd=True, "
@@ -330,6 +344,12 @@ class VirtualTrainer:
             hyper.update(qgm_hyper or {})
             self.group.attach_qgm(**hyper, master_weights=mixed, clip_grad_norm=clip_grad_norm,
                                   param_groups=param_groups)
+        if self.fused_gt:
+            # all-bfloat16 models: fp32 master weights, as above (csrc/gt_track_bf16.hip, csrc/gt_step_bf16.hip)
+            hyper = {"momentum": args.momentum, "weight_decay": 5e-4, "nesterov": args.nesterov}
+            hyper.update(gt_hyper or {})
+            self.group.attach_gt(**hyper, master_weights=mixed, clip_grad_norm=clip_grad_norm,
+                                 param_groups=param_groups)
         sync_rows(self.group.rows)
         if mixed:
             self.group.master_from_rows()                        # the masters of the synchronized rows
@@ -541,6 +561,8 @@ class VirtualTrainer:
                 comm_time += self.group.lion_communicate(lr)
             elif self.fused_qgm:
                 comm_time += self.group.qgm_communicate(lr)
+            elif self.fused_gt:
+                comm_time += self.group.gt_communicate(lr)
             else:
                 comm_time += self.communicate()              # train_mpi.py:142, all workers at once
             self._dev_iter_synced = False

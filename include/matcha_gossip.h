@@ -919,6 +919,138 @@ int mx_qgm_mix_bf16_grouped_at(const mx_qgm_mix_bf16_call* call, const mx_param_
                                const float* gscale_dev, const int64_t* iter_dev, int64_t n_iters, float lr,
                                const float* lr_dev, void* stream);
 
+/* ---------------------------------------------------------------- the hot path, gradient tracking (GT-DSGD)
+ * Gradient tracking (DIGing / DSGT / GT-DSGD: Di Lorenzo & Scutari 2016; Nedic, Olshevsky & Shi 2017; Pu &
+ * Nedic 2021) removes the stationary error that heterogeneous shards leave in D-PSGD at a constant learning
+ * rate.  Every worker keeps a tracker y of the network's mean gradient and steps along it instead of along its
+ * own gradient; the trackers are gossiped with the round's own doubly stochastic matrix, so mean_i y_i =
+ * mean_i gs_i after every round of a time-varying schedule.  One iteration is TWO launches on the same plan
+ * record (the same round), after the backward passes: the TRACK launch, then the STEP launch.
+ *
+ * Track launch (csrc/gt_track.hip; csrc/gt_track_bf16.hip for bfloat16 gradients).  Per (segment, row) three
+ * arrays -- y, the fp32 tracker (the record's x table: the row the round mixes); g, the gradient (float, or
+ * uint16_t bfloat16); gp, the fp32 previous gradient -- and per element, every line one IEEE fp32 rounding:
+ *   gs = f32(g)                 fp32 g as it is, bf16 g widened exactly (bits << 16); multiplied by the row's
+ *                               clip factor where there is one (_scaled: g' = fmul(gscale[r], f32(g)))
+ *   t  = fsub(gs, gp)
+ *   y' = fadd(y, t)
+ *   gp = gs                     always fp32, clip factor included: the differences telescope exactly as the
+ *                               tracker saw them
+ *   g  = 0                      when zero_grads != 0
+ *   y  = mx_sgd_mix's round on the y' values (same plan record, alpha, selfweight, ascending matchings, self
+ *        term last, one fma per step; a row the record leaves alone, and every row of an all-zero round,
+ *        keeps y' as it is)
+ * y and gp start as zeros and there is no first-step case: y' = g falls out.  The launch has no learning rate
+ * and no weight decay -- weight decay is local and sits in the step launch, so the track launch never reads the
+ * weights.  The family signature is the other families': lr, lr_dev and (for _grouped) the parameter runs are
+ * accepted and UNUSED (a non-NULL runs record is still checked for null tables).  Traffic: 20 bytes per element
+ * (24 with zero_grads); 18 / 20 with bfloat16 gradients.  Alignment rule: wide accesses (16 bytes on y, gp and
+ * fp32 g, 8 bytes on bf16 g) where the three pointers of a (segment, row) are so aligned and the 4 elements are
+ * in range, per element elsewhere.  Nothing is written at or past seg_len of a row in any array.  The other
+ * record fields, the tile (1024 / 1024 / 512 / 256 columns, 0 above 64 rows), the layout prefix, the host-side
+ * refusals (MX_ERR_INVALID, nothing launched: n_slots != n_local, more than 64 rows, M outside [1, 32], a null
+ * table, iter < 0) and the launch-side no-ops (a peer-reads plan record; for _at a counter outside
+ * [0, n_iters): y, g and gp are not written) are mx_sgd_mix's.  The knobs are mx_sgd_mix_set's, each family's
+ * own.  Speed only, never bits.
+ *
+ * Step launch: torch.optim.SGD's update with the tracker in the gradient's place,
+ *   d  = (wd_r != 0) ? fmaf(wd_r, x, y) : y
+ *   m  = fadd(fmul(mom, m), d);  d = nesterov ? fmaf(mom, m, d) : m      [mom != 0]
+ *   x' = fmaf(-lr_r, d, x)
+ *   x  = the round on the x' values;  p = bf16_rne(x) in the mixed-precision form
+ * For fp32 rows it IS mx_sgd_mix (and _grouped, _at), called with a second mx_sgd_mix_call whose g_ptrs_dev is
+ * the tracker's table and whose zero_grads is 0.  For bfloat16 rows over fp32 masters it is mx_gt_step_bf16
+ * (csrc/gt_step_bf16.hip): mx_sgd_mix_bf16 with a float g table (the tracker, 16-byte accesses).  Its record is
+ * mx_sgd_mix_bf16_call with that one type changed; zero_grads != 0 is refused (the launch never writes y), and
+ * so is a non-NULL gscale_dev (the clip factor entered the tracker in the track launch).  Traffic: 22 bytes per
+ * element with momentum, 14 without (fp32: mx_sgd_mix's 20 / 12). */
+typedef struct mx_gt_track_call {
+    float* const* x_ptrs_dev;              /* the tracker y */
+    float* const* g_ptrs_dev;
+    float* const* gp_ptrs_dev;
+    const int64_t* seg_len_dev;
+    const int64_t* tile_off_dev;
+    const int32_t* plan_dev;
+    int64_t total_tiles;
+    int32_t nseg, n_slots, n_local, M;
+    float alpha;
+    int32_t zero_grads;
+} mx_gt_track_call;
+int mx_gt_track_tile(int n_slots);
+int mx_gt_track_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host);
+int mx_gt_track_set(const char* key, int value);
+int mx_gt_track_get(const char* key);
+int mx_gt_track(const mx_gt_track_call* call, int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_gt_track_at(const mx_gt_track_call* call, const int64_t* iter_dev, int64_t n_iters, float lr,
+                   const float* lr_dev, void* stream);
+int mx_gt_track_scaled(const mx_gt_track_call* call, const float* gscale_dev, int64_t iter, float lr,
+                       const float* lr_dev, void* stream);
+int mx_gt_track_scaled_at(const mx_gt_track_call* call, const float* gscale_dev, const int64_t* iter_dev,
+                          int64_t n_iters, float lr, const float* lr_dev, void* stream);
+int mx_gt_track_grouped(const mx_gt_track_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                        int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_gt_track_grouped_at(const mx_gt_track_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                           const int64_t* iter_dev, int64_t n_iters, float lr, const float* lr_dev, void* stream);
+
+typedef struct mx_gt_track_bf16_call {
+    float* const* x_ptrs_dev;              /* the tracker y */
+    uint16_t* const* g_ptrs_dev;
+    float* const* gp_ptrs_dev;
+    const int64_t* seg_len_dev;
+    const int64_t* tile_off_dev;
+    const int32_t* plan_dev;
+    int64_t total_tiles;
+    int32_t nseg, n_slots, n_local, M;
+    float alpha;
+    int32_t zero_grads;
+} mx_gt_track_bf16_call;
+int mx_gt_track_bf16_tile(int n_slots);
+int mx_gt_track_bf16_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host);
+int mx_gt_track_bf16_set(const char* key, int value);
+int mx_gt_track_bf16_get(const char* key);
+int mx_gt_track_bf16(const mx_gt_track_bf16_call* call, int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_gt_track_bf16_at(const mx_gt_track_bf16_call* call, const int64_t* iter_dev, int64_t n_iters, float lr,
+                        const float* lr_dev, void* stream);
+int mx_gt_track_bf16_scaled(const mx_gt_track_bf16_call* call, const float* gscale_dev, int64_t iter, float lr,
+                            const float* lr_dev, void* stream);
+int mx_gt_track_bf16_scaled_at(const mx_gt_track_bf16_call* call, const float* gscale_dev, const int64_t* iter_dev,
+                               int64_t n_iters, float lr, const float* lr_dev, void* stream);
+int mx_gt_track_bf16_grouped(const mx_gt_track_bf16_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                             int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_gt_track_bf16_grouped_at(const mx_gt_track_bf16_call* call, const mx_param_runs* runs,
+                                const float* gscale_dev, const int64_t* iter_dev, int64_t n_iters, float lr,
+                                const float* lr_dev, void* stream);
+
+typedef struct mx_gt_step_bf16_call {
+    float* const* w_ptrs_dev;
+    float* const* g_ptrs_dev;              /* the tracker y: read only */
+    float* const* m_ptrs_dev;
+    uint16_t* const* p_ptrs_dev;
+    const int64_t* seg_len_dev;
+    const int64_t* tile_off_dev;
+    const int32_t* plan_dev;
+    int64_t total_tiles;
+    int32_t nseg, n_slots, n_local, M;
+    float alpha, wd, mom;
+    int32_t nesterov, zero_grads, pad_;    /* zero_grads must be 0 */
+} mx_gt_step_bf16_call;
+int mx_gt_step_bf16_tile(int n_slots);
+int mx_gt_step_bf16_layout(const int64_t* seg_len_host, int nseg, int n_slots, int64_t* tile_off_host);
+int mx_gt_step_bf16_set(const char* key, int value);
+int mx_gt_step_bf16_get(const char* key);
+int mx_gt_step_bf16(const mx_gt_step_bf16_call* call, int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_gt_step_bf16_at(const mx_gt_step_bf16_call* call, const int64_t* iter_dev, int64_t n_iters, float lr,
+                       const float* lr_dev, void* stream);
+int mx_gt_step_bf16_scaled(const mx_gt_step_bf16_call* call, const float* gscale_dev, int64_t iter, float lr,
+                           const float* lr_dev, void* stream);
+int mx_gt_step_bf16_scaled_at(const mx_gt_step_bf16_call* call, const float* gscale_dev, const int64_t* iter_dev,
+                              int64_t n_iters, float lr, const float* lr_dev, void* stream);
+int mx_gt_step_bf16_grouped(const mx_gt_step_bf16_call* call, const mx_param_runs* runs, const float* gscale_dev,
+                            int64_t iter, float lr, const float* lr_dev, void* stream);
+int mx_gt_step_bf16_grouped_at(const mx_gt_step_bf16_call* call, const mx_param_runs* runs,
+                               const float* gscale_dev, const int64_t* iter_dev, int64_t n_iters, float lr,
+                               const float* lr_dev, void* stream);
+
 /* ---------------------------------------------------------------- flatten / unflatten
  * mx_gather replaces flatten_tensors (comm_helpers.py:12-30): flat[off[s] + i] = src[s][i].
  * mx_scatter is the copy_ loop of reset_model over unflatten_tensors views

@@ -5,8 +5,8 @@
     make -C <package> EXTRA=-Rpass-analysis=kernel-resource-usage 2> after.log       (the other)
     tools/resource_compare.py before.log after.log [--show SUBSTRING ...] > profiles/<name>.txt
 
-Every fused_round_rows instantiation present in both logs is compared on VGPRs, SGPRs, LDS, scratch and
-waves per SIMD; the differing ones are listed (none: one line says so).  Instantiations whose demangled name
+Every fused_round_rows instantiation present in both logs is compared on VGPRs, SGPRs, LDS, scratch,
+waves per SIMD and SGPR / VGPR spills; the differing ones are listed (none: one line says so).  Instantiations whose demangled name
 holds one of the --show substrings are printed in full, new ones included."""
 import argparse
 import collections
@@ -14,7 +14,8 @@ import re
 import subprocess
 
 FIELDS = (("VGPRs", "vgpr"), ("TotalSGPRs", "sgpr"), ("LDS Size [bytes/block]", "lds"),
-          ("ScratchSize [bytes/lane]", "scratch"), ("Occupancy [waves/SIMD]", "waves"))
+          ("ScratchSize [bytes/lane]", "scratch"), ("Occupancy [waves/SIMD]", "waves"),
+          ("SGPRs Spill", "sspill"), ("VGPRs Spill", "vspill"))
 
 
 def parse(path):
@@ -69,7 +70,7 @@ def main():
     other_differ = [n for n in other if before[n] != after[n]]
     print(f"other kernels in both builds: {len(other)}, of which {len(other_differ)} differ")
     if not differ:
-        print("every instantiation present in both builds: VGPRs, SGPRs, LDS, scratch and waves per SIMD unchanged")
+        print("every instantiation present in both builds: VGPRs, SGPRs, LDS, scratch, waves per SIMD and spills unchanged")
     for n in differ + other_differ:
         print("CHANGED", short(names[n]))
         print("   before", row(before[n]))

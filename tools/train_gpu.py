@@ -9,6 +9,7 @@
     python tools/train_gpu.py --lr 1e-4 --no-warmup --fused-lion --wd 1e-2 --bf16 --lion-bf16-momentum
                                                                                 # Lion fused in, 18 bytes / parameter
     python tools/train_gpu.py --fused-qgm --qgm-mu 0.9 --nesterov --bf16          # quasi-global momentum fused in
+    python tools/train_gpu.py --fused-gt --momentum 0.9 --nesterov --bf16         # gradient tracking (GT-DSGD)
     torchrun --nproc-per-node N --master-addr 127.0.0.1 tools/train_gpu.py     # one worker per GPU
 
 Flags follow train_mpi.py:205-231 (same names and defaults where they apply); --workers,
@@ -64,6 +65,9 @@ def main():
                     "--nesterov --qgm-mu; weight decay 5e-4 as --fused-sgd)")
     ap.add_argument("--qgm-mu", default=None, type=float, metavar="X", help="--fused-qgm: the buffer's own averaging "
                     "factor mu in [0, 1) (default: --momentum, the paper's setting)")
+    ap.add_argument("--fused-gt", action="store_true", help="as --fused-sgd with gradient tracking (GT-DSGD): every "
+                    "worker steps along a gossiped tracker of the mean gradient, two launches per iteration "
+                    "(--momentum --nesterov; weight decay 5e-4 as --fused-sgd)")
     ap.add_argument("--beta1", default=0.9, type=float)
     ap.add_argument("--beta2", default=None, type=float, help="default 0.999 (--fused-adamw) / 0.99 (--fused-lion)")
     ap.add_argument("--eps", default=1e-8, type=float)
@@ -83,7 +87,7 @@ def main():
                     "the workers are after every K-th iteration's round (one read of the rows, no host wait per "
                     "round) and print the consensus distance and its ratio to the norm of the mean per epoch")
     a = ap.parse_args()
-    fused = a.fused_sgd or a.fused_adamw or a.fused_lion or a.fused_qgm
+    fused = a.fused_sgd or a.fused_adamw or a.fused_lion or a.fused_qgm or a.fused_gt
     if a.qgm_mu is not None and not a.fused_qgm:
         ap.error("--qgm-mu is the quasi-global momentum step's: add --fused-qgm")
     if a.consensus_every is not None and a.consensus_every < 1:
@@ -132,7 +136,7 @@ def main():
                               fused_lion=a.fused_lion,
                               lion_hyper={"betas": (a.beta1, 0.99 if a.beta2 is None else a.beta2), "weight_decay": a.wd,
                                           "momentum_dtype": torch.bfloat16 if a.lion_bf16_momentum else torch.float32},
-                              fused_qgm=a.fused_qgm, qgm_hyper={"mu": a.qgm_mu},
+                              fused_qgm=a.fused_qgm, qgm_hyper={"mu": a.qgm_mu}, fused_gt=a.fused_gt,
                               clip_grad_norm=a.clip_grad_norm,
                               param_groups=[{"params": lambda name, p: p.ndim <= 1, "weight_decay": 0.0}]
                               if a.no_decay_1d else None, consensus_every=a.consensus_every)
