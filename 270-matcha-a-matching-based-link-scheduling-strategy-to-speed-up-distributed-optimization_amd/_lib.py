@@ -88,6 +88,10 @@ SIGNATURES = {
     "mx_mean_rows": (c_int, [c_p, c_int, c_i64, c_i64, c_int, c_p, c_p]),
     "mx_mean_rows_to": (c_int, [c_p, c_int, c_i64, c_i64, c_int, c_p, c_int, c_i64, c_p]),
     "mx_mean_kernel_name": (ctypes.c_char_p, [c_p, c_int, c_i64, c_i64, c_int, c_p, c_int, c_i64]),
+    "mx_slowmo_step": (c_int, [c_p, c_f32, c_p, c_p]),
+    "mx_slowmo_set": (c_int, [ctypes.c_char_p, c_int]),
+    "mx_slowmo_get": (c_int, [ctypes.c_char_p]),
+    "mx_slowmo_kernel_name": (ctypes.c_char_p, [c_p]),
     "mx_pull_gate": (c_int, [c_p, c_p, c_int, c_p, c_int, c_p, c_p, c_int, c_int, c_int, c_int, c_i64, c_int, c_u64,
                              c_p, c_int, c_f64, c_p, c_p]),
     "mx_host_words": (c_int, [c_int, c_p, c_p]),

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "mx_common.h"
+#include "row_sum.h"
 
 #define MX_NCCL(call)                                                                       \
     do {                                                                                    \
@@ -338,11 +339,10 @@ __global__ void div_kernel(float* __restrict__ x, int64_t n, float d) {
 // out[i] = (sum of rows[0..nrows)[i] in the reference's order) / nrows, fp32 adds, one rounding
 // each (no contraction: -ffp-contract=off), then one correctly rounded division -- the
 // centralizedCommunicator's comm.allreduce(obj, MPI.SUM) + div_(size) (communicator.py:61-62):
-//   TREE = 1  mpi4py's default object all-reduce (rc.fast_reduce): a binomial-tree reduction to
-//             rank 0 -- at mask 1, 2, 4, ... rank r (a multiple of 2 * mask) adds the partial
-//             sum of rank r + mask -- then a broadcast: ((x0 + x1) + (x2 + x3)) + ((x4 + x5) + ...)
-//   TREE = 0  rank order ((x0 + x1) + x2) + ... (mpi4py with fast_reduce off: allgather, then
-//             functools-style left fold)
+//   TREE = 1  mpi4py's default object all-reduce (rc.fast_reduce), a binomial-tree reduction to
+//             rank 0, then a broadcast: row_sum.h's tree_order
+//   TREE = 0  rank order (mpi4py with fast_reduce off): row_sum.h's rank_order
+// The two orders are written once, in row_sum.h, which the SlowMo outer step (slowmo.hip) includes too.
 // MAXR bounds nrows; the tree runs over a register array with compile-time indices.
 //   TREE = 2  the same binomial tree for any nrows, row by row: a binary counter of partial sums
 //             (stack[l] = the sum of the last complete block of 2^l rows; pushing a row merges
@@ -389,11 +389,7 @@ __global__ __launch_bounds__(256) void mean_to_kernel(const V* rows, int nrows, 
 #pragma unroll
             for (int r = 0; r < MAXR; ++r)
                 v[r] = r < nrows ? __builtin_nontemporal_load(rows + (int64_t)r * ld + i) : V(0.0f);
-#pragma unroll
-            for (int m = 1; m < MAXR; m <<= 1)
-#pragma unroll
-                for (int r = 0; r + m < MAXR; r += 2 * m)
-                    if (r + m < nrows) v[r] = v[r] + v[r + m];
+            mx::rowsum::tree_sum<MAXR>(v, nrows);
             acc = v[0];
         } else {
             acc = __builtin_nontemporal_load(rows + i);
@@ -421,13 +417,10 @@ __global__ __launch_bounds__(256) void mean4_kernel(const f4v* rows, int nrows, 
                     v[r][u] = (r < nrows && i < count) ? __builtin_nontemporal_load(rows + (int64_t)r * ld + i)
                                                        : f4v(0.0f);
                 }
+            mx::rowsum::tree_order<8>(nrows, [&](int i, int j) __attribute__((always_inline)) {
 #pragma unroll
-            for (int m = 1; m < 8; m <<= 1)
-#pragma unroll
-                for (int r = 0; r + m < 8; r += 2 * m)
-                    if (r + m < nrows)
-#pragma unroll
-                        for (int u = 0; u < U; ++u) v[r][u] = v[r][u] + v[r + m][u];
+                for (int u = 0; u < U; ++u) v[i][u] = v[i][u] + v[j][u];
+            });
 #pragma unroll
             for (int u = 0; u < U; ++u) acc[u] = v[0][u];
         } else {
@@ -478,21 +471,10 @@ __global__ __launch_bounds__(256) void mean_tile_kernel(const f4v* rows, int nro
     f4v v[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) v[r] = lds[r * C4 + c];
-    f4v acc;
-    if (TREE) {
-#pragma unroll
-        for (int m = 1; m < 8; m <<= 1)
-#pragma unroll
-            for (int r = 0; r + m < 8; r += 2 * m)
-                if (r + m < nrows) v[r] = v[r] + v[r + m];
-        acc = v[0];
-    } else {
-        acc = v[0];
-#pragma unroll
-        for (int r = 1; r < 8; ++r)
-            if (r < nrows) acc = acc + v[r];
-    }
-    const f4v m = acc / size;
+    const auto add = [&](int i, int j) __attribute__((always_inline)) { v[i] = v[i] + v[j]; };
+    if (TREE) mx::rowsum::tree_order<8>(nrows, add);
+    else mx::rowsum::rank_order<8>(nrows, add);
+    const f4v m = v[0] / size;
     for (int d = h; d < ndst; d += 2) mx::store16<SP>(dst + (int64_t)d * dst_ld + c0 + c, m);
 }
 

@@ -13,6 +13,7 @@ Per round (reference: decenCommunicator.communicate, communicator.py:133-158):
 Everything is enqueued on one HIP stream; nothing is copied to or from the host per round.
 """
 import collections
+import contextlib
 import ctypes
 import math
 import sys
@@ -88,6 +89,19 @@ def consensus_tuning():
 def set_consensus_tuning(**knobs):
     for k, v in knobs.items():
         check(lib.mx_consensus_set(k.encode(), int(v)), "mx_consensus_set")
+
+
+SLOWMO_TUNE_KEYS = ("store_policy", "wgpc")
+
+
+def slowmo_tuning():
+    """Current knobs of the SlowMo outer-step kernel (mx_slowmo_set)."""
+    return {k: int(lib.mx_slowmo_get(k.encode())) for k in SLOWMO_TUNE_KEYS}
+
+
+def set_slowmo_tuning(**knobs):
+    for k, v in knobs.items():
+        check(lib.mx_slowmo_set(k.encode(), int(v)), "mx_slowmo_set")
 
 
 def clip_value(clip_grad_norm, who):
@@ -1245,6 +1259,31 @@ class Consensus:
             check(rc, "mx_consensus")
 
 
+class SlowmoCall(ctypes.Structure):
+    """mx_slowmo_call (include/matcha_gossip.h): the SlowMo outer step's arguments, packed once."""
+    _fields_ = [("rows", ctypes.c_void_p), ("a", ctypes.c_void_p), ("u", ctypes.c_void_p), ("p", ctypes.c_void_p),
+                ("ld", ctypes.c_int64), ("p_ld", ctypes.c_int64), ("count", ctypes.c_int64),
+                ("n_local", ctypes.c_int32), ("order", ctypes.c_int32), ("alpha", ctypes.c_float),
+                ("beta", ctypes.c_float)]
+
+
+SLOWMO_BUFFERS = ("maintain", "reset", "average")
+# fused family (a group's slot) -> the arenas that count as its momentum-like state at an outer step, by
+# attribute name.  Gradient tracking's tracker and previous gradient are not among them: the mean tracker is
+# what that algorithm preserves
+_SLOWMO_STATE = {
+    "sgd": ("mom_arena",),
+    "gt": ("mom_arena",),
+    "adamw": ("exp_avg_arena", "exp_avg_sq_arena"),
+    "lion": ("lion_exp_avg_arena",),
+    "qgm": ("qgm_buffer_arena",),
+}
+
+# what attach_slowmo holds in _slowmo: the call record and its address, the buffer strategy, the state arenas
+# it acts on and whether the family counts optimizer steps (AdamW: "reset" restarts the count)
+SlowmoState = collections.namedtuple("SlowmoState", ("call", "addr", "buffers", "arenas", "adam", "order"))
+
+
 IDLE_MODES = {"skip": 0, "canonical": 1}
 
 
@@ -1536,6 +1575,9 @@ class VirtualWorkerGroup:
         self._lion = None                    # attach_lion: the fused Lion + mixing launch's state
         self._qgm = None                     # attach_qgm: the fused quasi-global-momentum launch's state
         self._gt = None                      # attach_gt: the gradient-tracking launch pair's state (GtState)
+        self._slowmo = None                  # attach_slowmo: the outer step's state (SlowmoState)
+        self.slowmo_anchor = self.slowmo_momentum = None
+        self.lr_dev = None                   # the device rounds' learning rate (attach_*: a 1-element fp32 CUDA tensor)
         self._clip = None                    # attach_*(clip_grad_norm=...): the norm launch's state (GradNorm)
         self._runs = None                    # attach_*(param_groups=...): the run tables (ParamRuns)
         self.param_runs = None               # ... and the merged run list [(start, end, weight_decay, lr_scale)]
@@ -1814,6 +1856,9 @@ class VirtualWorkerGroup:
         clip = clip_value(clip_grad_norm, who)
         if getattr(self, "_" + opt) is not None:
             raise RuntimeError(f"{who}: already attached")
+        if self._slowmo is not None:
+            raise RuntimeError(f"{who}: the group already carries SlowMo state: attach_slowmo() comes after the "
+                               "base optimizer (it resolves the optimizer's state arenas and masters once)")
         for o in [other] + [k for k in _GROUP_WORDS if k not in (opt, other)]:
             if getattr(self, "_" + o) is not None:
                 raise RuntimeError(f"{who}: the group already carries {_GROUP_WORDS[o][0]} state (attach_{o})")
@@ -2303,12 +2348,147 @@ class VirtualWorkerGroup:
         group's own iteration counter, as the launch pair; returns seconds like communicate()."""
         return self._fused_communicate(self.gt_step, lr)
 
+    # ------------------------------------------------------------------ SlowMo: the outer step across iterations
+    def attach_slowmo(self, beta=0.5, alpha=1.0, buffers="maintain", order=0):
+        """Give the group SlowMo's outer step (Wang, Tantia, Ballas, Rabbat, ICLR 2020): every tau iterations
+        of the base optimizer -- any attach_* family, or plain rounds -- slowmo_step(lr) replaces every
+        worker's row by one common point in ONE launch (csrc/slowmo.hip): the exact average of the rows in
+        mx_mean_rows' order `order` (0 the binomial tree, 1 rank order), then
+            u' = beta * u + (a - mean) / lr;   a' = a - alpha * lr * u';   every row = a'
+        with the contract's roundings (include/matcha_gossip.h).  beta = 0, alpha = 1 is the periodic exact
+        average alone.  Call it AFTER the base optimizer's attach_*: the state arenas and the masters are
+        resolved here, once.
+
+        Allocates `slowmo_anchor` (a, the common point of the last outer step: a copy of local row 0, the
+        master row where masters exist -- the workers are expected to be in sync, as the harness leaves them)
+        and `slowmo_momentum` (u, zeros), fp32 [numel] views of ld-sized buffers, one pair per group, and
+        `lr_dev` if no fused family has.  On a mixed-precision group the step averages and rewrites the fp32
+        MASTERS and writes `rows` as bf16(master), so nothing has to be remembered afterwards; a bfloat16
+        group without masters is refused.  Call slowmo_anchor_from_rows() after anything else that rewrites
+        the rows (sync_rows, a checkpoint loaded by hand).
+
+        buffers: what an outer step does to the base optimizer's momentum-like state -- SGD's and gradient
+        tracking's momentum, AdamW's exp_avg and exp_avg_sq, Lion's exp_avg, QGM's buffer; gradient tracking's
+        tracker and previous gradient are never touched.  "maintain" (default) leaves it alone; "reset" (the
+        paper's choice) makes it that of a freshly attached optimizer: the arenas are zeroed on the stream and
+        AdamW's step count restarts; "average" is mx_mean_rows_to in place on every fp32 arena, in the same
+        order.  Anything but "maintain" needs an attached family, and "average" an fp32 state.
+
+        For a local row count that is not a power of two (in rank order: above 2) the pinned-order mean of
+        identical values can differ from the value in the last place, so a synced state is not an exact fixed
+        point there.
+        One GPU only: across GPUs the exact average is an all-reduce, another launch sequence."""
+        who = "attach_slowmo"
+        if not self._one_gpu or self.engine.max_remote:
+            raise NotImplementedError(f"{who}: one GPU only (nranks = 1, no transport): the average needs every "
+                                      "worker's row on this GPU")
+        if self._slowmo is not None:
+            raise RuntimeError(f"{who}: already attached")
+        beta, alpha = float(beta), float(alpha)
+        if not 0.0 <= float(np.float32(beta)) < 1.0:
+            raise ValueError(f"{who}: beta={beta} outside [0, 1)")
+        if not (math.isfinite(alpha) and 0.0 < float(np.float32(alpha)) < math.inf):
+            raise ValueError(f"{who}: alpha={alpha} must be finite and > 0")
+        if order not in (0, 1):
+            raise ValueError(f"{who}: order is 0 (binomial tree) or 1 (rank order), not {order!r}")
+        if buffers not in SLOWMO_BUFFERS:
+            raise ValueError(f"{who}: buffers is one of {SLOWMO_BUFFERS}, not {buffers!r}")
+        if self.n_local > 64:
+            raise NotImplementedError(f"{who}: {self.n_local} local rows exceed the outer-step kernel's 64")
+        mixed = self.dtype == torch.bfloat16
+        if mixed and self.master_arena is None:
+            raise ValueError(f"{who}: a bfloat16 group needs fp32 master weights for the outer step: attach an "
+                             "optimizer with master_weights=True first")
+        family = next((k for k in _SLOWMO_STATE if getattr(self, "_" + k) is not None), None)
+        if family is None and buffers != "maintain":
+            raise ValueError(f"{who}: buffers={buffers!r} acts on a fused optimizer's state and the group has "
+                             "none attached: attach_sgd / attach_adamw / attach_lion / attach_qgm / attach_gt "
+                             "first, or buffers='maintain'")
+        arenas = [] if family is None else [getattr(self, name) for name in _SLOWMO_STATE[family]]
+        arenas = [a for a in arenas if a is not None]                   # SGD without momentum has none
+        if buffers == "average" and any(a.dtype != torch.float32 for a in arenas):
+            raise ValueError(f"{who}: buffers='average' is mx_mean_rows_to on fp32 arenas; the bfloat16 Lion "
+                             "momentum has no such mean: 'reset' or 'maintain'")
+        self._slowmo_bufs = torch.zeros((2, self.ld), dtype=torch.float32, device="cuda")
+        self.slowmo_anchor = self._slowmo_bufs[0, :self.numel]
+        self.slowmo_momentum = self._slowmo_bufs[1, :self.numel]
+        x = self.master_arena if mixed else self.arena
+        call = SlowmoCall(x.data_ptr(), self._slowmo_bufs[0].data_ptr(), self._slowmo_bufs[1].data_ptr(),
+                          self.arena.data_ptr() if mixed else None, self.ld, self.ld, self.numel, self.n_local,
+                          int(order), alpha, beta)
+        if self.lr_dev is None:
+            self.lr_dev = torch.zeros(1, dtype=torch.float32, device="cuda")
+        self.slowmo_hyper = {"beta": beta, "alpha": alpha, "buffers": buffers, "order": int(order)}
+        self._slowmo = SlowmoState(call, ctypes.addressof(call), buffers, arenas, family == "adamw", int(order))
+        self.slowmo_anchor_from_rows()
+
+    def _slowmo_state(self, who):
+        if self._slowmo is None:
+            raise MXError(f"{who}: no SlowMo state: call attach_slowmo() first")
+        return self._slowmo
+
+    def slowmo_anchor_from_rows(self):
+        """Redo the anchor as a copy of local row 0 (the master row where masters exist), in the spirit of
+        master_from_rows(): call it after anything but slowmo_step that rewrites the rows.  The slow momentum
+        is left as it is."""
+        self._slowmo_state("slowmo_anchor_from_rows")
+        with torch.no_grad():
+            self.slowmo_anchor.copy_((self.master_rows if self.master_rows is not None else self.rows)[0])
+
+    def slowmo_kernel_name(self):
+        """The kernel slowmo_step launches for this group (mx_slowmo_kernel_name), for reports."""
+        return lib.mx_slowmo_kernel_name(self._slowmo_state("slowmo_kernel_name").addr).decode()
+
+    def _slowmo_buffers(self, st, s, stream, host):
+        """The buffer strategy's launches after the outer step, on the same stream; host: also restart
+        AdamW's host step count (the eager form)."""
+        if st.buffers == "maintain":
+            return
+        if st.buffers == "average":
+            for a in st.arenas:
+                check(lib.mx_mean_rows_to(a.data_ptr(), self.n_local, self.ld, self.numel, st.order, a.data_ptr(),
+                                          self.n_local, self.ld, s), "mx_mean_rows_to")
+            return
+        with torch.no_grad(), (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+            for a in st.arenas:
+                a.zero_()
+            if st.adam:
+                self.opt_step_dev.fill_(1)
+        if st.adam and host:
+            self.opt_step = 0
+
+    def slowmo_step(self, lr, stream=None):
+        """Enqueue the outer step at the base optimizer's learning rate `lr` (finite and > 0): ONE launch,
+        then the buffer strategy's launches (none for "maintain").  It does not advance `iter`: the next
+        round is the schedule's next.  Afterwards every row equals `slowmo_anchor`."""
+        st = self._slowmo_state("slowmo_step")
+        lr = float(lr)
+        if not (math.isfinite(lr) and 0.0 < float(np.float32(lr)) < math.inf):
+            raise ValueError(f"slowmo_step: lr={lr} must be finite and > 0")
+        s = stream_ptr(stream)
+        rc = lib.mx_slowmo_step(st.addr, lr, None, s)
+        if rc:
+            check(rc, "mx_slowmo_step")
+        self._slowmo_buffers(st, s, stream, True)
+
+    def slowmo_device_step(self, stream=None):
+        """Graph-replayable slowmo_step: the learning rate is read from `self.lr_dev` when the kernel runs, so
+        one captured step serves every learning rate.  A learning rate of exactly 0 there makes the outer
+        step's launch a complete no-op; the buffer strategy's launches run regardless.  With "reset" on an
+        AdamW group `opt_step_dev` restarts and `opt_step`, the host counter, is not touched (as
+        adamw_device_round leaves it)."""
+        st = self._slowmo_state("slowmo_device_step")
+        s = stream_ptr(stream)
+        check(lib.mx_slowmo_step(st.addr, 0.0, self.lr_dev.data_ptr(), s), "mx_slowmo_step")
+        self._slowmo_buffers(st, s, stream, False)
+
     def state_dict(self):
         """Checkpoint: the workers' rows and the iteration counter (resume on the same schedule);
         with attach_sgd(momentum != 0) the momentum rows too, with master_weights=True the fp32
         master rows, with attach_adamw the exp_avg / exp_avg_sq rows and the step count, and with
         attach_lion the lion_exp_avg rows (in the arena's dtype), with attach_qgm the qgm_buffer rows, with
-        attach_gt the gt_tracker and gt_prev_grad rows (and the momentum rows)."""
+        attach_gt the gt_tracker and gt_prev_grad rows (and the momentum rows), with attach_slowmo the anchor and
+        the slow momentum."""
         state = {"kind": "decen", "iter": int(self.iter), "row_base": int(self.row_base),
                  "workers": list(self.workers), "rows": self.rows.detach().clone()}
         if (self._sgd is not None or self._gt is not None) and self.momentum_rows is not None:
@@ -2326,6 +2506,9 @@ class VirtualWorkerGroup:
         if self._gt is not None:
             state["gt_tracker_rows"] = self.gt_tracker_rows.detach().clone()
             state["gt_prev_grad_rows"] = self.gt_prev_grad_rows.detach().clone()
+        if self._slowmo is not None:
+            state["slowmo_anchor"] = self.slowmo_anchor.detach().clone()
+            state["slowmo_momentum"] = self.slowmo_momentum.detach().clone()
         return state
 
     def load_state_dict(self, state):
@@ -2364,6 +2547,15 @@ class VirtualWorkerGroup:
             if self._gt is None or any(tuple(a.shape) != tuple(self.gt_tracker_rows.shape) for a in gt):
                 raise ValueError("checkpoint carries gradient-tracking state (gt_tracker rows): attach_gt() on a "
                                  "group of the same shape before loading it")
+        slow = [state.get(k) for k in ("slowmo_anchor", "slowmo_momentum")]
+        if any(a is not None for a in slow):
+            # the momentum is a displacement from the anchor it was taken at: either alone says nothing
+            if any(a is None for a in slow):
+                raise ValueError("checkpoint carries half of the SlowMo state: slowmo_anchor and slowmo_momentum "
+                                 "are only valid together")
+            if self._slowmo is None or any(tuple(a.shape) != tuple(self.slowmo_anchor.shape) for a in slow):
+                raise ValueError("checkpoint carries SlowMo state (slowmo_anchor): attach_slowmo() on a group of "
+                                 "the same shape before loading it")
         with torch.no_grad():
             self.rows.copy_(state["rows"])
             if self._gt is not None:             # a checkpoint without them: tracker and previous gradient zeros
@@ -2382,6 +2574,13 @@ class VirtualWorkerGroup:
                 self.momentum_rows.zero_() if mom is None else self.momentum_rows.copy_(mom)
             if self.master_rows is not None:     # a checkpoint without them: the widened rows
                 self.master_rows.copy_(self.rows if master is None else master)
+            if self._slowmo is not None:         # a checkpoint without them: the anchor from row 0, zero momentum
+                if slow[0] is None:
+                    self.slowmo_anchor_from_rows()
+                    self.slowmo_momentum.zero_()
+                else:
+                    self.slowmo_anchor.copy_(slow[0])
+                    self.slowmo_momentum.copy_(slow[1])
         self.iter = int(state["iter"])
 
     def communicate(self):

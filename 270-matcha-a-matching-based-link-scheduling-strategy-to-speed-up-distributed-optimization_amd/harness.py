@@ -198,7 +198,8 @@ class VirtualTrainer:
 
     def __init__(self, args, model_fn, n_batches, device="cuda", batched=False, graph=False, fused_sgd=False,
                  fused_adamw=False, adamw_hyper=None, clip_grad_norm=None, param_groups=None, fused_lion=False,
-                 lion_hyper=None, consensus_every=None, fused_qgm=False, qgm_hyper=None, fused_gt=False, gt_hyper=None):
+                 lion_hyper=None, consensus_every=None, fused_qgm=False, qgm_hyper=None, fused_gt=False, gt_hyper=None,
+                 slowmo_every=None, slowmo_hyper=None):
         """fused_sgd=True (non-batched, uncompressed): the workers' optimizer.step() /
         zero_grad() and the gossip round run as ONE launch (VirtualWorkerGroup.attach_sgd /
         sgd_communicate, csrc/sgd_mix.hip): backward() accumulates into the group's gradient arena,
@@ -253,6 +254,14 @@ class VirtualTrainer:
         from the mean row, the consensus distance, the norm of the mean) and the epoch stats carry
         "consensus" (the last consensus distance) and "consensus_dist" (that worker's own distance).
 
+        slowmo_every=tau (with one of the fused_* options; default None): SlowMo's outer step (attach_slowmo /
+        slowmo_step, csrc/slowmo.hip) after the round of every tau-th iteration, counted over the whole run
+        (the group's iteration counter, so a resumed run keeps the rhythm), at that iteration's learning rate:
+        every worker's row becomes one common point -- the exact average moved by the slow momentum.  It runs
+        before the consensus measurement, so the log shows the collapse to 0.  slowmo_hyper: {"beta", "alpha",
+        "buffers"} over the defaults beta 0.5, alpha 1.0, buffers "reset" (the base optimizer's momentum starts
+        afresh after every outer step, the paper's choice).
+
         graph=True (with batched=True, decentralized gossip, one GPU): once the learning rate
         is constant within an epoch, the whole training iteration -- vmap'd forward / backward,
         SGD update and the gossip round at a device-side iteration counter (device_round) -- is
@@ -303,6 +312,16 @@ class VirtualTrainer:
             raise ValueError("param_groups is honoured by the fused optimizer steps only (fused_sgd=True, "
                              "fused_adamw=True or fused_lion=True): the other paths step torch's optimizers with one group")
         self.grad_norm_log = []
+        if slowmo_every is not None and (int(slowmo_every) != slowmo_every or slowmo_every < 1):
+            raise ValueError(f"slowmo_every must be None or a positive integer, not {slowmo_every!r}")
+        if slowmo_every is not None and not self.fused:
+            raise ValueError("slowmo_every needs one of the fused optimizer steps (fused_sgd / fused_adamw / fused_lion / "
+                             "fused_qgm / fused_gt): the outer step acts on the group's optimizer state")
+        if slowmo_hyper is not None and slowmo_every is None:
+            raise ValueError("slowmo_hyper without slowmo_every: no outer step would run")
+        if set(slowmo_hyper or {}) - {"beta", "alpha", "buffers"}:
+            raise ValueError(f"slowmo_hyper takes beta, alpha and buffers, not {sorted(slowmo_hyper)}")
+        self.slowmo_every = None if slowmo_every is None else int(slowmo_every)
         if consensus_every is not None and (int(consensus_every) != consensus_every or consensus_every < 1):
             raise ValueError(f"consensus_every must be None or a positive integer, not {consensus_every!r}")
         self.consensus_every = None if consensus_every is None else int(consensus_every)
@@ -353,6 +372,10 @@ class VirtualTrainer:
         sync_rows(self.group.rows)
         if mixed:
             self.group.master_from_rows()                        # the masters of the synchronized rows
+        if self.slowmo_every is not None:                        # after the sync: the anchor is the common row
+            hyper = {"beta": 0.5, "alpha": 1.0, "buffers": "reset"}
+            hyper.update(slowmo_hyper or {})
+            self.group.attach_slowmo(**hyper)
         self.optimizers = [torch.optim.SGD(m.parameters(), lr=args.lr, momentum=args.momentum,
                                            weight_decay=5e-4, nesterov=args.nesterov, dampening=0)
                            for m in self.models]
@@ -568,6 +591,8 @@ class VirtualTrainer:
             self._dev_iter_synced = False
             if self.clip_grad_norm is not None:              # the round is complete (wait_round): a plain read
                 self.grad_norm_log.append(self.group.grad_norms.cpu())
+            if self.slowmo_every is not None and self.group.iter % self.slowmo_every == 0:
+                self.group.slowmo_step(lr)                   # the outer step: one launch, before the measurement
             self._consensus_tick()
             if on_round is not None:
                 on_round("after", self)

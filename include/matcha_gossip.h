@@ -1354,6 +1354,64 @@ int mx_mean_rows_to(const float* rows, int nrows, int64_t ld, int64_t count, int
 const char* mx_mean_kernel_name(const float* rows, int nrows, int64_t ld, int64_t count, int order, const float* dst,
                                 int ndst, int64_t dst_ld);
 
+/* ---------------------------------------------------------------- SlowMo outer step
+ * SlowMo (Wang, Tantia, Ballas, Rabbat, ICLR 2020) for workers held as rows of one arena
+ * (csrc/slowmo.hip): every tau iterations of any base optimizer, the exact average of the n = n_local
+ * rows, a slow momentum on the averaged displacement and the broadcast of the new common point, in ONE
+ * streaming pass over the rows.  State per group: a, the anchor (the common point of the last outer
+ * step), and u, the slow momentum (zeros at the start), fp32 [count] each.  Per column, every line one
+ * fp32 rounding (no contraction; the fmas are explicit):
+ *   s    = the sum of the n rows' values in mx_mean_rows' order (order 0: binomial tree, 1: rank order)
+ *   mean = fdiv(s, (float)n)                     the bits mx_mean_rows_to gives for the same rows and order
+ *   rl   = fdiv(1, lr);  al = fmul(alpha, lr)    once per launch
+ *   q    = fmul(fsub(a, mean), rl)
+ *   u'   = fmaf(beta, u, q)
+ *   a'   = fmaf(-al, u', a)
+ *   every row x_r = a';  a = a';  u = u'
+ *   mixed precision (p non-NULL): the rows are the fp32 masters and every p_r = bf16_rne(a') -- p is the
+ *   bfloat16 model arena, write only, rounded once to nearest even; NaN stays NaN
+ * lr is the argument or, when lr_dev is non-NULL, the float it points to on the device, read when the
+ * kernel runs; a learning rate of exactly 0 read there makes the launch a complete no-op (rl would be
+ * Inf).  A NaN or Inf in one row's column reaches a', u' and every row of that column and no other.
+ * Every lane reads its columns of all n rows, a and u before it writes anything in them: the step is in
+ * place.  Nothing is read or written at or past `count` in any array.
+ * Known limitation: for n that is not a power of two the pinned-order mean of n identical values can
+ * differ from the value in the last place (12-20 % of random fp32 values for n = 3, 5, 6, 7, 12; none
+ * for 2, 8, 16 in the tree order; in rank order the partial sums 3 x, 5 x, ... round for every n > 2), so a
+ * synced state is not an exact fixed point there.
+ * mx_slowmo_call, built once and kept alive by the caller (sizeof == 72):
+ *   rows       n_local rows of ld floats (device); count <= ld columns are used
+ *   a, u       float [count] (device); they may not overlap the rows, p or each other
+ *   p          NULL (an fp32 group) or the bfloat16 arena, n_local rows of p_ld elements
+ *   order      0 or 1, as mx_mean_rows
+ *   alpha      the slow learning rate, finite and > 0;  beta  the slow momentum factor, in [0, 1)
+ * mx_slowmo_step(call, lr, lr_dev, stream) enqueues one launch, with no host synchronisation and no host
+ * read, so it can be captured in a graph.  16-byte accesses on rows, a and u and 8-byte stores on p
+ * where every pointer is aligned that far, ld % 4 == 0 (and p_ld % 4 == 0) and the chunk is in range,
+ * per element for the last count % 4 columns and for unaligned tables.  Up to 8 rows go through
+ * 512-column tiles staged in LDS (mx_mean_rows_to's geometry); 9..64 rows are held per lane, 16 bytes
+ * a lane up to 16 rows, 8 up to 32, 4 up to 64.  The bits depend on none of this.
+ * MX_ERR_INVALID, nothing launched: a null record, rows, a or u; n_local outside [1, 64]; ld < count
+ * (p_ld < count); order not 0 or 1; a or u overlapping the rows, p or each other; alpha not finite and
+ * positive; beta outside [0, 1); lr not finite and positive when lr_dev is NULL.
+ * mx_slowmo_set / _get: "store_policy" (the 16-byte stores: 1 = nt, the default; 3 = sc1 nt, see
+ * mx_mix_set), "wgpc" (the tile kernel's workgroups per CU on rounds of more than 64 MB of rows,
+ * default 3, 0 = no cap).  mx_slowmo_kernel_name: the kernel mx_slowmo_step launches for the record
+ * (static string, "invalid" for a record it refuses; nothing launched), for reports. */
+typedef struct mx_slowmo_call {
+    float* rows;
+    float* a;
+    float* u;
+    void* p;
+    int64_t ld, p_ld, count;
+    int32_t n_local, order;
+    float alpha, beta;
+} mx_slowmo_call;
+int mx_slowmo_step(const mx_slowmo_call* call, float lr, const float* lr_dev, void* stream);
+int mx_slowmo_set(const char* key, int value);
+int mx_slowmo_get(const char* key);
+const char* mx_slowmo_kernel_name(const mx_slowmo_call* call);
+
 /* ---------------------------------------------------------------- host: matching decomposition
  * nx.max_weight_matching (graph_manager.py:64, inside GraphProcessor.getSubGraphs 57-83) without
  * networkx: the blossom algorithm networkx 3.4.2 runs, in its visiting orders, so the same maximum

@@ -86,12 +86,27 @@ def main():
     ap.add_argument("--consensus-every", default=None, type=int, metavar="K", help="one GPU: measure how far apart "
                     "the workers are after every K-th iteration's round (one read of the rows, no host wait per "
                     "round) and print the consensus distance and its ratio to the norm of the mean per epoch")
+    ap.add_argument("--slowmo-every", default=None, type=int, metavar="K", help="one GPU, with a --fused-* step: "
+                    "SlowMo's outer step after every K-th iteration's round -- the workers' exact average, moved by a "
+                    "slow momentum, becomes every worker's row (one launch)")
+    ap.add_argument("--slowmo-beta", default=None, type=float, metavar="X", help="--slowmo-every: the slow momentum "
+                    "factor in [0, 1) (default 0.5)")
+    ap.add_argument("--slowmo-alpha", default=None, type=float, metavar="X", help="--slowmo-every: the slow learning "
+                    "rate, > 0 (default 1.0)")
+    ap.add_argument("--slowmo-buffers", default=None, choices=("reset", "maintain", "average"), help="--slowmo-every: "
+                    "what the outer step does to the base optimizer's momentum (default reset)")
     a = ap.parse_args()
     fused = a.fused_sgd or a.fused_adamw or a.fused_lion or a.fused_qgm or a.fused_gt
     if a.qgm_mu is not None and not a.fused_qgm:
         ap.error("--qgm-mu is the quasi-global momentum step's: add --fused-qgm")
     if a.consensus_every is not None and a.consensus_every < 1:
         ap.error("--consensus-every: a positive number of iterations")
+    slowmo = {k: v for k, v in (("beta", a.slowmo_beta), ("alpha", a.slowmo_alpha), ("buffers", a.slowmo_buffers))
+              if v is not None}
+    if a.slowmo_every is None and slowmo:
+        ap.error("--slowmo-beta / --slowmo-alpha / --slowmo-buffers belong to --slowmo-every K")
+    if a.slowmo_every is not None and (a.slowmo_every < 1 or not fused):
+        ap.error("--slowmo-every: a positive number of iterations, with one of the --fused-* steps")
     if a.no_decay_1d and not fused:
         ap.error("--no-decay-1d is honoured by the fused optimizer steps only: add --fused-sgd, --fused-adamw or "
                  "--fused-lion")
@@ -108,6 +123,8 @@ def main():
                  "does not clip")
     if a.no_decay_1d and world > 1:
         ap.error("--no-decay-1d: one process per GPU trains with torch's optimizers (no fused step yet)")
+    if a.slowmo_every is not None and world > 1:
+        ap.error("--slowmo-every: the exact average needs every worker's rows on one GPU (one process)")
     if a.consensus_every is not None and world > 1:
         ap.error("--consensus-every: the mean needs every worker's rows on one GPU (one process)")
     args = H.HarnessArgs(name=a.name, description=a.description, model=a.model, lr=a.lr, momentum=a.momentum,
@@ -139,7 +156,8 @@ def main():
                               fused_qgm=a.fused_qgm, qgm_hyper={"mu": a.qgm_mu}, fused_gt=a.fused_gt,
                               clip_grad_norm=a.clip_grad_norm,
                               param_groups=[{"params": lambda name, p: p.ndim <= 1, "weight_decay": 0.0}]
-                              if a.no_decay_1d else None, consensus_every=a.consensus_every)
+                              if a.no_decay_1d else None, consensus_every=a.consensus_every,
+                              slowmo_every=a.slowmo_every, slowmo_hyper=slowmo or None)
         if a.resume:
             tr.load(a.resume)
     import time
