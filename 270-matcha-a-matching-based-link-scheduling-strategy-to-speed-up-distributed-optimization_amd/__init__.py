@@ -12,7 +12,7 @@ from .engine import GossipEngine, VirtualWorkerGroup, RcclComm, PullTransport, L
 from .choco import ChocoWorkerGroup, topk_count
 from .communicator import Communicator, decenCommunicator, ChocoCommunicator, centralizedCommunicator
 from .comm_helpers import flatten_tensors, unflatten_tensors, scatter_tensors
-from .compressors import get_top_k, check_top_k
+from .compressors import get_top_k, check_top_k, get_scaled_sign, unpack_scaled_sign
 from .topologies import select_graph, erdos_renyi, GRAPH_SIZES
 from . import solver
 from . import harness
@@ -23,6 +23,7 @@ __all__ = [
     "MXError", "lib", "GraphProcessor", "FixedProcessor", "MatchaProcessor", "GossipEngine",
     "VirtualWorkerGroup", "RcclComm", "PullTransport", "Layout", "partition", "pull_stats", "adam_bias_table", "param_runs", "slowmo_tuning", "set_slowmo_tuning", "ChocoWorkerGroup", "topk_count",
     "Communicator", "decenCommunicator", "ChocoCommunicator", "centralizedCommunicator",
-    "flatten_tensors", "unflatten_tensors", "scatter_tensors", "get_top_k", "check_top_k", "select_graph",
+    "flatten_tensors", "unflatten_tensors", "scatter_tensors", "get_top_k", "check_top_k", "get_scaled_sign",
+    "unpack_scaled_sign", "select_graph",
     "erdos_renyi", "GRAPH_SIZES", "solver", "harness", "placement", "best_placement", "placement_cost",
 ]

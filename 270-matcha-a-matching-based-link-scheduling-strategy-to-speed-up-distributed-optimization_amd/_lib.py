@@ -68,6 +68,15 @@ SIGNATURES = {
                                c_int, c_f32, c_f32, c_p, c_p]),
     "mx_choco_apply_at": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_int, c_p, c_p, c_i64, c_int,
                                   c_int, c_f32, c_f32, c_p, c_p]),
+    "mx_choco_sign_msg_bytes": (c_i64, [c_i64]),
+    "mx_choco_sign_work_bytes": (ctypes.c_size_t, [c_i64, c_int]),
+    "mx_choco_sign_compress": (c_int, [c_p, c_p, c_i64, c_int, c_i64, c_p, c_i64, c_p, c_p]),
+    "mx_choco_sign_apply": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_int, c_p, c_i64, c_int, c_int,
+                                    c_f32, c_f32, c_p]),
+    "mx_choco_sign_apply_at": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_int, c_p, c_p, c_i64, c_int,
+                                       c_int, c_f32, c_f32, c_p]),
+    "mx_choco_sign_set": (c_int, [ctypes.c_char_p, c_int]),
+    "mx_choco_sign_get": (c_int, [ctypes.c_char_p]),
     "mx_pull_fetch": (c_int, [c_p, c_int, c_int, c_p, c_p, c_i64, c_i64, c_p]),
     "mx_choco_apply_slots": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_int, c_p, c_i64, c_int, c_int,
                                      c_f32, c_f32, c_p]),

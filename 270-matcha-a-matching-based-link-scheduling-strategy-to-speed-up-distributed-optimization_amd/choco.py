@@ -5,6 +5,10 @@ persistent Choco state x_hat and s (all [n_local, P] in HBM).  Per round:
     q_r = top-k(|x_r - x_hat_r|)            mx_topk_abs_diff   (prepare_comm_buffer, 175-196)
     [N > 1] RCCL exchange of the messages   mx_exchange_round  (12 k bytes per edge direction)
     s / x_hat updates + dense x update      mx_choco_apply     (averaging, 200-230; one fused pass)
+With compressor="sign" the message is the scaled-sign (1-bit) quantizer Q(v) = (|v|_1 / P) sign(v) instead
+(csrc/choco_sign.hip): q_r = (scale_r, one bit per column, set where x_r - x_hat_r < 0), P/8 bytes on the
+wire; mx_choco_sign_compress and the elementwise mx_choco_sign_apply take the two kernels' places.  A 1-bit
+message has no zero: a zero difference travels as +scale (torch.sign would give 0).
 Under PullTransport (N > 1, one process per GPU of a node) the messages are not sent: every rank
 publishes the messages its peers read this round into its IPC-shared snapshot buffer
 (mx_snapshot_publish_rows), the device
@@ -29,10 +33,16 @@ def topk_count(P, ratio):
     return max(1, int(P * (1 - ratio)))
 
 
+COMPRESSORS = ("topk", "sign")
+
+
 class ChocoWorkerGroup:
-    def __init__(self, topology, models=None, numel=None, *, ratio, consensus_lr, rank=0, nranks=1,
-                 comm=None, adopt=True, placement=None, pull_read="fetch", dtype=torch.float32):
-        """placement: as VirtualWorkerGroup (None / "contiguous", "auto" or a worker order);
+    def __init__(self, topology, models=None, numel=None, *, ratio=None, consensus_lr, rank=0, nranks=1,
+                 comm=None, adopt=True, placement=None, pull_read="fetch", dtype=torch.float32,
+                 compressor="topk"):
+        """compressor: "topk" (compressors.get_top_k; `ratio` required) or "sign" (the scaled-sign
+        quantizer; takes no `ratio`, k = 0, check_topk() has nothing to check, PullTransport not built).
+        placement: as VirtualWorkerGroup (None / "contiguous", "auto" or a worker order);
         `workers` lists the worker id of each local row.  pull_read (PullTransport only): "fetch"
         (default) copies the round's partner messages from their owners' snapshots into the receive
         slots (mx_pull_fetch) before the apply; "direct" lets the apply read them in place
@@ -40,6 +50,17 @@ class ChocoWorkerGroup:
         load per message).  Same bits; which is faster across GPUs is measured by bench.py."""
         if pull_read not in ("fetch", "direct"):
             raise ValueError("pull_read must be 'fetch' or 'direct'")
+        if compressor not in COMPRESSORS:
+            raise ValueError(f"compressor must be one of {COMPRESSORS}, not {compressor!r}")
+        if compressor == "topk" and ratio is None:
+            raise ValueError("ChocoWorkerGroup: compressor='topk' needs a ratio")
+        if compressor == "sign" and ratio is not None:
+            raise ValueError("ChocoWorkerGroup: compressor='sign' takes no ratio")
+        if compressor == "sign" and isinstance(comm, PullTransport):
+            raise NotImplementedError("ChocoWorkerGroup: compressor='sign' under PullTransport -- the publish / "
+                                      "gate / fetch sizing of sign messages is not built")
+        self.compressor = compressor
+        self.sign = compressor == "sign"
         if dtype != torch.float32:
             # only VirtualWorkerGroup's mixing round has a bfloat16 form (csrc/mix_bf16.hip)
             raise NotImplementedError(f"ChocoWorkerGroup: {dtype} rows -- the top-k and apply kernels are fp32-only")
@@ -81,16 +102,22 @@ class ChocoWorkerGroup:
                     if adopt:
                         p.data = view
                     off += k
-        self.k = topk_count(P, ratio)
-        self.kpad = (self.k + 1) // 2 * 2
-        # vals f32[kpad] | idx int64[k] | tile bounds int32[ceil(P/4096) + 1] (written by the top-k)
-        self.msg_bytes = int(lib.mx_choco_msg_bytes(P, self.k))
-        self.bnd_off = 4 * self.kpad + 8 * self.k
+        if self.sign:
+            # scale f32 | L f64 | P int64 | zeros to 64 | bits uint8[8 ceil(P/64)] (mx_choco_sign_compress)
+            self.k = self.kpad = 0
+            self.msg_bytes = int(lib.mx_choco_sign_msg_bytes(P))
+            self.work_ld = int(lib.mx_choco_sign_work_bytes(P, 1))
+        else:
+            self.k = topk_count(P, ratio)
+            self.kpad = (self.k + 1) // 2 * 2
+            # vals f32[kpad] | idx int64[k] | tile bounds int32[ceil(P/4096) + 1] (written by the top-k)
+            self.msg_bytes = int(lib.mx_choco_msg_bytes(P, self.k))
+            self.bnd_off = 4 * self.kpad + 8 * self.k
+            self.work_ld = int(lib.mx_topk_work_bytes(P))
         self.msg_ld = (self.msg_bytes + 255) // 256 * 256
         self.msgs = torch.empty(self.engine.n_slots * self.msg_ld, dtype=torch.uint8, device="cuda")
-        self.work_ld = int(lib.mx_topk_work_bytes(P))
         self.work = torch.zeros(self.n_local * self.work_ld, dtype=torch.uint8, device="cuda")  # zero on first use
-        self.apply_work = torch.empty(int(lib.mx_choco_apply_work_bytes(P, self.engine.n_slots)),
+        self.apply_work = torch.empty(0 if self.sign else int(lib.mx_choco_apply_work_bytes(P, self.engine.n_slots)),
                                       dtype=torch.uint8, device="cuda")
         self.gamma32 = float(np.float32(consensus_lr))
         self.iter_dev = torch.zeros(1, dtype=torch.int64, device="cuda")   # device_round's counter
@@ -137,15 +164,25 @@ class ChocoWorkerGroup:
         return (self.msg_bytes + 15) // 16 * 4
 
     def message(self, slot):
-        """(values float32[k], indices int64[k]) views of message `slot` (index-sorted)."""
+        """(values float32[k], indices int64[k]) views of message `slot` (index-sorted); with
+        compressor="sign": (scale, a 0-dim float32 view, bits uint8[ceil(P/8)], column c = bit c & 7 of
+        byte c >> 3)."""
         base = slot * self.msg_ld
+        if self.sign:
+            return (self.msgs[base:base + 4].view(torch.float32)[0],
+                    self.msgs[base + 64:base + 64 + (self.numel + 7) // 8])
         vals = self.msgs[base:base + 4 * self.k].view(torch.float32)
         idx = self.msgs[base + 4 * self.kpad:base + 4 * self.kpad + 8 * self.k].view(torch.int64)
         return vals, idx
 
     def compress(self, it, stream=None):
         """prepare_comm_buffer (communicator.py:175-196): every local row's top-k message of
-        x - x_hat into its message slot."""
+        x - x_hat into its message slot (compressor="sign": its scaled-sign message)."""
+        if self.sign:
+            check(lib.mx_choco_sign_compress(self.x.data_ptr(), self.x_hat.data_ptr(), self.ld, self.n_local,
+                                             self.numel, self.msgs.data_ptr(), self.msg_ld, self.work.data_ptr(),
+                                             stream_ptr(stream)), "mx_choco_sign_compress")
+            return
         check(lib.mx_topk_abs_diff_rows(self.x.data_ptr(), self.x_hat.data_ptr(), self.ld, self.n_local,
                                         self.numel, self.k, self.msgs.data_ptr(), self.msg_ld, 4 * self.kpad,
                                         self.bnd_off, self.work.data_ptr(), self.work_ld, stream_ptr(stream)),
@@ -177,7 +214,10 @@ class ChocoWorkerGroup:
 
     def check_topk(self, stream=None):
         """Synchronise and raise MXError if a top-k row barrier's bounded wait expired since the
-        last check (mx_topk_check: that round's messages are undefined; never a GPU hang)."""
+        last check (mx_topk_check: that round's messages are undefined; never a GPU hang).  Nothing to
+        check with compressor="sign": its kernels have no barrier and no wait."""
+        if self.sign:
+            return
         check(lib.mx_topk_check(self.work.data_ptr(), self.work_ld, self.n_local, self.numel, stream_ptr(stream)),
               "mx_topk_check")
 
@@ -192,6 +232,13 @@ class ChocoWorkerGroup:
         if self.engine.comm is not None:
             self.engine.exchange(it, [mbase + r * self.msg_ld for r in range(self.n_local)],
                                  mbase + self.n_local * self.msg_ld, self.msg_ld, self.msg_bytes, stream)
+        if self.sign:
+            check(lib.mx_choco_sign_apply(self.x.data_ptr(), self.x_hat.data_ptr(), self.s.data_ptr(), self.ld,
+                                          self.numel, mbase, self.msg_ld, self.engine.n_slots,
+                                          self.engine.plan.data_ptr(), int(it), self.n_local, self.engine.M,
+                                          self.engine.alpha32, self.gamma32, stream_ptr(stream)),
+                  "mx_choco_sign_apply")
+            return
         check(lib.mx_choco_apply(self.x.data_ptr(), self.x_hat.data_ptr(), self.s.data_ptr(), self.ld,
                                  self.numel, self.k, mbase, self.msg_ld, self.engine.n_slots,
                                  self.engine.plan.data_ptr(), int(it), self.n_local, self.engine.M,
@@ -247,6 +294,14 @@ class ChocoWorkerGroup:
             raise RuntimeError("device_round: graph-replayable rounds need all partners on this GPU (nranks = 1)")
         self.compress(0, stream)
         sp = stream_ptr(stream)
+        if self.sign:
+            check(lib.mx_choco_sign_apply_at(self.x.data_ptr(), self.x_hat.data_ptr(), self.s.data_ptr(), self.ld,
+                                             self.numel, self.msgs.data_ptr(), self.msg_ld, self.engine.n_slots,
+                                             self.engine.plan.data_ptr(), self.iter_dev.data_ptr(), self.engine.T,
+                                             self.n_local, self.engine.M, self.engine.alpha32, self.gamma32, sp),
+                  "mx_choco_sign_apply_at")
+            check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, sp), "mx_iter_advance")
+            return
         check(lib.mx_choco_apply_at(self.x.data_ptr(), self.x_hat.data_ptr(), self.s.data_ptr(), self.ld,
                                     self.numel, self.k, self.msgs.data_ptr(), self.msg_ld, self.engine.n_slots,
                                     self.engine.plan.data_ptr(), self.iter_dev.data_ptr(), self.engine.T,
@@ -266,15 +321,19 @@ class ChocoWorkerGroup:
         """Checkpoint: rows, the persistent Choco state x_hat / s (communicator.py:179-182) and
         the iteration counter."""
         P = self.numel
-        return {"kind": "choco", "iter": int(self.iter), "row_base": int(self.row_base), "k": int(self.k),
-                "workers": list(self.workers),
-                "rows": self.x[:, :P].detach().clone(), "x_hat": self.x_hat[:, :P].detach().clone(),
-                "s": self.s[:, :P].detach().clone()}
+        state = {"kind": "choco", "iter": int(self.iter), "row_base": int(self.row_base), "k": int(self.k),
+                 "workers": list(self.workers),
+                 "rows": self.x[:, :P].detach().clone(), "x_hat": self.x_hat[:, :P].detach().clone(),
+                 "s": self.s[:, :P].detach().clone()}
+        if self.sign:                        # a top-k group's checkpoint stays key for key what it was
+            state["compressor"] = "sign"
+        return state
 
     def load_state_dict(self, state):
         P = self.numel
         if state.get("kind") != "choco" or int(state["row_base"]) != self.row_base or \
                 list(state.get("workers", self.workers)) != self.workers or \
+                state.get("compressor", "topk") != self.compressor or \
                 int(state["k"]) != self.k or tuple(state["rows"].shape) != (self.n_local, P):
             raise ValueError("checkpoint does not match this Choco worker group")
         with torch.no_grad():

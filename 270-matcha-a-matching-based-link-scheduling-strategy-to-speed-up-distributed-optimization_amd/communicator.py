@@ -363,10 +363,12 @@ class decenCommunicator(Communicator):
 
 
 class ChocoCommunicator(Communicator):
-    """communicator.py:161-268 -- top-k compressed gossip with persistent x_hat / s."""
+    """communicator.py:161-268 -- top-k compressed gossip with persistent x_hat / s.  compressor="sign":
+    the scaled-sign (1-bit) quantizer in top-k's place (`ratio` is then not used)."""
 
-    def __init__(self, rank, size, topology, ratio, consensus_lr, *, transport=None):
+    def __init__(self, rank, size, topology, ratio, consensus_lr, *, transport=None, compressor="topk"):
         super(ChocoCommunicator, self).__init__(rank, size, transport=transport)
+        self.compressor = compressor
         self.topology = topology
         self.neighbor_weight = topology.neighbor_weight
         self.iter = 0
@@ -384,6 +386,10 @@ class ChocoCommunicator(Communicator):
     def s(self):
         return self._group.s[0, :self._group.numel] if self._group is not None else None
 
+    def _compressor_args(self):
+        """what ChocoWorkerGroup takes for this communicator's compressor (the sign quantizer has no ratio)"""
+        return {"compressor": "sign"} if self.compressor == "sign" else {"ratio": self.ratio, "compressor": self.compressor}
+
     def _bind(self, model):
         params = [p for p in model.parameters()]
         n = int(sum(p.numel() for p in params))
@@ -397,7 +403,7 @@ class ChocoCommunicator(Communicator):
         else:
             on_gpu = all(p.device.type == "cuda" for p in params)
             self._group = ChocoWorkerGroup(self.topology, [model] if on_gpu else None,
-                                           numel=None if on_gpu else n, ratio=self.ratio,
+                                           numel=None if on_gpu else n, **self._compressor_args(),
                                            consensus_lr=self.consensus_lr, rank=self.rank,
                                            nranks=self.size, comm=self._comm())
             self._stage = _Staging(params, self._group.rows[0])
@@ -432,13 +438,13 @@ class ChocoCommunicator(Communicator):
         """communicator.py:175-196: `self.tensor_list` into this rank's x row (copied, or used in
         place when it lives there), x_hat / s created zero on first use (they persist), then the
         top-k of x - x_hat; `compressed` = {"values", "indices"} views of the message (GPU,
-        index-sorted).  Returns the compression seconds (the reference's encode time)."""
+        index-sorted; compressor="sign": {"scale", "bits"}).  Returns the compression seconds (the reference's encode time)."""
         tensors = list(self.tensor_list)
         n = int(sum(t.numel() for t in tensors))
         if self._group is not None and self._group.numel != n:
             raise ValueError(f"ChocoCommunicator: tensor_list holds {n} values, its x_hat / s hold {self._group.numel}")
         self.x = self._bind_list(tensors, lambda n: ChocoWorkerGroup(
-            self.topology, None, numel=n, ratio=self.ratio, consensus_lr=self.consensus_lr, rank=self.rank,
+            self.topology, None, numel=n, **self._compressor_args(), consensus_lr=self.consensus_lr, rank=self.rank,
             nranks=self.size, comm=self._comm()))
         self.initialized = True
         torch.cuda.synchronize()
@@ -446,6 +452,10 @@ class ChocoCommunicator(Communicator):
         self._group.compress(self.iter)
         self._group.check_topk()
         toc = time.time()
+        if self.compressor == "sign":
+            scale, bits = self._group.message(0)
+            self.compressed = {"scale": scale, "bits": bits}
+            return toc - tic
         vals, idx = self._group.message(0)
         self.compressed = {"values": vals, "indices": idx}
         return toc - tic

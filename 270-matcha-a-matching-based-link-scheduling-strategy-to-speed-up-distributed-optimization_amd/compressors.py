@@ -89,3 +89,39 @@ def get_top_k(x, ratio):
     if host:
         return vals.to(x.device), idx.to(x.device)
     return vals, idx
+
+
+def get_scaled_sign(x):
+    """The scaled-sign (1-bit) quantizer Q(v) = (|v|_1 / P) sign(v) of a float32 tensor, flattened:
+    returns (scale, bits) -- scale a 0-dim float32 tensor, f32(sum f64(|v|) / P), and bits uint8[ceil(P/8)],
+    column c = bit c & 7 of byte c >> 3, set where v[c] < 0 (padding bits zero).  A 1-bit message has no
+    zero: v[c] == 0 (either sign) and NaN travel as +scale, where torch.sign would give 0 / NaN.  The one-row
+    mx_choco_sign_compress without an x_hat, on any alignment; CPU input is staged to the GPU and the result
+    returned on the input's device, as get_top_k."""
+    x_data = x.reshape(-1)
+    if x_data.dtype != torch.float32:
+        raise TypeError("get_scaled_sign: a float32 tensor is required")
+    host = x_data.device.type != "cuda"
+    if host:
+        x_data = x_data.to("cuda")
+    x_data = x_data.contiguous()
+    dev = x_data.device
+    P = x_data.numel()
+    nbytes = int(lib.mx_choco_sign_msg_bytes(P))
+    if nbytes < 0:
+        raise ValueError("get_scaled_sign: an empty tensor")
+    msg = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev).view(torch.uint8)   # 8-byte aligned
+    work = torch.empty(int(lib.mx_choco_sign_work_bytes(P, 1)) // 8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.mx_choco_sign_compress(x_data.data_ptr(), None, P, 1, P, msg.data_ptr(), nbytes, work.data_ptr(),
+                                         stream_ptr()), "mx_choco_sign_compress")
+    scale, bits = msg[:4].view(torch.float32)[0], msg[64:64 + (P + 7) // 8]
+    if host:
+        return scale.to(x.device), bits.to(x.device)
+    return scale, bits
+
+
+def unpack_scaled_sign(scale, bits, numel):
+    """The dense float32 [numel] message of get_scaled_sign's (scale, bits): -scale where the bit is set."""
+    neg = ((bits[:, None] >> torch.arange(8, device=bits.device, dtype=torch.uint8)) & 1).reshape(-1)[:numel].bool()
+    return torch.where(neg, -scale, scale)

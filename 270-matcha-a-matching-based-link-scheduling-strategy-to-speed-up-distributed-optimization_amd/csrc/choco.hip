@@ -36,6 +36,7 @@
 //
 // Work invariant: the histograms and the candidate total are zero on entry (the
 // caller zero-fills the scratch once; every call leaves it that way), so no zeroing launch runs.
+#include "choco_round.h"
 #include "mx_common.h"
 
 #include <climits>
@@ -1619,17 +1620,7 @@ __device__ __forceinline__ void peer_acquire(int32_t mode_word) {
     }
 }
 
-// The plan record of this round: `rec` itself, or with iter_dev (graph-replayable launches) the
-// record of round *iter_dev of the plan table at `rec`; null (launch is a no-op) when that round
-// is outside [0, n_iters) or has no active matching -- communicator.py:249-250 skips such rounds.
-__device__ __forceinline__ const int32_t* round_rec(const int32_t* rec, const int64_t* iter_dev, int64_t n_iters,
-                                                   int64_t words) {
-    if (!iter_dev) return rec;
-    const int64_t v = *iter_dev;
-    if (v < 0 || v >= n_iters) return nullptr;
-    const int32_t* r = rec + v * words;
-    return r[0] ? r : nullptr;
-}
+using mx::choco::round_rec;     // this round's plan record (choco_round.h, shared with choco_sign.hip)
 
 // The launch arguments of the apply kernels.  The scalars travel as one record, passed by value as Rows
 // is to the top-k kernels.  The six arrays stay __restrict__ kernel parameters: a by-value record cannot

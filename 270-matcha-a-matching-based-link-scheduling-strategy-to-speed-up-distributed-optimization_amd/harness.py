@@ -333,8 +333,9 @@ class VirtualTrainer:
             torch.manual_seed(args.randomSeed + r)                # train_mpi.py:61, per rank
             self.models.append(model_fn().to(device))
         if args.compress:
-            self.group = ChocoWorkerGroup(self.GP, self.models, ratio=args.ratio,
-                                          consensus_lr=args.consensus_lr)
+            compressor = getattr(args, "compressor", "topk")
+            self.group = ChocoWorkerGroup(self.GP, self.models, consensus_lr=args.consensus_lr, compressor=compressor,
+                                          ratio=None if compressor == "sign" else args.ratio)   # sign takes no ratio
         else:
             # bfloat16 models are mixed as bfloat16 rows (half the bytes per round), like decenCommunicator
             dts = {p.dtype for m in self.models for p in m.parameters()}
@@ -733,7 +734,11 @@ class RankTrainer:
 
 
 class HarnessArgs:
-    """train_mpi.py:205-231 defaults, plus the harness's own (size, shape, num_classes, ratio)."""
+    """train_mpi.py:205-231 defaults, plus the harness's own (size, shape, num_classes, ratio, compressor)."""
+
+    # with compress: "topk" (the reference's) or "sign" (the scaled-sign quantizer; VirtualTrainer).  A class
+    # default, so the argument line a run logs changes only when it is set
+    compressor = "topk"
 
     def __init__(self, **kw):
         self.name = "Vanilla DecenSGD-synthetic"

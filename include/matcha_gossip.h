@@ -1188,6 +1188,47 @@ int mx_choco_apply_slots(float* x, float* xhat, float* s, int64_t ld, int64_t P,
                          const int64_t* slot_ptrs_dev, int n_slots, const int32_t* plan_dev, int64_t iter,
                          int n_local, int M, float alpha, float gamma, void* stream);
 
+/* ---------------------------------------------------------------- ChocoSGD, scaled-sign compressor
+ * The 1-bit quantizer Q(v) = (|v|_1 / P) sign(v) in place of compressors.get_top_k in
+ * ChocoCommunicator.prepare_comm_buffer (communicator.py:175-196) and averaging (communicator.py:200-230).
+ * For a row with d = x - x_hat (one fp32 subtraction; x_hat NULL: d = x):
+ *   L = sum_c f64(|d[c]|) (fp64, any order);  scale = f32(L / f64(P));  bit c = d[c] < 0 (false for +0, -0
+ *   and NaN: a zero difference travels as +scale);  q[c] = bit c ? -scale : +scale.
+ * A message slot holds mx_choco_sign_msg_bytes(P) = 64 + 8 ceil(P/64) bytes (communicator.py:175-230: the
+ * send buffer): float32 scale at 0, float64 L at 8 (diagnostic), int64 P at 16, zeros up to 64, then the
+ * bits -- column c is bit c & 7 of byte c >> 3, padding bits past P zero.  -1 for P < 1. */
+int64_t mx_choco_sign_msg_bytes(int64_t P);
+/* Scratch of mx_choco_sign_compress (communicator.py:175-230; one fp64 partial per 4096 columns of a row);
+ * 0 with mx_last_error for P < 1 or nrows < 1.  It needs no zero-fill. */
+size_t mx_choco_sign_work_bytes(int64_t P, int nrows);
+/* prepare_comm_buffer (communicator.py:175-230) of `nrows` rows: row r reads x + r*ld (and x_hat + r*ld;
+ * x_hat may be NULL), writes its message at msgs + r*msg_ld_bytes (8-byte aligned, msg_ld_bytes a multiple of
+ * 8 and >= mx_choco_sign_msg_bytes(P); ignored for one row).  Two launches, no atomics: scale depends on the
+ * row's values and P alone -- the same bits for any row count, grid or knob -- and is within 1 fp32 ulp of the
+ * correctly rounded value for P <= 2^26. */
+int mx_choco_sign_compress(const float* x, const float* x_hat, int64_t ld, int nrows, int64_t P, void* msgs,
+                           int64_t msg_ld_bytes, void* work, void* stream);
+/* averaging (communicator.py:175-230) for one round of n_local workers on scaled-sign messages, in place:
+ *   for each partner j of row r (ascending matching): s_r = s_r + f32(alpha) * q_j
+ *   s_r += (self weight of the plan record) * q_r ; x_hat_r += q_r
+ *   x_r = fma(gamma, s_r, x_r) ; x_r = fma(-gamma, x_hat_r, x_r)
+ * msgs: one slot per plan slot, msg_ld_bytes apart; slots [0, n_local) are the local rows' own messages.
+ * One elementwise launch; of a message's header only `scale` is read. */
+int mx_choco_sign_apply(float* x, float* xhat, float* s, int64_t ld, int64_t P, const void* msgs,
+                        int64_t msg_ld_bytes, int n_slots, const int32_t* plan_dev, int64_t iter, int n_local,
+                        int M, float alpha, float gamma, void* stream);
+/* Graph-replayable form (communicator.py:175-230; the no-op rules of mx_choco_apply_at): the round is
+ * *iter_dev; one outside [0, n_iters) or with no active matching leaves x, x_hat and s untouched. */
+int mx_choco_sign_apply_at(float* x, float* xhat, float* s, int64_t ld, int64_t P, const void* msgs,
+                           int64_t msg_ld_bytes, int n_slots, const int32_t* plan_dev, const int64_t* iter_dev,
+                           int64_t n_iters, int n_local, int M, float alpha, float gamma, void* stream);
+/* Knobs of the scaled-sign passes (communicator.py:175-230 has none; speed only, never results):
+ * "apply_nt" = mx_choco_sign_apply's access hints: -1 (default) non-temporal with several rows only, 0 / 1
+ * forced; "blocks_per_cu" = workgroups per CU of the compress pass's persistent grid (default 8, 1..64);
+ * "grid" = its exact grid size (0 = from blocks_per_cu; up to 65536). */
+int mx_choco_sign_set(const char* key, int value);
+int mx_choco_sign_get(const char* key);
+
 /* ---------------------------------------------------------------- cross-GPU exchange (RCCL)
  * One process per GPU; workers partitioned by owner[].  mx_exchange_round posts, inside one
  * ncclGroupStart/End, an ncclSend of every local row whose active partner lives on another

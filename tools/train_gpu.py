@@ -43,6 +43,8 @@ def main():
     ap.add_argument("--savePath", default="./saveModel")
     ap.add_argument("--save", action="store_true")
     ap.add_argument("--compress", action="store_true")
+    ap.add_argument("--compressor", default=None, choices=("topk", "sign"), help="--compress: the message -- topk "
+                    "(default: the reference's top 10 %) or sign (the scaled-sign 1-bit quantizer; one process)")
     ap.add_argument("--consensus_lr", default=0.1, type=float)
     ap.add_argument("--randomSeed", default=1234, type=int)
     ap.add_argument("--workers", default=8, type=int)
@@ -99,6 +101,8 @@ def main():
     fused = a.fused_sgd or a.fused_adamw or a.fused_lion or a.fused_qgm or a.fused_gt
     if a.qgm_mu is not None and not a.fused_qgm:
         ap.error("--qgm-mu is the quasi-global momentum step's: add --fused-qgm")
+    if a.compressor is not None and not a.compress:
+        ap.error("--compressor chooses ChocoSGD's message: add --compress")
     if a.consensus_every is not None and a.consensus_every < 1:
         ap.error("--consensus-every: a positive number of iterations")
     slowmo = {k: v for k, v in (("beta", a.slowmo_beta), ("alpha", a.slowmo_alpha), ("buffers", a.slowmo_buffers))
@@ -132,6 +136,10 @@ def main():
                          budget=a.budget, graphid=a.graphid, savePath=a.savePath, save=a.save,
                          compress=a.compress, consensus_lr=a.consensus_lr, randomSeed=a.randomSeed,
                          size=a.workers if world == 1 else world)
+    if a.compressor is not None:
+        if a.compressor == "sign" and world > 1:
+            ap.error("--compressor sign: one process (the per-GPU trainer keeps the top-k message)")
+        args.compressor = a.compressor
     import torch
     model_fn = H.model_factory(args)
     if a.bf16:
