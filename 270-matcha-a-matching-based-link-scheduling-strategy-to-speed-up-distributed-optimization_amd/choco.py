@@ -65,6 +65,7 @@ class ChocoWorkerGroup:
             # only VirtualWorkerGroup's mixing round has a bfloat16 form (csrc/mix_bf16.hip)
             raise NotImplementedError(f"ChocoWorkerGroup: {dtype} rows -- the top-k and apply kernels are fp32-only")
         self.pull_read = pull_read
+        self.dtype = dtype
         require_device()
         from .placement import block_workers, place
         n = int(topology.size)
@@ -85,6 +86,11 @@ class ChocoWorkerGroup:
             self.numel = int(sum(p.numel() for p in models[0].parameters()))
         else:
             self.numel = int(numel)
+        # attach_sgd: the models whose parameters are views of `x` (their .grad become views of the gradient arena)
+        self._adopted = list(models) if models is not None and adopt else None
+        self._copied_models = models is not None and not adopt
+        self._sgd = None                     # attach_sgd's hyperparameters
+        self.grad_arena = self.grads = self.mom_arena = self.momentum_rows = self.lr_dev = None
         P = self.numel
         self.ld = (P + ROW_ALIGN - 1) // ROW_ALIGN * ROW_ALIGN
         self.x = torch.zeros((self.n_local, self.ld), dtype=torch.float32, device="cuda")
@@ -293,6 +299,11 @@ class ChocoWorkerGroup:
         if self.engine.comm is not None:
             raise RuntimeError("device_round: graph-replayable rounds need all partners on this GPU (nranks = 1)")
         self.compress(0, stream)
+        self._apply_at(stream)
+
+    def _apply_at(self, stream=None):
+        """The apply launch at the device counter, then the counter's advance (device_round,
+        sgd_device_round)."""
         sp = stream_ptr(stream)
         if self.sign:
             check(lib.mx_choco_sign_apply_at(self.x.data_ptr(), self.x_hat.data_ptr(), self.s.data_ptr(), self.ld,
@@ -300,13 +311,12 @@ class ChocoWorkerGroup:
                                              self.engine.plan.data_ptr(), self.iter_dev.data_ptr(), self.engine.T,
                                              self.n_local, self.engine.M, self.engine.alpha32, self.gamma32, sp),
                   "mx_choco_sign_apply_at")
-            check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, sp), "mx_iter_advance")
-            return
-        check(lib.mx_choco_apply_at(self.x.data_ptr(), self.x_hat.data_ptr(), self.s.data_ptr(), self.ld,
-                                    self.numel, self.k, self.msgs.data_ptr(), self.msg_ld, self.engine.n_slots,
-                                    self.engine.plan.data_ptr(), self.iter_dev.data_ptr(), self.engine.T,
-                                    self.n_local, self.engine.M, self.engine.alpha32, self.gamma32,
-                                    self.apply_work.data_ptr(), sp), "mx_choco_apply_at")
+        else:
+            check(lib.mx_choco_apply_at(self.x.data_ptr(), self.x_hat.data_ptr(), self.s.data_ptr(), self.ld,
+                                        self.numel, self.k, self.msgs.data_ptr(), self.msg_ld, self.engine.n_slots,
+                                        self.engine.plan.data_ptr(), self.iter_dev.data_ptr(), self.engine.T,
+                                        self.n_local, self.engine.M, self.engine.alpha32, self.gamma32,
+                                        self.apply_work.data_ptr(), sp), "mx_choco_apply_at")
         check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, sp), "mx_iter_advance")
 
     def step(self, it, stream=None):
@@ -316,6 +326,102 @@ class ChocoWorkerGroup:
         self.compress(it, stream)
         self.average(it, stream)
         return True
+
+    # ------------------------------------------------------------------ SGD step fused into the round
+    def attach_sgd(self, momentum=0.0, weight_decay=0.0, nesterov=False, zero_grads=True):
+        """Give the group torch.optim.SGD's state (dampening 0) so that every worker's optimizer.step() +
+        zero_grad() (train_mpi.py:131-142) runs on the way into the compressor (csrc/choco_sgd.hip): with
+        compressor="sign" inside the compress pass itself, with "topk" as one launch before the selection.
+
+        Allocates `grad_arena` ([n_local, ld] fp32 zeros; `grads` is its [:, :numel] view) and, with
+        momentum, `mom_arena` / `momentum_rows`, and `lr_dev` (the device rounds' learning rate).  For
+        adopted models every parameter's .grad becomes the matching view of the gradient arena (see
+        VirtualWorkerGroup.attach_sgd on zero_grad(set_to_none=True), which would detach them); a group
+        whose models were copied (adopt=False) is refused: their gradients never reach the arena.
+        The exchange runs after the step, so any transport the unfused round has works here too."""
+        momentum, weight_decay = float(momentum), float(weight_decay)
+        if nesterov and momentum == 0.0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if self._copied_models:
+            raise ValueError("ChocoWorkerGroup.attach_sgd: the models were copied (adopt=False); their gradients "
+                             "would never reach the group's gradient arena")
+        self.grad_arena = torch.zeros_like(self.x)
+        self.grads = self.grad_arena[:, :self.numel]
+        self.mom_arena = self.momentum_rows = None
+        if momentum != 0.0:
+            self.mom_arena = torch.zeros_like(self.x)
+            self.momentum_rows = self.mom_arena[:, :self.numel]
+        for r, m in enumerate(self._adopted or ()):
+            off = 0
+            for p in m.parameters():
+                k = p.numel()
+                p.grad = self.grad_arena[r, off:off + k].view(p.shape)
+                off += k
+        self.lr_dev = torch.zeros(1, dtype=torch.float32, device="cuda")
+        self.sgd_hyper = {"momentum": momentum, "weight_decay": weight_decay, "nesterov": bool(nesterov),
+                          "zero_grads": bool(zero_grads)}
+        self._sgd = (weight_decay, momentum, int(bool(nesterov)), int(bool(zero_grads)))
+
+    def _sgd_launch(self, compress, lr, lr_dev, iter_dev, stream):
+        """The step of every local row: fused into the sign compress pass (`compress`), or alone."""
+        if self._sgd is None:
+            raise MXError("no SGD state: call attach_sgd() first")
+        m = self.mom_arena.data_ptr() if self.mom_arena is not None else None
+        tail = (float(lr), lr_dev, *self._sgd, iter_dev, self.engine.T if iter_dev else 0, stream_ptr(stream))
+        if compress:
+            check(lib.mx_choco_sign_sgd_compress(self.x.data_ptr(), self.grad_arena.data_ptr(), m,
+                                                 self.x_hat.data_ptr(), self.ld, self.n_local, self.numel,
+                                                 self.msgs.data_ptr(), self.msg_ld, self.work.data_ptr(), *tail),
+                  "mx_choco_sign_sgd_compress")
+        else:
+            check(lib.mx_choco_sgd_step(self.x.data_ptr(), self.grad_arena.data_ptr(), m, self.ld, self.n_local,
+                                        self.numel, *tail), "mx_choco_sgd_step")
+
+    def sgd_compress(self, lr, stream=None):
+        """optimizer.step() + zero_grad() + prepare_comm_buffer of every local row: with compressor="sign"
+        one fused launch (and the finish), with "topk" the step launch, then compress()."""
+        self._sgd_launch(self.sign, lr, None, None, stream)
+        if not self.sign:
+            self.compress(0, stream)
+
+    def sgd_step(self, it, lr, stream=None):
+        """Every local worker's SGD update at learning rate `lr`, then round `it` on the updated rows.
+        sign: the fused step + compress launch, then average(); topk: the step launch, compress(),
+        average().  A round with no active matching is the step launch alone (False is returned): the
+        reference communicates nothing there (communicator.py:249-250) but its optimizers still step."""
+        if not self.engine.any_active[it]:
+            self._sgd_launch(False, lr, None, None, stream)
+            return False
+        self.sgd_compress(lr, stream)
+        self.average(it, stream)
+        return True
+
+    def sgd_device_round(self, stream=None):
+        """Graph-replayable sgd_step: the round is read from `self.iter_dev` and the learning rate from
+        `self.lr_dev` when the kernels run, then the counter is advanced.  The step runs whatever the
+        round (the messages of a round without active matchings are scratch, as device_round's); a
+        counter outside the schedule makes every launch a no-op: no SGD step either.  One GPU only."""
+        if self.engine.comm is not None:
+            raise RuntimeError("sgd_device_round: graph-replayable rounds need all partners on this GPU (nranks = 1)")
+        if self._sgd is None:
+            raise MXError("no SGD state: call attach_sgd() first")
+        self._sgd_launch(self.sign, 0.0, self.lr_dev.data_ptr(), self.iter_dev.data_ptr(), stream)
+        if not self.sign:
+            self.compress(0, stream)
+        self._apply_at(stream)
+
+    def sgd_communicate(self, lr):
+        """optimizer.step() + zero_grad() + communicate() of every worker at the group's own iteration
+        counter; returns seconds like communicate() (a round with no active matching: the step's)."""
+        it = self.iter
+        self.iter += 1
+        torch.cuda.synchronize()
+        tic = time.time()
+        self.sgd_step(it, lr)
+        self.wait_round()
+        toc = time.time()
+        self.check_topk()
+        return toc - tic
 
     def state_dict(self):
         """Checkpoint: rows, the persistent Choco state x_hat / s (communicator.py:179-182) and
@@ -327,6 +433,8 @@ class ChocoWorkerGroup:
                  "s": self.s[:, :P].detach().clone()}
         if self.sign:                        # a top-k group's checkpoint stays key for key what it was
             state["compressor"] = "sign"
+        if self.momentum_rows is not None:   # attach_sgd with momentum; without it, key for key what it was
+            state["momentum_rows"] = self.momentum_rows.detach().clone()
         return state
 
     def load_state_dict(self, state):
@@ -336,7 +444,13 @@ class ChocoWorkerGroup:
                 state.get("compressor", "topk") != self.compressor or \
                 int(state["k"]) != self.k or tuple(state["rows"].shape) != (self.n_local, P):
             raise ValueError("checkpoint does not match this Choco worker group")
+        if ("momentum_rows" in state) != (self.momentum_rows is not None):
+            raise ValueError("checkpoint does not match this Choco worker group: it was saved %s SGD momentum rows, "
+                             "this group is attached %s them" % (("with", "without") if "momentum_rows" in state
+                                                                 else ("without", "with")))
         with torch.no_grad():
+            if self.momentum_rows is not None:
+                self.momentum_rows.copy_(state["momentum_rows"])
             self.x[:, :P].copy_(state["rows"])
             self.x_hat[:, :P].copy_(state["x_hat"])
             self.s[:, :P].copy_(state["s"])

@@ -36,57 +36,13 @@
 // No LDS, no barrier, no error path.  NaN and Inf need no special case: they make scale NaN or Inf, which
 // the arithmetic above propagates.
 #include "choco_round.h"
+#include "choco_sign.h"
 #include "mx_common.h"
 #include "row_walk.h"
 
 namespace {
-using namespace mx::rows;        // GPtr, al16, F4
+using namespace mx::choco::sign;    // the geometry, ld4 / st4 / ld1, pass_of; GPtr, al16, F4
 using mx::choco::round_rec;
-constexpr int kTPB = 256;
-constexpr int kWV = kTPB / 64;
-constexpr int kItem = 4096;              // columns per work item = per workspace slot = per apply tile
-constexpr int kPass = 64 * 4;            // columns a wave covers per pass
-constexpr int kNP = kItem / kWV / kPass; // passes per wave: 4
-constexpr int kHeader = 64;              // bytes of a slot before its bits
-static_assert(kNP * kPass * kWV == kItem, "sign compress geometry");
-
-__host__ __device__ inline int64_t n_items(int64_t P) { return (P + kItem - 1) / kItem; }
-__host__ __device__ inline int64_t n_words(int64_t P) { return 2 * ((P + 63) / 64); }   // uint32 words of bits
-
-template <bool NT>
-__device__ __forceinline__ F4 ld4(const float* p) {
-    if constexpr (NT) return __builtin_nontemporal_load((GPtr<const F4>)(p));
-    else return *(GPtr<const F4>)(p);
-}
-template <bool NT>
-__device__ __forceinline__ void st4(const F4& v, float* p) {
-    if constexpr (NT) __builtin_nontemporal_store(v, (GPtr<F4>)(p));
-    else *(GPtr<F4>)(p) = v;
-}
-__device__ __forceinline__ float ld1(const float* p) { return *(GPtr<const float>)(p); }
-
-// the value of lane + N of the same 16-lane row (row_shl:N; zero past the row's end)
-template <int N>
-__device__ __forceinline__ uint32_t row_up(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x100 + N, 0xf, 0xf, true);
-}
-
-// One pass of a lane: its 4 differences' magnitudes added in column order (returned), and the word of sign
-// bits of the 32 columns that start at the lane's own (valid in lanes 0, 8, ... of the wave)
-__device__ __forceinline__ double pass_of(const float (&d)[4], uint32_t& word) {
-    double acc = 0.0;
-    uint32_t v = 0;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        acc += (double)__builtin_fabsf(d[t]);            // the widening is exact
-        v |= (d[t] < 0.0f ? 1u : 0u) << t;               // false for +0, -0 and NaN
-    }
-    v |= row_up<1>(v) << 4;
-    v |= row_up<2>(v) << 8;
-    v |= row_up<4>(v) << 16;
-    word = v;
-    return acc;
-}
 
 template <bool NT>
 __global__ __launch_bounds__(kTPB) void sign_compress(const float* __restrict__ x, const float* __restrict__ xh,
@@ -324,6 +280,18 @@ int sign_apply_launch(float* x, float* xhat, float* s, int64_t ld, int64_t P, co
 }
 }  // namespace
 
+unsigned mx::choco::sign_grid(int64_t total) {
+    const int64_t target = g_grid > 0 ? (int64_t)g_grid : (int64_t)mx::cu_count() * g_blocks_per_cu;
+    return (unsigned)(total < target ? total : target);
+}
+
+int mx::choco::sign_finish_launch(const double* work, int64_t chunks, int64_t P, char* msgs, int64_t msg_ld_bytes,
+                                  int nrows, hipStream_t st) {
+    hipLaunchKernelGGL(sign_finish, dim3((unsigned)nrows), dim3(kTPB), 0, st, work, chunks, P, msgs, msg_ld_bytes);
+    MX_LAUNCH_CHECK();
+    return MX_OK;
+}
+
 extern "C" int64_t mx_choco_sign_msg_bytes(int64_t P) {
     if (P < 1) {
         mx::set_error("mx_choco_sign_msg_bytes: P=%lld", (long long)P);
@@ -356,19 +324,14 @@ extern "C" int mx_choco_sign_compress(const float* x, const float* x_hat, int64_
              "mx_choco_sign_compress: msg_ld %lld or an unaligned buffer", (long long)msg_ld_bytes);
     hipStream_t st = mx::as_stream(stream);
     const int64_t chunks = n_items(P);
-    const int64_t total = chunks * nrows;
-    const int64_t target = g_grid > 0 ? (int64_t)g_grid : (int64_t)mx::cu_count() * g_blocks_per_cu;
-    const unsigned grid = (unsigned)(total < target ? total : target);
     // the rows of several workers are far larger than the Infinity Cache: non-temporal loads; one row's apply
     // pass finds part of what this pass read still on die (the top-k passes' rule)
     const auto kern = nrows > 1 ? sign_compress<true> : sign_compress<false>;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kTPB), 0, st, x, x_hat, ld, nrows, P, static_cast<char*>(msgs),
-                       msg_ld_bytes, chunks, static_cast<double*>(work));
+    hipLaunchKernelGGL(kern, dim3(mx::choco::sign_grid(chunks * nrows)), dim3(kTPB), 0, st, x, x_hat, ld, nrows, P,
+                       static_cast<char*>(msgs), msg_ld_bytes, chunks, static_cast<double*>(work));
     MX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sign_finish, dim3((unsigned)nrows), dim3(kTPB), 0, st, static_cast<const double*>(work), chunks, P,
-                       static_cast<char*>(msgs), msg_ld_bytes);
-    MX_LAUNCH_CHECK();
-    return MX_OK;
+    return mx::choco::sign_finish_launch(static_cast<const double*>(work), chunks, P, static_cast<char*>(msgs),
+                                         msg_ld_bytes, nrows, st);
 }
 
 extern "C" int mx_choco_sign_apply(float* x, float* xhat, float* s, int64_t ld, int64_t P, const void* msgs,

@@ -200,14 +200,18 @@ class VirtualTrainer:
                  fused_adamw=False, adamw_hyper=None, clip_grad_norm=None, param_groups=None, fused_lion=False,
                  lion_hyper=None, consensus_every=None, fused_qgm=False, qgm_hyper=None, fused_gt=False, gt_hyper=None,
                  slowmo_every=None, slowmo_hyper=None):
-        """fused_sgd=True (non-batched, uncompressed): the workers' optimizer.step() /
+        """fused_sgd=True (non-batched): the workers' optimizer.step() /
         zero_grad() and the gossip round run as ONE launch (VirtualWorkerGroup.attach_sgd /
         sgd_communicate, csrc/sgd_mix.hip): backward() accumulates into the group's gradient arena,
         the optimizers stay constructed only because their param_groups carry the learning-rate
         schedule, and checkpoints save the group's momentum rows.  All-bfloat16 models train in
         mixed precision (attach_sgd(master_weights=True), csrc/sgd_mix_bf16.hip): fp32 master rows
         are updated and mixed, the bfloat16 models are their rounded image, and checkpoints save
-        the masters too.
+        the masters too.  With args.compress and compressor "sign" (ChocoSGD) the step runs inside the
+        scaled-sign compress pass instead (ChocoWorkerGroup.attach_sgd / sgd_communicate,
+        csrc/choco_sgd.hip): fp32 models, no clip_grad_norm, param_groups or slowmo_every.  The trainer
+        keeps refusing fused_sgd with the top-k compressor (a top-k group has the step through
+        ChocoWorkerGroup.attach_sgd); the other fused_* options stay uncompressed.
 
         fused_adamw=True (same conditions, not together with fused_sgd): the same with AdamW's update
         in the launch (VirtualWorkerGroup.attach_adamw / adamw_communicate, csrc/adamw_mix.hip;
@@ -273,9 +277,11 @@ class VirtualTrainer:
         np.random.seed(args.randomSeed)                          # train_mpi.py:62
         torch.manual_seed(args.randomSeed)
         self.fused_sgd = bool(fused_sgd)
-        if self.fused_sgd and (batched or args.compress):
-            raise ValueError("fused_sgd needs per-worker (non-batched), uncompressed training: the vmap path's "
-                             "gradients are fresh tensors every iteration and ChocoSGD mixes compressed messages")
+        if self.fused_sgd and (batched or (args.compress and getattr(args, "compressor", "topk") != "sign")):
+            raise ValueError("fused_sgd needs per-worker (non-batched) training, uncompressed or with the scaled-sign "
+                             "compressor: the vmap path's gradients are fresh tensors every iteration, and the step is "
+                             "fused into the sign compress pass only (a top-k group takes it through "
+                             "ChocoWorkerGroup.attach_sgd, not through the trainer)")
         self.fused_adamw = bool(fused_adamw)
         if self.fused_adamw and self.fused_sgd:
             raise ValueError("fused_adamw and fused_sgd are mutually exclusive: the group carries one optimizer")
@@ -333,6 +339,9 @@ class VirtualTrainer:
             torch.manual_seed(args.randomSeed + r)                # train_mpi.py:61, per rank
             self.models.append(model_fn().to(device))
         if args.compress:
+            if self.fused_sgd and any(p.dtype != torch.float32 for p in self.models[0].parameters()):
+                raise ValueError("fused_sgd with compress needs float32 models: ChocoWorkerGroup's rows and its SGD "
+                                 "step are fp32-only")
             compressor = getattr(args, "compressor", "topk")
             self.group = ChocoWorkerGroup(self.GP, self.models, consensus_lr=args.consensus_lr, compressor=compressor,
                                           ratio=None if compressor == "sign" else args.ratio)   # sign takes no ratio
@@ -342,7 +351,13 @@ class VirtualTrainer:
             self.group = VirtualWorkerGroup(self.GP, self.models,
                                             dtype=torch.bfloat16 if dts == {torch.bfloat16} else torch.float32)
         mixed = self.fused and self.group.dtype == torch.bfloat16
-        if self.fused_sgd:
+        if self.fused_sgd and args.compress:
+            # ChocoSGD, sign compressor: the step runs inside the compress pass (csrc/choco_sgd.hip); no clipping, no groups
+            if clip_grad_norm is not None or param_groups is not None or slowmo_every is not None:
+                raise ValueError("fused_sgd with compress takes no clip_grad_norm, param_groups or slowmo_every: "
+                                 "ChocoWorkerGroup.attach_sgd has none of them")
+            self.group.attach_sgd(args.momentum, 5e-4, args.nesterov)
+        elif self.fused_sgd:
             # all-bfloat16 models: fp32 master weights, updated and mixed by the launch (csrc/sgd_mix_bf16.hip)
             self.group.attach_sgd(args.momentum, 5e-4, args.nesterov, master_weights=mixed,
                                   clip_grad_norm=clip_grad_norm, param_groups=param_groups)

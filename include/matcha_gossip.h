@@ -1229,6 +1229,30 @@ int mx_choco_sign_apply_at(float* x, float* xhat, float* s, int64_t ld, int64_t 
 int mx_choco_sign_set(const char* key, int value);
 int mx_choco_sign_get(const char* key);
 
+/* ---------------------------------------------------------------- ChocoSGD, the SGD step fused in
+ * optimizer.step() + zero_grad() of every row (train_mpi.py:131-142; torch.optim.SGD, dampening 0) on the way
+ * into the compressor (communicator.py:175-196), for `nrows` rows `ld` floats apart:
+ *   d = weight_decay != 0 ? fma(weight_decay, x, g) : g
+ *   [momentum != 0]  m = f32(momentum * m) + d;  d = nesterov ? fma(momentum, m, d) : m
+ *   x = fma(-lr, d, x);  g = +0 under zero_grads
+ * lr_dev non-NULL: the learning rate is read from it when the kernel runs (`lr` ignored).  iter_dev non-NULL:
+ * the launch leaves everything untouched when *iter_dev is outside [0, n_iters) (graph-replayable rounds; no
+ * SGD step past the schedule).  m is given exactly when momentum != 0; nesterov needs momentum.
+ *
+ * mx_choco_sign_sgd_compress: the step, then mx_choco_sign_compress of the updated rows against x_hat (not
+ * NULL here), as ONE pass over x, g, m and x_hat plus the finish launch: msgs / msg_ld_bytes / work as
+ * mx_choco_sign_compress.  x, m and g are exact; the bits are those of fsub(x', x_hat); the scale is the same
+ * bits mx_choco_sign_compress writes when run on the updated rows. */
+int mx_choco_sign_sgd_compress(float* x, float* g, float* m, const float* x_hat, int64_t ld, int nrows, int64_t P,
+                               void* msgs, int64_t msg_ld_bytes, void* work, float lr, const float* lr_dev,
+                               float weight_decay, float momentum, int nesterov, int zero_grads,
+                               const int64_t* iter_dev, int64_t n_iters, void* stream);
+/* The step alone (train_mpi.py:131-142), one launch: top-k groups before mx_topk_abs_diff_rows, and rounds with
+ * no active matching, which communicate nothing (communicator.py:249-250) but still step. */
+int mx_choco_sgd_step(float* x, float* g, float* m, int64_t ld, int nrows, int64_t P, float lr, const float* lr_dev,
+                      float weight_decay, float momentum, int nesterov, int zero_grads, const int64_t* iter_dev,
+                      int64_t n_iters, void* stream);
+
 /* ---------------------------------------------------------------- cross-GPU exchange (RCCL)
  * One process per GPU; workers partitioned by owner[].  mx_exchange_round posts, inside one
  * ncclGroupStart/End, an ncclSend of every local row whose active partner lives on another

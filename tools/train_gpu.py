@@ -4,6 +4,8 @@
     python tools/train_gpu.py --compress --budget 0.5                           # ChocoSGD
     python tools/train_gpu.py --momentum 0.9 --fused-sgd                        # SGD step fused into the round
     python tools/train_gpu.py --momentum 0.9 --fused-sgd --bf16                 # the same, bf16 models + fp32 masters
+    python tools/train_gpu.py --compress --compressor sign --fused-sgd --momentum 0.9
+                                                                                # ChocoSGD, SGD step fused into the compress pass
     python tools/train_gpu.py --lr 1e-3 --no-warmup --fused-adamw --wd 1e-2       # AdamW step fused into the round
     python tools/train_gpu.py --lr 1e-3 --no-warmup --fused-adamw --wd 1e-2 --bf16 # the same, bf16 models + fp32 masters
     python tools/train_gpu.py --lr 1e-4 --no-warmup --fused-lion --wd 1e-2 --bf16 --lion-bf16-momentum
