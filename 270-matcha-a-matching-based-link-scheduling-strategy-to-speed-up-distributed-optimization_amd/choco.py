@@ -9,6 +9,10 @@ With compressor="sign" the message is the scaled-sign (1-bit) quantizer Q(v) = (
 (csrc/choco_sign.hip): q_r = (scale_r, one bit per column, set where x_r - x_hat_r < 0), P/8 bytes on the
 wire; mx_choco_sign_compress and the elementwise mx_choco_sign_apply take the two kernels' places.  A 1-bit
 message has no zero: a zero difference travels as +scale (torch.sign would give 0).
+With compressor="quant" it is the bucketed stochastic quantizer at bits = 4 or 8 (csrc/choco_quant.hip: QSGD's
+qsgd_s normalised per 256 columns): q_r = (one fp32 norm per bucket, one sign-and-level code per column), drawn
+from a counter-based hash of (seed, round, worker, column); mx_choco_quant_compress is one launch with no
+workspace, mx_choco_quant_apply the elementwise apply.
 Under PullTransport (N > 1, one process per GPU of a node) the messages are not sent: every rank
 publishes the messages its peers read this round into its IPC-shared snapshot buffer
 (mx_snapshot_publish_rows), the device
@@ -33,15 +37,17 @@ def topk_count(P, ratio):
     return max(1, int(P * (1 - ratio)))
 
 
-COMPRESSORS = ("topk", "sign")
+COMPRESSORS = ("topk", "sign", "quant")
 
 
 class ChocoWorkerGroup:
     def __init__(self, topology, models=None, numel=None, *, ratio=None, consensus_lr, rank=0, nranks=1,
                  comm=None, adopt=True, placement=None, pull_read="fetch", dtype=torch.float32,
-                 compressor="topk"):
-        """compressor: "topk" (compressors.get_top_k; `ratio` required) or "sign" (the scaled-sign
-        quantizer; takes no `ratio`, k = 0, check_topk() has nothing to check, PullTransport not built).
+                 compressor="topk", bits=None, seed=0):
+        """compressor: "topk" (compressors.get_top_k; `ratio` required), "sign" (the scaled-sign
+        quantizer) or "quant" (the bucketed stochastic quantizer: `bits` 4 or 8, default 8; `seed` of its
+        counter-based random numbers); the last two take no `ratio`, have k = 0 and nothing for check_topk()
+        to check, and PullTransport is not built for them.
         placement: as VirtualWorkerGroup (None / "contiguous", "auto" or a worker order);
         `workers` lists the worker id of each local row.  pull_read (PullTransport only): "fetch"
         (default) copies the round's partner messages from their owners' snapshots into the receive
@@ -54,13 +60,20 @@ class ChocoWorkerGroup:
             raise ValueError(f"compressor must be one of {COMPRESSORS}, not {compressor!r}")
         if compressor == "topk" and ratio is None:
             raise ValueError("ChocoWorkerGroup: compressor='topk' needs a ratio")
-        if compressor == "sign" and ratio is not None:
-            raise ValueError("ChocoWorkerGroup: compressor='sign' takes no ratio")
-        if compressor == "sign" and isinstance(comm, PullTransport):
-            raise NotImplementedError("ChocoWorkerGroup: compressor='sign' under PullTransport -- the publish / "
-                                      "gate / fetch sizing of sign messages is not built")
+        if compressor != "topk" and ratio is not None:
+            raise ValueError(f"ChocoWorkerGroup: compressor={compressor!r} takes no ratio")
+        if compressor != "topk" and isinstance(comm, PullTransport):
+            raise NotImplementedError(f"ChocoWorkerGroup: compressor={compressor!r} under PullTransport -- the "
+                                      "publish / gate / fetch sizing of its messages is not built")
+        if bits is not None and compressor != "quant":
+            raise ValueError(f"ChocoWorkerGroup: bits belongs to compressor='quant', not {compressor!r}")
+        if compressor == "quant" and (8 if bits is None else bits) not in (4, 8):
+            raise ValueError(f"ChocoWorkerGroup: compressor='quant' has bits 4 or 8, not {bits!r}")
         self.compressor = compressor
         self.sign = compressor == "sign"
+        self.quant = compressor == "quant"
+        self.bits = (8 if bits is None else int(bits)) if self.quant else None
+        self.seed = int(seed)
         if dtype != torch.float32:
             # only VirtualWorkerGroup's mixing round has a bfloat16 form (csrc/mix_bf16.hip)
             raise NotImplementedError(f"ChocoWorkerGroup: {dtype} rows -- the top-k and apply kernels are fp32-only")
@@ -108,7 +121,12 @@ class ChocoWorkerGroup:
                     if adopt:
                         p.data = view
                     off += k
-        if self.sign:
+        if self.quant:
+            # header 64 | norm f32[ceil(P/256)] padded to 64 | codes uint8[32 bits ceil(P/256)]; no workspace
+            self.k = self.kpad = self.work_ld = 0
+            self.msg_bytes = int(lib.mx_choco_quant_msg_bytes(P, self.bits))
+            self.codes_off = 64 + 64 * ((P + 4095) // 4096)
+        elif self.sign:
             # scale f32 | L f64 | P int64 | zeros to 64 | bits uint8[8 ceil(P/64)] (mx_choco_sign_compress)
             self.k = self.kpad = 0
             self.msg_bytes = int(lib.mx_choco_sign_msg_bytes(P))
@@ -123,7 +141,7 @@ class ChocoWorkerGroup:
         self.msg_ld = (self.msg_bytes + 255) // 256 * 256
         self.msgs = torch.empty(self.engine.n_slots * self.msg_ld, dtype=torch.uint8, device="cuda")
         self.work = torch.zeros(self.n_local * self.work_ld, dtype=torch.uint8, device="cuda")  # zero on first use
-        self.apply_work = torch.empty(0 if self.sign else int(lib.mx_choco_apply_work_bytes(P, self.engine.n_slots)),
+        self.apply_work = torch.empty(0 if self.k == 0 else int(lib.mx_choco_apply_work_bytes(P, self.engine.n_slots)),
                                       dtype=torch.uint8, device="cuda")
         self.gamma32 = float(np.float32(consensus_lr))
         self.iter_dev = torch.zeros(1, dtype=torch.int64, device="cuda")   # device_round's counter
@@ -172,8 +190,11 @@ class ChocoWorkerGroup:
     def message(self, slot):
         """(values float32[k], indices int64[k]) views of message `slot` (index-sorted); with
         compressor="sign": (scale, a 0-dim float32 view, bits uint8[ceil(P/8)], column c = bit c & 7 of
-        byte c >> 3)."""
+        byte c >> 3); with compressor="quant": (norms float32[ceil(P/256)], codes uint8[ceil(P bits / 8)])."""
         base = slot * self.msg_ld
+        if self.quant:
+            return (self.msgs[base + 64:base + 64 + 4 * ((self.numel + 255) // 256)].view(torch.float32),
+                    self.msgs[base + self.codes_off:base + self.codes_off + (self.numel * self.bits + 7) // 8])
         if self.sign:
             return (self.msgs[base:base + 4].view(torch.float32)[0],
                     self.msgs[base + 64:base + 64 + (self.numel + 7) // 8])
@@ -183,7 +204,10 @@ class ChocoWorkerGroup:
 
     def compress(self, it, stream=None):
         """prepare_comm_buffer (communicator.py:175-196): every local row's top-k message of
-        x - x_hat into its message slot (compressor="sign": its scaled-sign message)."""
+        x - x_hat into its message slot (compressor="sign": its scaled-sign message; "quant": its quantized
+        message of round `it`)."""
+        if self.quant:
+            return self._quant_compress(int(it), None, stream)
         if self.sign:
             check(lib.mx_choco_sign_compress(self.x.data_ptr(), self.x_hat.data_ptr(), self.ld, self.n_local,
                                              self.numel, self.msgs.data_ptr(), self.msg_ld, self.work.data_ptr(),
@@ -193,6 +217,19 @@ class ChocoWorkerGroup:
                                         self.numel, self.k, self.msgs.data_ptr(), self.msg_ld, 4 * self.kpad,
                                         self.bnd_off, self.work.data_ptr(), self.work_ld, stream_ptr(stream)),
               "mx_topk_abs_diff_rows")
+
+    def _quant_compress(self, it, iter_dev, stream=None):
+        """mx_choco_quant_compress at round `it`, or at the device counter (`iter_dev`: its address)"""
+        check(lib.mx_choco_quant_compress(self.x.data_ptr(), self.x_hat.data_ptr(), self.ld, self.n_local, self.numel,
+                                          self.bits, self.msgs.data_ptr(), self.msg_ld, self.seed, it, iter_dev,
+                                          self.engine.T if iter_dev else 0, self.row_base, stream_ptr(stream)),
+              "mx_choco_quant_compress")
+
+    def _compress_at(self, stream=None):
+        """compress() of a graph-replayable round: the quantizer reads its round from the device counter"""
+        if self.quant:
+            return self._quant_compress(0, self.iter_dev.data_ptr(), stream)
+        self.compress(0, stream)
 
     def wait_round(self, stream=None):
         """The end of a round for communicate(): the transport's wait (engine.wait_round), then
@@ -221,8 +258,8 @@ class ChocoWorkerGroup:
     def check_topk(self, stream=None):
         """Synchronise and raise MXError if a top-k row barrier's bounded wait expired since the
         last check (mx_topk_check: that round's messages are undefined; never a GPU hang).  Nothing to
-        check with compressor="sign": its kernels have no barrier and no wait."""
-        if self.sign:
+        check with compressor="sign" or "quant": their kernels have no barrier and no wait."""
+        if self.k == 0:
             return
         check(lib.mx_topk_check(self.work.data_ptr(), self.work_ld, self.n_local, self.numel, stream_ptr(stream)),
               "mx_topk_check")
@@ -238,6 +275,13 @@ class ChocoWorkerGroup:
         if self.engine.comm is not None:
             self.engine.exchange(it, [mbase + r * self.msg_ld for r in range(self.n_local)],
                                  mbase + self.n_local * self.msg_ld, self.msg_ld, self.msg_bytes, stream)
+        if self.quant:
+            check(lib.mx_choco_quant_apply(self.x.data_ptr(), self.x_hat.data_ptr(), self.s.data_ptr(), self.ld,
+                                           self.numel, self.bits, mbase, self.msg_ld, self.engine.n_slots,
+                                           self.engine.plan.data_ptr(), int(it), self.n_local, self.engine.M,
+                                           self.engine.alpha32, self.gamma32, stream_ptr(stream)),
+                  "mx_choco_quant_apply")
+            return
         if self.sign:
             check(lib.mx_choco_sign_apply(self.x.data_ptr(), self.x_hat.data_ptr(), self.s.data_ptr(), self.ld,
                                           self.numel, mbase, self.msg_ld, self.engine.n_slots,
@@ -298,14 +342,20 @@ class ChocoWorkerGroup:
         communicator.py:249-250; the messages written meanwhile are scratch).  One GPU only."""
         if self.engine.comm is not None:
             raise RuntimeError("device_round: graph-replayable rounds need all partners on this GPU (nranks = 1)")
-        self.compress(0, stream)
+        self._compress_at(stream)
         self._apply_at(stream)
 
     def _apply_at(self, stream=None):
         """The apply launch at the device counter, then the counter's advance (device_round,
         sgd_device_round)."""
         sp = stream_ptr(stream)
-        if self.sign:
+        if self.quant:
+            check(lib.mx_choco_quant_apply_at(self.x.data_ptr(), self.x_hat.data_ptr(), self.s.data_ptr(), self.ld,
+                                              self.numel, self.bits, self.msgs.data_ptr(), self.msg_ld,
+                                              self.engine.n_slots, self.engine.plan.data_ptr(),
+                                              self.iter_dev.data_ptr(), self.engine.T, self.n_local, self.engine.M,
+                                              self.engine.alpha32, self.gamma32, sp), "mx_choco_quant_apply_at")
+        elif self.sign:
             check(lib.mx_choco_sign_apply_at(self.x.data_ptr(), self.x_hat.data_ptr(), self.s.data_ptr(), self.ld,
                                              self.numel, self.msgs.data_ptr(), self.msg_ld, self.engine.n_slots,
                                              self.engine.plan.data_ptr(), self.iter_dev.data_ptr(), self.engine.T,
@@ -377,12 +427,12 @@ class ChocoWorkerGroup:
             check(lib.mx_choco_sgd_step(self.x.data_ptr(), self.grad_arena.data_ptr(), m, self.ld, self.n_local,
                                         self.numel, *tail), "mx_choco_sgd_step")
 
-    def sgd_compress(self, lr, stream=None):
+    def sgd_compress(self, lr, stream=None, it=0):
         """optimizer.step() + zero_grad() + prepare_comm_buffer of every local row: with compressor="sign"
-        one fused launch (and the finish), with "topk" the step launch, then compress()."""
+        one fused launch (and the finish), with "topk" and "quant" the step launch, then compress(it)."""
         self._sgd_launch(self.sign, lr, None, None, stream)
         if not self.sign:
-            self.compress(0, stream)
+            self.compress(it, stream)
 
     def sgd_step(self, it, lr, stream=None):
         """Every local worker's SGD update at learning rate `lr`, then round `it` on the updated rows.
@@ -392,7 +442,7 @@ class ChocoWorkerGroup:
         if not self.engine.any_active[it]:
             self._sgd_launch(False, lr, None, None, stream)
             return False
-        self.sgd_compress(lr, stream)
+        self.sgd_compress(lr, stream, it)
         self.average(it, stream)
         return True
 
@@ -407,7 +457,7 @@ class ChocoWorkerGroup:
             raise MXError("no SGD state: call attach_sgd() first")
         self._sgd_launch(self.sign, 0.0, self.lr_dev.data_ptr(), self.iter_dev.data_ptr(), stream)
         if not self.sign:
-            self.compress(0, stream)
+            self._compress_at(stream)
         self._apply_at(stream)
 
     def sgd_communicate(self, lr):
@@ -433,6 +483,8 @@ class ChocoWorkerGroup:
                  "s": self.s[:, :P].detach().clone()}
         if self.sign:                        # a top-k group's checkpoint stays key for key what it was
             state["compressor"] = "sign"
+        if self.quant:
+            state.update(compressor="quant", bits=self.bits, seed=self.seed)
         if self.momentum_rows is not None:   # attach_sgd with momentum; without it, key for key what it was
             state["momentum_rows"] = self.momentum_rows.detach().clone()
         return state
@@ -441,7 +493,7 @@ class ChocoWorkerGroup:
         P = self.numel
         if state.get("kind") != "choco" or int(state["row_base"]) != self.row_base or \
                 list(state.get("workers", self.workers)) != self.workers or \
-                state.get("compressor", "topk") != self.compressor or \
+                state.get("compressor", "topk") != self.compressor or state.get("bits") != self.bits or \
                 int(state["k"]) != self.k or tuple(state["rows"].shape) != (self.n_local, P):
             raise ValueError("checkpoint does not match this Choco worker group")
         if ("momentum_rows" in state) != (self.momentum_rows is not None):
@@ -455,6 +507,8 @@ class ChocoWorkerGroup:
             self.x_hat[:, :P].copy_(state["x_hat"])
             self.s[:, :P].copy_(state["s"])
         self.iter = int(state["iter"])
+        if self.quant:
+            self.seed = int(state["seed"])       # the resumed run draws the saved run's random numbers
 
     def communicate(self):
         it = self.iter

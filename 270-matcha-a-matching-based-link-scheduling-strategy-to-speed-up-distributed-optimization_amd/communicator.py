@@ -364,11 +364,13 @@ class decenCommunicator(Communicator):
 
 class ChocoCommunicator(Communicator):
     """communicator.py:161-268 -- top-k compressed gossip with persistent x_hat / s.  compressor="sign":
-    the scaled-sign (1-bit) quantizer in top-k's place (`ratio` is then not used)."""
+    the scaled-sign (1-bit) quantizer in top-k's place; compressor="quant": the bucketed stochastic quantizer
+    at `bits` = 4 or 8 (`ratio` is then not used)."""
 
-    def __init__(self, rank, size, topology, ratio, consensus_lr, *, transport=None, compressor="topk"):
+    def __init__(self, rank, size, topology, ratio, consensus_lr, *, transport=None, compressor="topk", bits=None):
         super(ChocoCommunicator, self).__init__(rank, size, transport=transport)
         self.compressor = compressor
+        self.bits = bits
         self.topology = topology
         self.neighbor_weight = topology.neighbor_weight
         self.iter = 0
@@ -387,7 +389,9 @@ class ChocoCommunicator(Communicator):
         return self._group.s[0, :self._group.numel] if self._group is not None else None
 
     def _compressor_args(self):
-        """what ChocoWorkerGroup takes for this communicator's compressor (the sign quantizer has no ratio)"""
+        """what ChocoWorkerGroup takes for this communicator's compressor (the quantizers have no ratio)"""
+        if self.compressor == "quant":
+            return {"compressor": "quant", "bits": self.bits}
         return {"compressor": "sign"} if self.compressor == "sign" else {"ratio": self.ratio, "compressor": self.compressor}
 
     def _bind(self, model):
@@ -438,7 +442,7 @@ class ChocoCommunicator(Communicator):
         """communicator.py:175-196: `self.tensor_list` into this rank's x row (copied, or used in
         place when it lives there), x_hat / s created zero on first use (they persist), then the
         top-k of x - x_hat; `compressed` = {"values", "indices"} views of the message (GPU,
-        index-sorted; compressor="sign": {"scale", "bits"}).  Returns the compression seconds (the reference's encode time)."""
+        index-sorted; compressor="sign": {"scale", "bits"}; "quant": {"norms", "codes"}).  Returns the compression seconds (the reference's encode time)."""
         tensors = list(self.tensor_list)
         n = int(sum(t.numel() for t in tensors))
         if self._group is not None and self._group.numel != n:
@@ -452,6 +456,10 @@ class ChocoCommunicator(Communicator):
         self._group.compress(self.iter)
         self._group.check_topk()
         toc = time.time()
+        if self.compressor == "quant":
+            norms, codes = self._group.message(0)
+            self.compressed = {"norms": norms, "codes": codes}
+            return toc - tic
         if self.compressor == "sign":
             scale, bits = self._group.message(0)
             self.compressed = {"scale": scale, "bits": bits}

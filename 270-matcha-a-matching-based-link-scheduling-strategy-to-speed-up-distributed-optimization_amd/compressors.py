@@ -125,3 +125,48 @@ def unpack_scaled_sign(scale, bits, numel):
     """The dense float32 [numel] message of get_scaled_sign's (scale, bits): -scale where the bit is set."""
     neg = ((bits[:, None] >> torch.arange(8, device=bits.device, dtype=torch.uint8)) & 1).reshape(-1)[:numel].bool()
     return torch.where(neg, -scale, scale)
+
+
+def get_quantized(x, bits=8, seed=0, round=0, row=0):
+    """The bucketed stochastic quantizer (QSGD's qsgd_s per bucket of 256, rescaled to a contraction) of a
+    float32 tensor, flattened, at `bits` = 4 or 8: returns (norms, codes) -- norms float32[ceil(P/256)], the
+    buckets' 2-norms, and codes uint8[ceil(P bits / 8)], column c's sign << (bits - 1) | level in byte c
+    (8 bits) or nibble c & 1 of byte c >> 1 (4 bits).  The random numbers are a hash of (seed, round, row,
+    column): the same arguments give the same message.  The one-row mx_choco_quant_compress without an x_hat,
+    on any alignment; CPU input is staged to the GPU and the result returned on the input's device."""
+    x_data = x.reshape(-1)
+    if x_data.dtype != torch.float32:
+        raise TypeError("get_quantized: a float32 tensor is required")
+    host = x_data.device.type != "cuda"
+    if host:
+        x_data = x_data.to("cuda")
+    x_data = x_data.contiguous()
+    dev = x_data.device
+    P = x_data.numel()
+    nbytes = int(lib.mx_choco_quant_msg_bytes(P, int(bits)))
+    if nbytes < 0:
+        raise ValueError(f"get_quantized: an empty tensor, or bits={bits!r} (4 or 8)")
+    msg = torch.empty(nbytes // 8, dtype=torch.int64, device=dev).view(torch.uint8)   # 8-byte aligned
+    with torch.cuda.device(dev):
+        check(lib.mx_choco_quant_compress(x_data.data_ptr(), None, P, 1, P, int(bits), msg.data_ptr(), nbytes,
+                                          int(seed), int(round), None, 0, int(row), stream_ptr()),
+              "mx_choco_quant_compress")
+    off = 64 + 64 * ((P + 4095) // 4096)
+    norms = msg[64:64 + 4 * ((P + 255) // 256)].view(torch.float32)
+    codes = msg[off:off + (P * int(bits) + 7) // 8]
+    if host:
+        return norms.to(x.device), codes.to(x.device)
+    return norms, codes
+
+
+def unpack_quantized(norms, codes, numel, bits):
+    """The dense float32 [numel] message of get_quantized's (norms, codes): sign * level * (norm * c) per
+    bucket, c = f32(1 / (s tau)) with s = 2^(bits-1) - 1 and tau = 1 + min(256 / s^2, 16 / s)."""
+    s = (1 << (bits - 1)) - 1
+    c = torch.tensor(1.0 / (s * (1.0 + min(256.0 / (s * s), 16.0 / s))), dtype=torch.float32, device=norms.device)
+    if bits == 4:
+        codes = torch.stack([codes & 15, codes >> 4], 1).reshape(-1)
+    codes = codes[:numel].to(torch.int32)
+    unit = (norms * c).repeat_interleave(256)[:numel]
+    mag = (codes & s).to(torch.float32) * unit
+    return torch.where((codes >> (bits - 1)).bool(), -mag, mag)

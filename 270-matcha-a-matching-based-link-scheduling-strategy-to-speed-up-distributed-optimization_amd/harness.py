@@ -343,8 +343,10 @@ class VirtualTrainer:
                 raise ValueError("fused_sgd with compress needs float32 models: ChocoWorkerGroup's rows and its SGD "
                                  "step are fp32-only")
             compressor = getattr(args, "compressor", "topk")
+            extra = {"bits": getattr(args, "quant_bits", 8)} if compressor == "quant" else {}
             self.group = ChocoWorkerGroup(self.GP, self.models, consensus_lr=args.consensus_lr, compressor=compressor,
-                                          ratio=None if compressor == "sign" else args.ratio)   # sign takes no ratio
+                                          ratio=args.ratio if compressor == "topk" else None,   # only top-k has a ratio
+                                          **extra)
         else:
             # bfloat16 models are mixed as bfloat16 rows (half the bytes per round), like decenCommunicator
             dts = {p.dtype for m in self.models for p in m.parameters()}
@@ -751,9 +753,11 @@ class RankTrainer:
 class HarnessArgs:
     """train_mpi.py:205-231 defaults, plus the harness's own (size, shape, num_classes, ratio, compressor)."""
 
-    # with compress: "topk" (the reference's) or "sign" (the scaled-sign quantizer; VirtualTrainer).  A class
-    # default, so the argument line a run logs changes only when it is set
+    # with compress: "topk" (the reference's), "sign" (the scaled-sign quantizer) or "quant" (the bucketed
+    # stochastic quantizer at quant_bits = 4 or 8); VirtualTrainer.  Class defaults, so the argument line a run
+    # logs changes only when they are set
     compressor = "topk"
+    quant_bits = 8
 
     def __init__(self, **kw):
         self.name = "Vanilla DecenSGD-synthetic"

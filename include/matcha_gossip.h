@@ -1253,6 +1253,45 @@ int mx_choco_sgd_step(float* x, float* g, float* m, int64_t ld, int nrows, int64
                       float weight_decay, float momentum, int nesterov, int zero_grads, const int64_t* iter_dev,
                       int64_t n_iters, void* stream);
 
+/* ---------------------------------------------------------------- ChocoSGD, bucketed stochastic quantizer
+ * QSGD's qsgd_s at bits = 4 or 8, normalised per bucket of 256 columns and rescaled to a contraction, in place
+ * of compressors.get_top_k in prepare_comm_buffer (communicator.py:175-196) and averaging
+ * (communicator.py:200-230).  s = 2^(bits-1) - 1, tau = 1 + min(256 / s^2, 16 / s), c = f32(1 / (s tau)).  For
+ * bucket b (columns [256 b, 256 b + 256), +0 at and past P) of a row with d = x - x_hat (x_hat NULL: d = x):
+ *   norm = f32(sqrt_f64(sum f64(d) f64(d)));  inv = norm == 0 ? 0 : f32(s) / norm
+ *   xi[c] = f32(mix32(key + u32(c)) >> 8) 2^-24;  v = fadd(fmul(|d[c]|, inv), xi[c])
+ *   level = v >= 1 ? min(s, floor(v)) : 0;  neg = d[c] < 0;  q[c] = (neg ? -1 : 1) f32(level) fmul(norm, c)
+ *   mix32(h): h ^= h>>16; h *= 0x7feb352d; h ^= h>>15; h *= 0x846ca68b; h ^= h>>16 (uint32)
+ *   key = mix32(mix32(mix32(u32(seed)) ^ u32(round)) ^ u32(row_base + r))
+ * A message slot holds mx_choco_quant_msg_bytes(P, bits) = 64 + 64 ceil(nb/16) + 32 bits nb bytes, nb =
+ * ceil(P/256) (communicator.py:175-230: the send buffer): int64 P at 16, int32 bits at 24, int32 256 at 28,
+ * zeros elsewhere up to 64; fp32 norm[nb] zero-padded to 64 bytes; the codes neg << (bits-1) | level to the
+ * end of the last bucket (zero at and past P) -- 8 bits: column c is byte c; 4 bits: nibble c & 1 of byte
+ * c >> 1.  -1 for P < 1 or bits not 4 or 8. */
+int64_t mx_choco_quant_msg_bytes(int64_t P, int bits);
+/* prepare_comm_buffer (communicator.py:175-230) of `nrows` rows, ONE launch with no scratch: row r reads
+ * x + r*ld (and x_hat + r*ld; x_hat may be NULL) and writes every byte of its slot at msgs + r*msg_ld_bytes
+ * (8-byte aligned, msg_ld_bytes a multiple of 8 and >= mx_choco_quant_msg_bytes; ignored for one row).  The
+ * round is `round`, or with round_dev non-NULL *round_dev when the kernel runs -- outside [0, n_rounds) the
+ * launch writes nothing.  seed, the round and row_base + r enter by their low 32 bits.  A norm depends on its
+ * bucket's values alone -- the same bits for any row count, grid or knob -- and is within 1 fp32 ulp of the
+ * correctly rounded value; everything else is exact given the norms. */
+int mx_choco_quant_compress(const float* x, const float* x_hat, int64_t ld, int nrows, int64_t P, int bits,
+                            void* msgs, int64_t msg_ld_bytes, int64_t seed, int64_t round, const int64_t* round_dev,
+                            int64_t n_rounds, int row_base, void* stream);
+/* averaging (communicator.py:175-230) on those messages, in place: mx_choco_sign_apply's update with this q. */
+int mx_choco_quant_apply(float* x, float* xhat, float* s, int64_t ld, int64_t P, int bits, const void* msgs,
+                         int64_t msg_ld_bytes, int n_slots, const int32_t* plan_dev, int64_t iter, int n_local,
+                         int M, float alpha, float gamma, void* stream);
+/* Graph-replayable form (communicator.py:175-230; the no-op rules of mx_choco_apply_at). */
+int mx_choco_quant_apply_at(float* x, float* xhat, float* s, int64_t ld, int64_t P, int bits, const void* msgs,
+                            int64_t msg_ld_bytes, int n_slots, const int32_t* plan_dev, const int64_t* iter_dev,
+                            int64_t n_iters, int n_local, int M, float alpha, float gamma, void* stream);
+/* Knobs of the quantizer passes (communicator.py:175-230 has none; speed only, never results): "apply_nt",
+ * "blocks_per_cu" and "grid" as mx_choco_sign_set's, with their own values. */
+int mx_choco_quant_set(const char* key, int value);
+int mx_choco_quant_get(const char* key);
+
 /* ---------------------------------------------------------------- cross-GPU exchange (RCCL)
  * One process per GPU; workers partitioned by owner[].  mx_exchange_round posts, inside one
  * ncclGroupStart/End, an ncclSend of every local row whose active partner lives on another

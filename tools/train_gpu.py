@@ -45,8 +45,11 @@ def main():
     ap.add_argument("--savePath", default="./saveModel")
     ap.add_argument("--save", action="store_true")
     ap.add_argument("--compress", action="store_true")
-    ap.add_argument("--compressor", default=None, choices=("topk", "sign"), help="--compress: the message -- topk "
-                    "(default: the reference's top 10 %) or sign (the scaled-sign 1-bit quantizer; one process)")
+    ap.add_argument("--compressor", default=None, choices=("topk", "sign", "quant"), help="--compress: the message -- "
+                    "topk (default: the reference's top 10 %), sign (the scaled-sign 1-bit quantizer) or quant (the "
+                    "bucketed stochastic quantizer, --quant-bits); sign and quant: one process")
+    ap.add_argument("--quant-bits", default=None, type=int, choices=(4, 8), help="--compressor quant: bits per "
+                    "element (default 8)")
     ap.add_argument("--consensus_lr", default=0.1, type=float)
     ap.add_argument("--randomSeed", default=1234, type=int)
     ap.add_argument("--workers", default=8, type=int)
@@ -139,9 +142,13 @@ def main():
                          compress=a.compress, consensus_lr=a.consensus_lr, randomSeed=a.randomSeed,
                          size=a.workers if world == 1 else world)
     if a.compressor is not None:
-        if a.compressor == "sign" and world > 1:
-            ap.error("--compressor sign: one process (the per-GPU trainer keeps the top-k message)")
+        if a.compressor != "topk" and world > 1:
+            ap.error(f"--compressor {a.compressor}: one process (the per-GPU trainer keeps the top-k message)")
         args.compressor = a.compressor
+    if a.quant_bits is not None:
+        if a.compressor != "quant":
+            ap.error("--quant-bits belongs to --compressor quant")
+        args.quant_bits = a.quant_bits
     import torch
     model_fn = H.model_factory(args)
     if a.bf16:
