@@ -90,6 +90,16 @@ SIGNATURES = {
                                         c_int, c_int, c_f32, c_f32, c_p]),
     "mx_choco_quant_set": (c_int, [ctypes.c_char_p, c_int]),
     "mx_choco_quant_get": (c_int, [ctypes.c_char_p]),
+    "mx_choco_quant_round": (c_int, [c_p, c_p, c_p, c_i64, c_int, c_i64, c_int, c_p, c_i64, c_int, c_f32, c_f32,
+                                     c_i64, c_int, c_p, c_i64, c_p]),
+    "mx_choco_quant_round_at": (c_int, [c_p, c_p, c_p, c_i64, c_int, c_i64, c_int, c_p, c_p, c_i64, c_int, c_f32,
+                                        c_f32, c_i64, c_int, c_p, c_i64, c_p]),
+    "mx_choco_quant_sgd_round": (c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_i64, c_int, c_p, c_i64, c_int,
+                                         c_f32, c_f32, c_i64, c_int, c_p, c_i64, c_f32, c_p, c_f32, c_f32, c_int,
+                                         c_int, c_p]),
+    "mx_choco_quant_sgd_round_at": (c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_i64, c_int, c_p, c_p, c_i64,
+                                            c_int, c_f32, c_f32, c_i64, c_int, c_p, c_i64, c_f32, c_p, c_f32, c_f32,
+                                            c_int, c_int, c_p]),
     "mx_pull_fetch": (c_int, [c_p, c_int, c_int, c_p, c_p, c_i64, c_i64, c_p]),
     "mx_choco_apply_slots": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_int, c_p, c_i64, c_int, c_int,
                                      c_f32, c_f32, c_p]),

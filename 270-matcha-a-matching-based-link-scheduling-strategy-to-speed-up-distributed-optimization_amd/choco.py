@@ -12,7 +12,9 @@ message has no zero: a zero difference travels as +scale (torch.sign would give 
 With compressor="quant" it is the bucketed stochastic quantizer at bits = 4 or 8 (csrc/choco_quant.hip: QSGD's
 qsgd_s normalised per 256 columns): q_r = (one fp32 norm per bucket, one sign-and-level code per column), drawn
 from a counter-based hash of (seed, round, worker, column); mx_choco_quant_compress is one launch with no
-workspace, mx_choco_quant_apply the elementwise apply.
+workspace, mx_choco_quant_apply the elementwise apply.  With one_launch=True (nranks = 1, at most 16 rows) both,
+and the SGD step of attach_sgd(), are ONE launch that keeps the messages in LDS (csrc/choco_quant_round.hip:
+mx_choco_quant_round / mx_choco_quant_sgd_round), with the same bits in x, x_hat and s.
 Under PullTransport (N > 1, one process per GPU of a node) the messages are not sent: every rank
 publishes the messages its peers read this round into its IPC-shared snapshot buffer
 (mx_snapshot_publish_rows), the device
@@ -43,11 +45,16 @@ COMPRESSORS = ("topk", "sign", "quant")
 class ChocoWorkerGroup:
     def __init__(self, topology, models=None, numel=None, *, ratio=None, consensus_lr, rank=0, nranks=1,
                  comm=None, adopt=True, placement=None, pull_read="fetch", dtype=torch.float32,
-                 compressor="topk", bits=None, seed=0):
+                 compressor="topk", bits=None, seed=0, one_launch=False):
         """compressor: "topk" (compressors.get_top_k; `ratio` required), "sign" (the scaled-sign
         quantizer) or "quant" (the bucketed stochastic quantizer: `bits` 4 or 8, default 8; `seed` of its
         counter-based random numbers); the last two take no `ratio`, have k = 0 and nothing for check_topk()
         to check, and PullTransport is not built for them.
+        one_launch (compressor="quant", nranks = 1, at most 16 rows): a round, and with attach_sgd() the SGD
+        step in front of it, is ONE launch (csrc/choco_quant_round.hip) that keeps the messages on chip --
+        the same bits in x, x_hat and s as the two launches; there are no message slots, so message(),
+        compress() and average() raise, and `round_norms` ([n_local, ceil(P/256)] fp32) holds the last
+        round's bucket norms.
         placement: as VirtualWorkerGroup (None / "contiguous", "auto" or a worker order);
         `workers` lists the worker id of each local row.  pull_read (PullTransport only): "fetch"
         (default) copies the round's partner messages from their owners' snapshots into the receive
@@ -69,6 +76,13 @@ class ChocoWorkerGroup:
             raise ValueError(f"ChocoWorkerGroup: bits belongs to compressor='quant', not {compressor!r}")
         if compressor == "quant" and (8 if bits is None else bits) not in (4, 8):
             raise ValueError(f"ChocoWorkerGroup: compressor='quant' has bits 4 or 8, not {bits!r}")
+        if one_launch and compressor != "quant":
+            raise ValueError(f"ChocoWorkerGroup: one_launch belongs to compressor='quant', not {compressor!r} "
+                             "(a top-k threshold and a sign scale are row-wide)")
+        if one_launch and (nranks > 1 or comm is not None):
+            raise NotImplementedError("ChocoWorkerGroup: one_launch needs every worker's row on this GPU (nranks = 1, "
+                                      "no transport); use the two-launch path (one_launch=False)")
+        self.one_launch = bool(one_launch)
         self.compressor = compressor
         self.sign = compressor == "sign"
         self.quant = compressor == "quant"
@@ -85,6 +99,9 @@ class ChocoWorkerGroup:
         topology, self.placement = place(topology, nranks, placement)
         self.row_base, self.n_local = partition(n, nranks)[rank]
         self.workers = block_workers(self.placement, self.row_base, self.n_local)
+        if one_launch and self.n_local > 16:
+            raise NotImplementedError(f"ChocoWorkerGroup: one_launch holds a tile of at most 16 rows on chip, not "
+                                      f"{self.n_local}; use the two-launch path (one_launch=False)")
         if nranks > 1 and comm is None:
             comm = default_comm()
         self.engine = GossipEngine(topology, self.row_base, self.n_local, comm=comm,
@@ -139,7 +156,11 @@ class ChocoWorkerGroup:
             self.bnd_off = 4 * self.kpad + 8 * self.k
             self.work_ld = int(lib.mx_topk_work_bytes(P))
         self.msg_ld = (self.msg_bytes + 255) // 256 * 256
-        self.msgs = torch.empty(self.engine.n_slots * self.msg_ld, dtype=torch.uint8, device="cuda")
+        self.round_norms = None
+        if self.one_launch:                  # no message slots: the norms are all of a message that reaches memory
+            self.round_norms = torch.zeros((self.n_local, (P + 255) // 256), dtype=torch.float32, device="cuda")
+        self.msgs = torch.empty(0 if self.one_launch else self.engine.n_slots * self.msg_ld, dtype=torch.uint8,
+                                device="cuda")
         self.work = torch.zeros(self.n_local * self.work_ld, dtype=torch.uint8, device="cuda")  # zero on first use
         self.apply_work = torch.empty(0 if self.k == 0 else int(lib.mx_choco_apply_work_bytes(P, self.engine.n_slots)),
                                       dtype=torch.uint8, device="cuda")
@@ -191,6 +212,7 @@ class ChocoWorkerGroup:
         """(values float32[k], indices int64[k]) views of message `slot` (index-sorted); with
         compressor="sign": (scale, a 0-dim float32 view, bits uint8[ceil(P/8)], column c = bit c & 7 of
         byte c >> 3); with compressor="quant": (norms float32[ceil(P/256)], codes uint8[ceil(P bits / 8)])."""
+        self._needs_slots("message")
         base = slot * self.msg_ld
         if self.quant:
             return (self.msgs[base + 64:base + 64 + 4 * ((self.numel + 255) // 256)].view(torch.float32),
@@ -206,6 +228,7 @@ class ChocoWorkerGroup:
         """prepare_comm_buffer (communicator.py:175-196): every local row's top-k message of
         x - x_hat into its message slot (compressor="sign": its scaled-sign message; "quant": its quantized
         message of round `it`)."""
+        self._needs_slots("compress")
         if self.quant:
             return self._quant_compress(int(it), None, stream)
         if self.sign:
@@ -217,6 +240,30 @@ class ChocoWorkerGroup:
                                         self.numel, self.k, self.msgs.data_ptr(), self.msg_ld, 4 * self.kpad,
                                         self.bnd_off, self.work.data_ptr(), self.work_ld, stream_ptr(stream)),
               "mx_topk_abs_diff_rows")
+
+    def _needs_slots(self, what):
+        if self.one_launch:
+            raise MXError(f"ChocoWorkerGroup.{what}: a one_launch group has no message slots -- its messages never "
+                          "reach memory (round_norms holds the last round's norms)")
+
+    def _quant_round(self, it, iter_dev, stream, sgd=None):
+        """The one-launch round at plan record `it`, or at the device counter (`iter_dev`: its address); `sgd`:
+        (lr, lr_dev) of the SGD step in front of it."""
+        head = (self.x_hat.data_ptr(), self.s.data_ptr(), self.ld, self.n_local, self.numel, self.bits,
+                self.engine.plan.data_ptr())
+        at = (iter_dev, self.engine.T) if iter_dev else (int(it),)
+        tail = (self.engine.M, self.engine.alpha32, self.gamma32, self.seed, self.row_base,
+                self.round_norms.data_ptr(), self.round_norms.shape[1])
+        if sgd is None:
+            fn = "mx_choco_quant_round_at" if iter_dev else "mx_choco_quant_round"
+            check(getattr(lib, fn)(self.x.data_ptr(), *head, *at, *tail, stream_ptr(stream)), fn)
+            return
+        if self._sgd is None:
+            raise MXError("no SGD state: call attach_sgd() first")
+        m = self.mom_arena.data_ptr() if self.mom_arena is not None else None
+        fn = "mx_choco_quant_sgd_round_at" if iter_dev else "mx_choco_quant_sgd_round"
+        check(getattr(lib, fn)(self.x.data_ptr(), self.grad_arena.data_ptr(), m, *head, *at, *tail, float(sgd[0]),
+                               sgd[1], *self._sgd, stream_ptr(stream)), fn)
 
     def _quant_compress(self, it, iter_dev, stream=None):
         """mx_choco_quant_compress at round `it`, or at the device counter (`iter_dev`: its address)"""
@@ -268,6 +315,7 @@ class ChocoWorkerGroup:
         """averaging (communicator.py:200-230): receive partner messages ([N > 1] over the
         transport into the message slots after the local ones), then the s / x_hat scatters and
         the dense x update."""
+        self._needs_slots("average")
         it = self.engine.round_index(it)         # mx_choco_apply indexes the plan table by `it`
         if self._pull is not None:
             return self._average_pull(it, stream)
@@ -342,6 +390,10 @@ class ChocoWorkerGroup:
         communicator.py:249-250; the messages written meanwhile are scratch).  One GPU only."""
         if self.engine.comm is not None:
             raise RuntimeError("device_round: graph-replayable rounds need all partners on this GPU (nranks = 1)")
+        if self.one_launch:
+            self._quant_round(0, self.iter_dev.data_ptr(), stream)
+            check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, stream_ptr(stream)), "mx_iter_advance")
+            return
         self._compress_at(stream)
         self._apply_at(stream)
 
@@ -373,6 +425,9 @@ class ChocoWorkerGroup:
         """One round at iteration `it`; False (nothing done) for an all-zero flags row."""
         if not self.engine.any_active[it]:
             return False
+        if self.one_launch:
+            self._quant_round(self.engine.round_index(it), None, stream)
+            return True
         self.compress(it, stream)
         self.average(it, stream)
         return True
@@ -430,6 +485,7 @@ class ChocoWorkerGroup:
     def sgd_compress(self, lr, stream=None, it=0):
         """optimizer.step() + zero_grad() + prepare_comm_buffer of every local row: with compressor="sign"
         one fused launch (and the finish), with "topk" and "quant" the step launch, then compress(it)."""
+        self._needs_slots("sgd_compress")
         self._sgd_launch(self.sign, lr, None, None, stream)
         if not self.sign:
             self.compress(it, stream)
@@ -442,6 +498,9 @@ class ChocoWorkerGroup:
         if not self.engine.any_active[it]:
             self._sgd_launch(False, lr, None, None, stream)
             return False
+        if self.one_launch:                  # the step, the quantizer and the round: one launch
+            self._quant_round(self.engine.round_index(it), None, stream, sgd=(lr, None))
+            return True
         self.sgd_compress(lr, stream, it)
         self.average(it, stream)
         return True
@@ -455,6 +514,10 @@ class ChocoWorkerGroup:
             raise RuntimeError("sgd_device_round: graph-replayable rounds need all partners on this GPU (nranks = 1)")
         if self._sgd is None:
             raise MXError("no SGD state: call attach_sgd() first")
+        if self.one_launch:                  # a round of the schedule with no active matching: the step alone
+            self._quant_round(0, self.iter_dev.data_ptr(), stream, sgd=(0.0, self.lr_dev.data_ptr()))
+            check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, stream_ptr(stream)), "mx_iter_advance")
+            return
         self._sgd_launch(self.sign, 0.0, self.lr_dev.data_ptr(), self.iter_dev.data_ptr(), stream)
         if not self.sign:
             self._compress_at(stream)

@@ -209,7 +209,9 @@ class VirtualTrainer:
         are updated and mixed, the bfloat16 models are their rounded image, and checkpoints save
         the masters too.  With args.compress and compressor "sign" (ChocoSGD) the step runs inside the
         scaled-sign compress pass instead (ChocoWorkerGroup.attach_sgd / sgd_communicate,
-        csrc/choco_sgd.hip): fp32 models, no clip_grad_norm, param_groups or slowmo_every.  The trainer
+        csrc/choco_sgd.hip), and with compressor "quant" the group is built with one_launch=True: step,
+        quantizer and round are one launch (csrc/choco_quant_round.hip; at most 16 workers).  Both: fp32
+        models, no clip_grad_norm, param_groups or slowmo_every.  The trainer
         keeps refusing fused_sgd with the top-k compressor (a top-k group has the step through
         ChocoWorkerGroup.attach_sgd); the other fused_* options stay uncompressed.
 
@@ -277,11 +279,11 @@ class VirtualTrainer:
         np.random.seed(args.randomSeed)                          # train_mpi.py:62
         torch.manual_seed(args.randomSeed)
         self.fused_sgd = bool(fused_sgd)
-        if self.fused_sgd and (batched or (args.compress and getattr(args, "compressor", "topk") != "sign")):
+        if self.fused_sgd and (batched or (args.compress and getattr(args, "compressor", "topk") == "topk")):
             raise ValueError("fused_sgd needs per-worker (non-batched) training, uncompressed or with the scaled-sign "
-                             "compressor: the vmap path's gradients are fresh tensors every iteration, and the step is "
-                             "fused into the sign compress pass only (a top-k group takes it through "
-                             "ChocoWorkerGroup.attach_sgd, not through the trainer)")
+                             "or the quant compressor: the vmap path's gradients are fresh tensors every iteration, and "
+                             "the step is fused into the sign compress pass and the one-launch quant round only (a top-k "
+                             "group takes it through ChocoWorkerGroup.attach_sgd, not through the trainer)")
         self.fused_adamw = bool(fused_adamw)
         if self.fused_adamw and self.fused_sgd:
             raise ValueError("fused_adamw and fused_sgd are mutually exclusive: the group carries one optimizer")
@@ -344,6 +346,8 @@ class VirtualTrainer:
                                  "step are fp32-only")
             compressor = getattr(args, "compressor", "topk")
             extra = {"bits": getattr(args, "quant_bits", 8)} if compressor == "quant" else {}
+            if self.fused_sgd and compressor == "quant":         # step + quantizer + round: csrc/choco_quant_round.hip
+                extra["one_launch"] = True
             self.group = ChocoWorkerGroup(self.GP, self.models, consensus_lr=args.consensus_lr, compressor=compressor,
                                           ratio=args.ratio if compressor == "topk" else None,   # only top-k has a ratio
                                           **extra)
@@ -354,7 +358,8 @@ class VirtualTrainer:
                                             dtype=torch.bfloat16 if dts == {torch.bfloat16} else torch.float32)
         mixed = self.fused and self.group.dtype == torch.bfloat16
         if self.fused_sgd and args.compress:
-            # ChocoSGD, sign compressor: the step runs inside the compress pass (csrc/choco_sgd.hip); no clipping, no groups
+            # ChocoSGD: the step runs inside the sign compress pass (csrc/choco_sgd.hip) or the one-launch quant round
+            # (csrc/choco_quant_round.hip); no clipping, no groups
             if clip_grad_norm is not None or param_groups is not None or slowmo_every is not None:
                 raise ValueError("fused_sgd with compress takes no clip_grad_norm, param_groups or slowmo_every: "
                                  "ChocoWorkerGroup.attach_sgd has none of them")

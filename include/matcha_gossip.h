@@ -1288,9 +1288,41 @@ int mx_choco_quant_apply_at(float* x, float* xhat, float* s, int64_t ld, int64_t
                             int64_t msg_ld_bytes, int n_slots, const int32_t* plan_dev, const int64_t* iter_dev,
                             int64_t n_iters, int n_local, int M, float alpha, float gamma, void* stream);
 /* Knobs of the quantizer passes (communicator.py:175-230 has none; speed only, never results): "apply_nt",
- * "blocks_per_cu" and "grid" as mx_choco_sign_set's, with their own values. */
+ * "blocks_per_cu" and "grid" as mx_choco_sign_set's, with their own values; "round_blocks_per_cu" and
+ * "round_grid" are the one-launch round's persistent grid, in the same two senses. */
 int mx_choco_quant_set(const char* key, int value);
 int mx_choco_quant_get(const char* key);
+/* prepare_comm_buffer + averaging (communicator.py:175-230) of a whole group in ONE launch, when every worker's
+ * row lives on this GPU: mx_choco_quant_compress (x_hat given) followed by mx_choco_quant_apply, with the same
+ * bits in x, x_hat and s, and no message in memory -- a workgroup quantizes one column tile of all n_local rows
+ * into LDS and applies the round from there, in place.  1-16 rows (row r at + r*ld; ld >= P with several), all
+ * partners local: the plan has n_slots == n_local, and a record with receive slots or the peer-reads bit
+ * (mx_plan_set_peer_reads) makes the launch write nothing.  `iter` selects the plan record AND is the round of
+ * the random numbers; the caller skips rounds without an active matching, as for mx_choco_quant_apply.
+ * norms: NULL, or fp32 [n_local][norm_ld], norm_ld >= ceil(P/256): receives every bucket's norm of the round,
+ * the bits mx_choco_quant_compress would put into the slots. */
+int mx_choco_quant_round(float* x, float* xhat, float* s, int64_t ld, int n_local, int64_t P, int bits,
+                         const int32_t* plan_dev, int64_t iter, int M, float alpha, float gamma, int64_t seed,
+                         int row_base, float* norms, int64_t norm_ld, void* stream);
+/* Graph-replayable form (communicator.py:249-250 skips rounds without an active matching): the round is
+ * *iter_dev when the kernel runs; outside [0, n_iters), or with no active matching, nothing is touched. */
+int mx_choco_quant_round_at(float* x, float* xhat, float* s, int64_t ld, int n_local, int64_t P, int bits,
+                            const int32_t* plan_dev, const int64_t* iter_dev, int64_t n_iters, int M, float alpha,
+                            float gamma, int64_t seed, int row_base, float* norms, int64_t norm_ld, void* stream);
+/* optimizer.step() + zero_grad() (train_mpi.py:131-142), then that round, in the same launch: mx_choco_sgd_step's
+ * update of x from g and m (m NULL exactly when momentum == 0; lr_dev non-NULL: the learning rate, read when
+ * the kernel runs; zero_grads: +0 over g), the round on the updated x from the registers.  The _at form with a
+ * counter outside [0, n_iters) touches nothing, no step either; inside the schedule but with no active matching
+ * it is the step alone. */
+int mx_choco_quant_sgd_round(float* x, float* g, float* m, float* xhat, float* s, int64_t ld, int n_local, int64_t P,
+                             int bits, const int32_t* plan_dev, int64_t iter, int M, float alpha, float gamma,
+                             int64_t seed, int row_base, float* norms, int64_t norm_ld, float lr, const float* lr_dev,
+                             float weight_decay, float momentum, int nesterov, int zero_grads, void* stream);
+int mx_choco_quant_sgd_round_at(float* x, float* g, float* m, float* xhat, float* s, int64_t ld, int n_local,
+                                int64_t P, int bits, const int32_t* plan_dev, const int64_t* iter_dev,
+                                int64_t n_iters, int M, float alpha, float gamma, int64_t seed, int row_base,
+                                float* norms, int64_t norm_ld, float lr, const float* lr_dev, float weight_decay,
+                                float momentum, int nesterov, int zero_grads, void* stream);
 
 /* ---------------------------------------------------------------- cross-GPU exchange (RCCL)
  * One process per GPU; workers partitioned by owner[].  mx_exchange_round posts, inside one
