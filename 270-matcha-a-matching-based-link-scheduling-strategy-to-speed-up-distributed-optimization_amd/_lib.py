@@ -100,6 +100,17 @@ SIGNATURES = {
     "mx_choco_quant_sgd_round_at": (c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_i64, c_int, c_p, c_p, c_i64,
                                             c_int, c_f32, c_f32, c_i64, c_int, c_p, c_i64, c_f32, c_p, c_f32, c_f32,
                                             c_int, c_int, c_p]),
+    # the mixed-precision forms: the fp32 lists with p (the bf16 model rows) after s
+    "mx_choco_quant_round_bf16": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_int, c_i64, c_int, c_p, c_i64, c_int, c_f32,
+                                          c_f32, c_i64, c_int, c_p, c_i64, c_p]),
+    "mx_choco_quant_round_bf16_at": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_int, c_i64, c_int, c_p, c_p, c_i64, c_int,
+                                             c_f32, c_f32, c_i64, c_int, c_p, c_i64, c_p]),
+    "mx_choco_quant_sgd_round_bf16": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_i64, c_int, c_p, c_i64,
+                                              c_int, c_f32, c_f32, c_i64, c_int, c_p, c_i64, c_f32, c_p, c_f32, c_f32,
+                                              c_int, c_int, c_p]),
+    "mx_choco_quant_sgd_round_bf16_at": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_i64, c_int, c_p, c_p,
+                                                 c_i64, c_int, c_f32, c_f32, c_i64, c_int, c_p, c_i64, c_f32, c_p,
+                                                 c_f32, c_f32, c_int, c_int, c_p]),
     "mx_pull_fetch": (c_int, [c_p, c_int, c_int, c_p, c_p, c_i64, c_i64, c_p]),
     "mx_choco_apply_slots": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_int, c_p, c_i64, c_int, c_int,
                                      c_f32, c_f32, c_p]),

@@ -14,7 +14,9 @@ qsgd_s normalised per 256 columns): q_r = (one fp32 norm per bucket, one sign-an
 from a counter-based hash of (seed, round, worker, column); mx_choco_quant_compress is one launch with no
 workspace, mx_choco_quant_apply the elementwise apply.  With one_launch=True (nranks = 1, at most 16 rows) both,
 and the SGD step of attach_sgd(), are ONE launch that keeps the messages in LDS (csrc/choco_quant_round.hip:
-mx_choco_quant_round / mx_choco_quant_sgd_round), with the same bits in x, x_hat and s.
+mx_choco_quant_round / mx_choco_quant_sgd_round), with the same bits in x, x_hat and s.  That form alone also
+serves models held in bfloat16 (dtype=torch.bfloat16, csrc/choco_quant_round_bf16.hip): x, x_hat, s and the
+momentum stay fp32, the gradients come in as bfloat16 and the same launch rewrites the models as bf16_rne(x).
 Under PullTransport (N > 1, one process per GPU of a node) the messages are not sent: every rank
 publishes the messages its peers read this round into its IPC-shared snapshot buffer
 (mx_snapshot_publish_rows), the device
@@ -55,6 +57,11 @@ class ChocoWorkerGroup:
         the same bits in x, x_hat and s as the two launches; there are no message slots, so message(),
         compress() and average() raise, and `round_norms` ([n_local, ceil(P/256)] fp32) holds the last
         round's bucket norms.
+        dtype=torch.bfloat16 (that one_launch form only; everything else raises NotImplementedError): the
+        models are bfloat16 and adopt a bfloat16 arena, `rows` is its [:, :numel] view, every launch rewrites it as
+        the rounded image of `x`; `x` (fp32, `master_rows` is its [:, :numel] view -- None on an fp32 group) starts
+        as the models' exact widening and is what the round updates; attach_sgd's gradient arena is bfloat16, its
+        momentum fp32; master_from_rows() re-widens after the models were written from outside.
         placement: as VirtualWorkerGroup (None / "contiguous", "auto" or a worker order);
         `workers` lists the worker id of each local row.  pull_read (PullTransport only): "fetch"
         (default) copies the round's partner messages from their owners' snapshots into the receive
@@ -79,6 +86,11 @@ class ChocoWorkerGroup:
         if one_launch and compressor != "quant":
             raise ValueError(f"ChocoWorkerGroup: one_launch belongs to compressor='quant', not {compressor!r} "
                              "(a top-k threshold and a sign scale are row-wide)")
+        if dtype != torch.float32 and (dtype != torch.bfloat16 or compressor != "quant" or not one_launch or
+                                       nranks > 1 or comm is not None):
+            raise NotImplementedError(f"ChocoWorkerGroup: {dtype} rows -- the top-k, sign and two-launch quant kernels "
+                                      "and every transport are fp32-only; bfloat16 models take compressor='quant', "
+                                      "one_launch=True with nranks = 1 (csrc/choco_quant_round_bf16.hip)")
         if one_launch and (nranks > 1 or comm is not None):
             raise NotImplementedError("ChocoWorkerGroup: one_launch needs every worker's row on this GPU (nranks = 1, "
                                       "no transport); use the two-launch path (one_launch=False)")
@@ -88,9 +100,6 @@ class ChocoWorkerGroup:
         self.quant = compressor == "quant"
         self.bits = (8 if bits is None else int(bits)) if self.quant else None
         self.seed = int(seed)
-        if dtype != torch.float32:
-            # only VirtualWorkerGroup's mixing round has a bfloat16 form (csrc/mix_bf16.hip)
-            raise NotImplementedError(f"ChocoWorkerGroup: {dtype} rows -- the top-k and apply kernels are fp32-only")
         self.pull_read = pull_read
         self.dtype = dtype
         require_device()
@@ -120,24 +129,28 @@ class ChocoWorkerGroup:
         self._adopted = list(models) if models is not None and adopt else None
         self._copied_models = models is not None and not adopt
         self._sgd = None                     # attach_sgd's hyperparameters
+        self._iters = None                   # bfloat16 sgd_step on an inactive round: 0 .. T on the device
         self.grad_arena = self.grads = self.mom_arena = self.momentum_rows = self.lr_dev = None
         P = self.numel
         self.ld = (P + ROW_ALIGN - 1) // ROW_ALIGN * ROW_ALIGN
         self.x = torch.zeros((self.n_local, self.ld), dtype=torch.float32, device="cuda")
         self.x_hat = torch.zeros_like(self.x)     # communicator.py:179-182 (lazy zeros)
         self.s = torch.zeros_like(self.x)
+        # bfloat16 models: their arena, the image of x that every launch rewrites; x is the fp32 master
+        self.arena = self.x if dtype == torch.float32 else torch.zeros_like(self.x, dtype=dtype)
         if models is not None:
             for r, m in enumerate(models):
                 off = 0
                 for p in m.parameters():
-                    if p.dtype != torch.float32 or p.device.type != "cuda":
-                        raise TypeError("worker parameters must be float32 CUDA tensors")
+                    if p.dtype != dtype or p.device.type != "cuda":
+                        raise TypeError(f"worker parameters must be {dtype} CUDA tensors")
                     k = p.numel()
-                    view = self.x[r, off:off + k].view(p.shape)
+                    view = self.arena[r, off:off + k].view(p.shape)
                     view.copy_(p.data)
                     if adopt:
                         p.data = view
                     off += k
+            self.master_from_rows()
         if self.quant:
             # header 64 | norm f32[ceil(P/256)] padded to 64 | codes uint8[32 bits ceil(P/256)]; no workspace
             self.k = self.kpad = self.work_ld = 0
@@ -187,7 +200,18 @@ class ChocoWorkerGroup:
 
     @property
     def rows(self):
-        return self.x[:, :self.numel]
+        """The models' rows: `x` itself, or on a bfloat16 group its bfloat16 image."""
+        return self.arena[:, :self.numel]
+
+    @property
+    def master_rows(self):
+        """The fp32 rows the round updates under bfloat16 models (`x`); None on an fp32 group."""
+        return self.x[:, :self.numel] if self.dtype == torch.bfloat16 else None
+
+    def master_from_rows(self):
+        """x = f32(rows), the exact widening: after the models were written from outside.  Nothing on an fp32 group."""
+        if self.arena is not self.x:
+            self.x.copy_(self.arena)
 
     def consensus_distance(self, stream=None):
         """VirtualWorkerGroup.consensus_distance over the `x` arena: every worker's distance from the mean
@@ -246,22 +270,23 @@ class ChocoWorkerGroup:
             raise MXError(f"ChocoWorkerGroup.{what}: a one_launch group has no message slots -- its messages never "
                           "reach memory (round_norms holds the last round's norms)")
 
-    def _quant_round(self, it, iter_dev, stream, sgd=None):
-        """The one-launch round at plan record `it`, or at the device counter (`iter_dev`: its address); `sgd`:
-        (lr, lr_dev) of the SGD step in front of it."""
-        head = (self.x_hat.data_ptr(), self.s.data_ptr(), self.ld, self.n_local, self.numel, self.bits,
-                self.engine.plan.data_ptr())
-        at = (iter_dev, self.engine.T) if iter_dev else (int(it),)
+    def _quant_round(self, it, iter_dev, stream, sgd=None, n_iters=None):
+        """The one-launch round at plan record `it`, or at the device counter (`iter_dev`: its address, valid below
+        `n_iters`, by default the schedule's length); `sgd`: (lr, lr_dev) of the SGD step in front of it."""
+        bf = self.dtype == torch.bfloat16        # the models' image p after s, and _bf16 in the entry point's name
+        head = (self.x_hat.data_ptr(), self.s.data_ptr(), *((self.arena.data_ptr(),) if bf else ()), self.ld,
+                self.n_local, self.numel, self.bits, self.engine.plan.data_ptr())
+        at = (iter_dev, self.engine.T if n_iters is None else n_iters) if iter_dev else (int(it),)
         tail = (self.engine.M, self.engine.alpha32, self.gamma32, self.seed, self.row_base,
                 self.round_norms.data_ptr(), self.round_norms.shape[1])
         if sgd is None:
-            fn = "mx_choco_quant_round_at" if iter_dev else "mx_choco_quant_round"
+            fn = "mx_choco_quant_round" + ("_bf16" if bf else "") + ("_at" if iter_dev else "")
             check(getattr(lib, fn)(self.x.data_ptr(), *head, *at, *tail, stream_ptr(stream)), fn)
             return
         if self._sgd is None:
             raise MXError("no SGD state: call attach_sgd() first")
         m = self.mom_arena.data_ptr() if self.mom_arena is not None else None
-        fn = "mx_choco_quant_sgd_round_at" if iter_dev else "mx_choco_quant_sgd_round"
+        fn = "mx_choco_quant_sgd_round" + ("_bf16" if bf else "") + ("_at" if iter_dev else "")
         check(getattr(lib, fn)(self.x.data_ptr(), self.grad_arena.data_ptr(), m, *head, *at, *tail, float(sgd[0]),
                                sgd[1], *self._sgd, stream_ptr(stream)), fn)
 
@@ -438,7 +463,7 @@ class ChocoWorkerGroup:
         zero_grad() (train_mpi.py:131-142) runs on the way into the compressor (csrc/choco_sgd.hip): with
         compressor="sign" inside the compress pass itself, with "topk" as one launch before the selection.
 
-        Allocates `grad_arena` ([n_local, ld] fp32 zeros; `grads` is its [:, :numel] view) and, with
+        Allocates `grad_arena` ([n_local, ld] zeros of the models' dtype; `grads` is its [:, :numel] view) and, with
         momentum, `mom_arena` / `momentum_rows`, and `lr_dev` (the device rounds' learning rate).  For
         adopted models every parameter's .grad becomes the matching view of the gradient arena (see
         VirtualWorkerGroup.attach_sgd on zero_grad(set_to_none=True), which would detach them); a group
@@ -450,7 +475,7 @@ class ChocoWorkerGroup:
         if self._copied_models:
             raise ValueError("ChocoWorkerGroup.attach_sgd: the models were copied (adopt=False); their gradients "
                              "would never reach the group's gradient arena")
-        self.grad_arena = torch.zeros_like(self.x)
+        self.grad_arena = torch.zeros_like(self.arena)
         self.grads = self.grad_arena[:, :self.numel]
         self.mom_arena = self.momentum_rows = None
         if momentum != 0.0:
@@ -496,7 +521,15 @@ class ChocoWorkerGroup:
         average().  A round with no active matching is the step launch alone (False is returned): the
         reference communicates nothing there (communicator.py:249-250) but its optimizers still step."""
         if not self.engine.any_active[it]:
-            self._sgd_launch(False, lr, None, None, stream)
+            if self.dtype == torch.bfloat16:
+                # the step has to rewrite the image: the same launch in its _at form, whose counter is entry `it` of
+                # a constant table -- it finds the record inactive and is the step alone (a host `iter` would not look)
+                if self._iters is None:
+                    self._iters = torch.arange(self.engine.T + 1, dtype=torch.int64, device="cuda")
+                self._quant_round(0, self._iters.data_ptr() + 8 * self.engine.round_index(it), stream, sgd=(lr, None),
+                                  n_iters=self.engine.T + 1)
+            else:
+                self._sgd_launch(False, lr, None, None, stream)
             return False
         if self.one_launch:                  # the step, the quantizer and the round: one launch
             self._quant_round(self.engine.round_index(it), None, stream, sgd=(lr, None))
@@ -537,8 +570,8 @@ class ChocoWorkerGroup:
         return toc - tic
 
     def state_dict(self):
-        """Checkpoint: rows, the persistent Choco state x_hat / s (communicator.py:179-182) and
-        the iteration counter."""
+        """Checkpoint: rows (the fp32 `x`: under bfloat16 models the masters, with a "dtype" tag), the persistent
+        Choco state x_hat / s (communicator.py:179-182) and the iteration counter."""
         P = self.numel
         state = {"kind": "choco", "iter": int(self.iter), "row_base": int(self.row_base), "k": int(self.k),
                  "workers": list(self.workers),
@@ -548,6 +581,8 @@ class ChocoWorkerGroup:
             state["compressor"] = "sign"
         if self.quant:
             state.update(compressor="quant", bits=self.bits, seed=self.seed)
+        if self.dtype == torch.bfloat16:     # `rows` are the fp32 masters either way: an fp32 group loads them
+            state["dtype"] = "bfloat16"
         if self.momentum_rows is not None:   # attach_sgd with momentum; without it, key for key what it was
             state["momentum_rows"] = self.momentum_rows.detach().clone()
         return state
@@ -569,6 +604,8 @@ class ChocoWorkerGroup:
             self.x[:, :P].copy_(state["rows"])
             self.x_hat[:, :P].copy_(state["x_hat"])
             self.s[:, :P].copy_(state["s"])
+            if self.arena is not self.x:     # the image of the loaded masters
+                self.arena[:, :P].copy_(self.x[:, :P].to(self.dtype))
         self.iter = int(state["iter"])
         if self.quant:
             self.seed = int(state["seed"])       # the resumed run draws the saved run's random numbers

@@ -210,8 +210,9 @@ class VirtualTrainer:
         the masters too.  With args.compress and compressor "sign" (ChocoSGD) the step runs inside the
         scaled-sign compress pass instead (ChocoWorkerGroup.attach_sgd / sgd_communicate,
         csrc/choco_sgd.hip), and with compressor "quant" the group is built with one_launch=True: step,
-        quantizer and round are one launch (csrc/choco_quant_round.hip; at most 16 workers).  Both: fp32
-        models, no clip_grad_norm, param_groups or slowmo_every.  The trainer
+        quantizer and round are one launch (csrc/choco_quant_round.hip; at most 16 workers; all-bfloat16
+        models in mixed precision, csrc/choco_quant_round_bf16.hip: fp32 x, x_hat, s and momentum).  Both: fp32
+        models otherwise, no clip_grad_norm, param_groups or slowmo_every.  The trainer
         keeps refusing fused_sgd with the top-k compressor (a top-k group has the step through
         ChocoWorkerGroup.attach_sgd); the other fused_* options stay uncompressed.
 
@@ -341,13 +342,20 @@ class VirtualTrainer:
             torch.manual_seed(args.randomSeed + r)                # train_mpi.py:61, per rank
             self.models.append(model_fn().to(device))
         if args.compress:
-            if self.fused_sgd and any(p.dtype != torch.float32 for p in self.models[0].parameters()):
-                raise ValueError("fused_sgd with compress needs float32 models: ChocoWorkerGroup's rows and its SGD "
-                                 "step are fp32-only")
             compressor = getattr(args, "compressor", "topk")
+            dts = {p.dtype for m in self.models for p in m.parameters()}
+            # all-bfloat16 models: only the one-launch quant round has the mixed-precision form
+            # (csrc/choco_quant_round_bf16.hip: fp32 x, x_hat, s and momentum, the models their rounded image)
+            bf16 = self.fused_sgd and compressor == "quant" and dts == {torch.bfloat16}
+            if self.fused_sgd and dts != {torch.float32} and not bf16:
+                raise ValueError("fused_sgd with compress needs float32 models: ChocoWorkerGroup's rows and its SGD "
+                                 "step are fp32-only, but for the quant compressor, which also takes all-bfloat16 "
+                                 "models")
             extra = {"bits": getattr(args, "quant_bits", 8)} if compressor == "quant" else {}
             if self.fused_sgd and compressor == "quant":         # step + quantizer + round: csrc/choco_quant_round.hip
                 extra["one_launch"] = True
+            if bf16:
+                extra["dtype"] = torch.bfloat16
             self.group = ChocoWorkerGroup(self.GP, self.models, consensus_lr=args.consensus_lr, compressor=compressor,
                                           ratio=args.ratio if compressor == "topk" else None,   # only top-k has a ratio
                                           **extra)

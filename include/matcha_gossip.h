@@ -1323,6 +1323,32 @@ int mx_choco_quant_sgd_round_at(float* x, float* g, float* m, float* xhat, float
                                 int64_t n_iters, int M, float alpha, float gamma, int64_t seed, int row_base,
                                 float* norms, int64_t norm_ld, float lr, const float* lr_dev, float weight_decay,
                                 float momentum, int nesterov, int zero_grads, void* stream);
+/* The same four launches for models held in bfloat16 (csrc/choco_quant_round_bf16.hip; train_mpi.py:131-142 and
+ * communicator.py:175-230 on fp32 master rows): x, x_hat, s and m stay fp32, g points to bfloat16 gradients (read
+ * as f32(g) = bits << 16, overwritten with bfloat16 zeros when zero_grads) and p to the bfloat16 model rows, WRITE
+ * ONLY: p = bf16_rne(x), one rounding to nearest even of the value stored to x, for every column below P of every
+ * row in which the launch writes x -- with the step that is every launch that runs, a round with no active
+ * matching included.  Every array has the leading dimension ld, in elements.  x, x_hat, s, m and the norms are the
+ * bits the fp32 entry points give for gradients equal to the widened ones.  The refusals and no-op rules are the
+ * fp32 entry points', plus p NULL. */
+int mx_choco_quant_round_bf16(float* x, float* xhat, float* s, uint16_t* p, int64_t ld, int n_local, int64_t P,
+                              int bits, const int32_t* plan_dev, int64_t iter, int M, float alpha, float gamma,
+                              int64_t seed, int row_base, float* norms, int64_t norm_ld, void* stream);
+int mx_choco_quant_round_bf16_at(float* x, float* xhat, float* s, uint16_t* p, int64_t ld, int n_local, int64_t P,
+                                 int bits, const int32_t* plan_dev, const int64_t* iter_dev, int64_t n_iters, int M,
+                                 float alpha, float gamma, int64_t seed, int row_base, float* norms, int64_t norm_ld,
+                                 void* stream);
+int mx_choco_quant_sgd_round_bf16(float* x, uint16_t* g, float* m, float* xhat, float* s, uint16_t* p, int64_t ld,
+                                  int n_local, int64_t P, int bits, const int32_t* plan_dev, int64_t iter, int M,
+                                  float alpha, float gamma, int64_t seed, int row_base, float* norms, int64_t norm_ld,
+                                  float lr, const float* lr_dev, float weight_decay, float momentum, int nesterov,
+                                  int zero_grads, void* stream);
+int mx_choco_quant_sgd_round_bf16_at(float* x, uint16_t* g, float* m, float* xhat, float* s, uint16_t* p, int64_t ld,
+                                     int n_local, int64_t P, int bits, const int32_t* plan_dev,
+                                     const int64_t* iter_dev, int64_t n_iters, int M, float alpha, float gamma,
+                                     int64_t seed, int row_base, float* norms, int64_t norm_ld, float lr,
+                                     const float* lr_dev, float weight_decay, float momentum, int nesterov,
+                                     int zero_grads, void* stream);
 
 /* ---------------------------------------------------------------- cross-GPU exchange (RCCL)
  * One process per GPU; workers partitioned by owner[].  mx_exchange_round posts, inside one

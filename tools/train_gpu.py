@@ -6,6 +6,7 @@
     python tools/train_gpu.py --momentum 0.9 --fused-sgd --bf16                 # the same, bf16 models + fp32 masters
     python tools/train_gpu.py --compress --compressor sign --fused-sgd --momentum 0.9
                                                                                 # ChocoSGD, SGD step fused into the compress pass
+    python tools/train_gpu.py --compress --compressor quant --fused-sgd --bf16  # one-launch quantized round, bf16 models
     python tools/train_gpu.py --lr 1e-3 --no-warmup --fused-adamw --wd 1e-2       # AdamW step fused into the round
     python tools/train_gpu.py --lr 1e-3 --no-warmup --fused-adamw --wd 1e-2 --bf16 # the same, bf16 models + fp32 masters
     python tools/train_gpu.py --lr 1e-4 --no-warmup --fused-lion --wd 1e-2 --bf16 --lion-bf16-momentum
@@ -81,7 +82,8 @@ def main():
     ap.add_argument("--wd", default=5e-4, type=float, help="--fused-adamw / --fused-lion: the decoupled weight decay")
     ap.add_argument("--bf16", action="store_true", help="one GPU: the models are cast to bfloat16 (bfloat16 gossip "
                     "rows); with --fused-sgd / --fused-adamw the step runs in mixed precision on fp32 master weights, which the "
-                    "round mixes, and the bfloat16 models are their rounded image")
+                    "round mixes, and the bfloat16 models are their rounded image; with --compress only as --compressor quant "
+                    "--fused-sgd (the one-launch round on fp32 x, x_hat and s)")
     ap.add_argument("--pull", action="store_true", help="one process per GPU: gossip rounds over the pull "
                     "transport (partner rows / Choco messages read from the peers' HBM) instead of RCCL")
     ap.add_argument("--clip-grad-norm", default=None, type=float, metavar="X", help="--fused-sgd / --fused-adamw: "
@@ -154,6 +156,9 @@ def main():
     if a.bf16:
         if world > 1:
             ap.error("--bf16: bfloat16 worker rows are mixed on one GPU only")
+        if a.compress and not (a.compressor == "quant" and a.fused_sgd):
+            ap.error("--bf16 --compress: ChocoSGD has bfloat16 models in its one-launch quantized round only: "
+                     "--compressor quant --fused-sgd")
         fp32_fn = model_fn
 
         def model_fn():
