@@ -111,6 +111,20 @@ SIGNATURES = {
     "mx_choco_quant_sgd_round_bf16_at": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_i64, c_int, c_p, c_p,
                                                  c_i64, c_int, c_f32, c_f32, c_i64, c_int, c_p, c_i64, c_f32, c_p,
                                                  c_f32, c_f32, c_int, c_int, c_p]),
+    # the AdamW forms: m, v for m; lr, lr_dev, omb1, beta2, omb2, eps, weight_decay, decoupled, zero_grads, then
+    # bias_dev, n_bias, step, step_dev
+    "mx_choco_quant_adamw_round": (c_int, [c_p] * 6 + [c_i64, c_int, c_i64, c_int, c_p, c_i64, c_int, c_f32, c_f32,
+                                                       c_i64, c_int, c_p, c_i64, c_f32, c_p] + [c_f32] * 5 +
+                                   [c_int, c_int, c_p, c_i64, c_i64, c_p, c_p]),
+    "mx_choco_quant_adamw_round_at": (c_int, [c_p] * 6 + [c_i64, c_int, c_i64, c_int, c_p, c_p, c_i64, c_int, c_f32,
+                                                          c_f32, c_i64, c_int, c_p, c_i64, c_f32, c_p] + [c_f32] * 5 +
+                                      [c_int, c_int, c_p, c_i64, c_i64, c_p, c_p]),
+    "mx_choco_quant_adamw_round_bf16": (c_int, [c_p] * 7 + [c_i64, c_int, c_i64, c_int, c_p, c_i64, c_int, c_f32,
+                                                            c_f32, c_i64, c_int, c_p, c_i64, c_f32, c_p] +
+                                        [c_f32] * 5 + [c_int, c_int, c_p, c_i64, c_i64, c_p, c_p]),
+    "mx_choco_quant_adamw_round_bf16_at": (c_int, [c_p] * 7 + [c_i64, c_int, c_i64, c_int, c_p, c_p, c_i64, c_int,
+                                                               c_f32, c_f32, c_i64, c_int, c_p, c_i64, c_f32, c_p] +
+                                           [c_f32] * 5 + [c_int, c_int, c_p, c_i64, c_i64, c_p, c_p]),
     "mx_pull_fetch": (c_int, [c_p, c_int, c_int, c_p, c_p, c_i64, c_i64, c_p]),
     "mx_choco_apply_slots": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_int, c_p, c_i64, c_int, c_int,
                                      c_f32, c_f32, c_p]),

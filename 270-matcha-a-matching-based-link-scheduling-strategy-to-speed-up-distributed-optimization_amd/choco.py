@@ -17,6 +17,8 @@ and the SGD step of attach_sgd(), are ONE launch that keeps the messages in LDS 
 mx_choco_quant_round / mx_choco_quant_sgd_round), with the same bits in x, x_hat and s.  That form alone also
 serves models held in bfloat16 (dtype=torch.bfloat16, csrc/choco_quant_round_bf16.hip): x, x_hat, s and the
 momentum stay fp32, the gradients come in as bfloat16 and the same launch rewrites the models as bf16_rne(x).
+attach_adamw() puts torch.optim.AdamW's (or Adam's) step in front of that one launch instead of SGD's
+(csrc/choco_quant_adamw_round.hip, csrc/choco_quant_adamw_round_bf16.hip: exp_avg and exp_avg_sq fp32).
 Under PullTransport (N > 1, one process per GPU of a node) the messages are not sent: every rank
 publishes the messages its peers read this round into its IPC-shared snapshot buffer
 (mx_snapshot_publish_rows), the device
@@ -129,8 +131,11 @@ class ChocoWorkerGroup:
         self._adopted = list(models) if models is not None and adopt else None
         self._copied_models = models is not None and not adopt
         self._sgd = None                     # attach_sgd's hyperparameters
-        self._iters = None                   # bfloat16 sgd_step on an inactive round: 0 .. T on the device
+        self._adamw = None                   # attach_adamw's, in the entry points' order
+        self._iters = None                   # a one-launch step on an inactive round: 0 .. T on the device
         self.grad_arena = self.grads = self.mom_arena = self.momentum_rows = self.lr_dev = None
+        self.exp_avg_arena = self.exp_avg_sq_arena = self.exp_avg_rows = self.exp_avg_sq_rows = None
+        self.opt_step = self.opt_step_dev = None
         P = self.numel
         self.ld = (P + ROW_ALIGN - 1) // ROW_ALIGN * ROW_ALIGN
         self.x = torch.zeros((self.n_local, self.ld), dtype=torch.float32, device="cuda")
@@ -270,15 +275,25 @@ class ChocoWorkerGroup:
             raise MXError(f"ChocoWorkerGroup.{what}: a one_launch group has no message slots -- its messages never "
                           "reach memory (round_norms holds the last round's norms)")
 
-    def _quant_round(self, it, iter_dev, stream, sgd=None, n_iters=None):
+    def _quant_round(self, it, iter_dev, stream, sgd=None, n_iters=None, adamw=None):
         """The one-launch round at plan record `it`, or at the device counter (`iter_dev`: its address, valid below
-        `n_iters`, by default the schedule's length); `sgd`: (lr, lr_dev) of the SGD step in front of it."""
+        `n_iters`, by default the schedule's length); `sgd`: (lr, lr_dev) of the SGD step in front of it; `adamw`:
+        (lr, lr_dev, step, step_dev) of the AdamW step in front of it."""
         bf = self.dtype == torch.bfloat16        # the models' image p after s, and _bf16 in the entry point's name
         head = (self.x_hat.data_ptr(), self.s.data_ptr(), *((self.arena.data_ptr(),) if bf else ()), self.ld,
                 self.n_local, self.numel, self.bits, self.engine.plan.data_ptr())
         at = (iter_dev, self.engine.T if n_iters is None else n_iters) if iter_dev else (int(it),)
         tail = (self.engine.M, self.engine.alpha32, self.gamma32, self.seed, self.row_base,
                 self.round_norms.data_ptr(), self.round_norms.shape[1])
+        if adamw is not None:
+            if self._adamw is None:
+                raise MXError("no AdamW state: call attach_adamw() first")
+            fn = "mx_choco_quant_adamw_round" + ("_bf16" if bf else "") + ("_at" if iter_dev else "")
+            check(getattr(lib, fn)(self.x.data_ptr(), self.grad_arena.data_ptr(), self.exp_avg_arena.data_ptr(),
+                                   self.exp_avg_sq_arena.data_ptr(), *head, *at, *tail, float(adamw[0]), adamw[1],
+                                   *self._adamw, self._bias_dev.data_ptr(), self._bias_dev.shape[0], int(adamw[2]),
+                                   adamw[3], stream_ptr(stream)), fn)
+            return
         if sgd is None:
             fn = "mx_choco_quant_round" + ("_bf16" if bf else "") + ("_at" if iter_dev else "")
             check(getattr(lib, fn)(self.x.data_ptr(), *head, *at, *tail, stream_ptr(stream)), fn)
@@ -472,15 +487,26 @@ class ChocoWorkerGroup:
         momentum, weight_decay = float(momentum), float(weight_decay)
         if nesterov and momentum == 0.0:
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        if self._copied_models:
-            raise ValueError("ChocoWorkerGroup.attach_sgd: the models were copied (adopt=False); their gradients "
-                             "would never reach the group's gradient arena")
-        self.grad_arena = torch.zeros_like(self.arena)
-        self.grads = self.grad_arena[:, :self.numel]
+        if self._adamw is not None:
+            raise ValueError("ChocoWorkerGroup.attach_sgd: the group carries one optimizer, and attach_adamw() gave "
+                             "it AdamW")
+        self._attach_grads("attach_sgd")
         self.mom_arena = self.momentum_rows = None
         if momentum != 0.0:
             self.mom_arena = torch.zeros_like(self.x)
             self.momentum_rows = self.mom_arena[:, :self.numel]
+        self.sgd_hyper = {"momentum": momentum, "weight_decay": weight_decay, "nesterov": bool(nesterov),
+                          "zero_grads": bool(zero_grads)}
+        self._sgd = (weight_decay, momentum, int(bool(nesterov)), int(bool(zero_grads)))
+
+    def _attach_grads(self, who):
+        """The gradient arena of a fused step (zeros of the models' dtype; adopted parameters' .grad become its
+        views) and `lr_dev`, the device rounds' learning rate."""
+        if self._copied_models:
+            raise ValueError(f"ChocoWorkerGroup.{who}: the models were copied (adopt=False); their gradients "
+                             "would never reach the group's gradient arena")
+        self.grad_arena = torch.zeros_like(self.arena)
+        self.grads = self.grad_arena[:, :self.numel]
         for r, m in enumerate(self._adopted or ()):
             off = 0
             for p in m.parameters():
@@ -488,9 +514,6 @@ class ChocoWorkerGroup:
                 p.grad = self.grad_arena[r, off:off + k].view(p.shape)
                 off += k
         self.lr_dev = torch.zeros(1, dtype=torch.float32, device="cuda")
-        self.sgd_hyper = {"momentum": momentum, "weight_decay": weight_decay, "nesterov": bool(nesterov),
-                          "zero_grads": bool(zero_grads)}
-        self._sgd = (weight_decay, momentum, int(bool(nesterov)), int(bool(zero_grads)))
 
     def _sgd_launch(self, compress, lr, lr_dev, iter_dev, stream):
         """The step of every local row: fused into the sign compress pass (`compress`), or alone."""
@@ -524,10 +547,7 @@ class ChocoWorkerGroup:
             if self.dtype == torch.bfloat16:
                 # the step has to rewrite the image: the same launch in its _at form, whose counter is entry `it` of
                 # a constant table -- it finds the record inactive and is the step alone (a host `iter` would not look)
-                if self._iters is None:
-                    self._iters = torch.arange(self.engine.T + 1, dtype=torch.int64, device="cuda")
-                self._quant_round(0, self._iters.data_ptr() + 8 * self.engine.round_index(it), stream, sgd=(lr, None),
-                                  n_iters=self.engine.T + 1)
+                self._quant_round(0, self._iter_entry(it), stream, sgd=(lr, None), n_iters=self.engine.T + 1)
             else:
                 self._sgd_launch(False, lr, None, None, stream)
             return False
@@ -569,9 +589,94 @@ class ChocoWorkerGroup:
         self.check_topk()
         return toc - tic
 
+    def _iter_entry(self, it):
+        """The address of entry round_index(it) of a constant device table 0 .. T: a counter for the _at launches
+        (valid below T + 1), through which a host-side step reaches the record of a round with no active matching"""
+        if self._iters is None:
+            self._iters = torch.arange(self.engine.T + 1, dtype=torch.int64, device="cuda")
+        return self._iters.data_ptr() + 8 * self.engine.round_index(it)
+
+    # ------------------------------------------------------------------ AdamW step fused into the one-launch round
+    def attach_adamw(self, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled=True, zero_grads=True):
+        """Give the group torch.optim.AdamW's state (decoupled=False: torch.optim.Adam's, the decay as an L2 term
+        in the gradient; no amsgrad, no maximize) so that every worker's optimizer.step() + zero_grad()
+        (train_mpi.py:131-142), the quantizer and the round are ONE launch (csrc/choco_quant_adamw_round.hip; bfloat16
+        models: csrc/choco_quant_adamw_round_bf16.hip).  compressor="quant", one_launch=True groups only, and not
+        together with attach_sgd.
+
+        Allocates `grad_arena` / `grads` as attach_sgd does (the models' dtype; adopted parameters' .grad become
+        views), `exp_avg_arena` / `exp_avg_rows` and `exp_avg_sq_arena` / `exp_avg_sq_rows` (fp32 zeros) and the
+        bias-correction table (engine.adam_bias_table) on the device.  `opt_step` counts the optimizer steps taken
+        (adamw_step runs step opt_step + 1); `opt_step_dev` (int64 CUDA, starts at 1) is the NEXT step of
+        adamw_device_round and `lr_dev` its learning rate, as VirtualWorkerGroup.attach_adamw's."""
+        if not (self.quant and self.one_launch):
+            raise NotImplementedError("ChocoWorkerGroup.attach_adamw: AdamW runs inside the one-launch quantized round "
+                                      "only (compressor='quant', one_launch=True); there is no standalone Adam step "
+                                      "launch for the slot-based paths (top-k, sign, the two quant launches)")
+        if self._sgd is not None:
+            raise ValueError("ChocoWorkerGroup.attach_adamw: the group carries one optimizer, and attach_sgd() gave "
+                             "it SGD")
+        from .engine import adam_bias_table, adam_hyper
+        betas = (float(betas[0]), float(betas[1]))
+        eps, weight_decay = float(eps), float(weight_decay)
+        if eps < 0.0 or weight_decay < 0.0:
+            raise ValueError("attach_adamw: eps and weight_decay must not be negative")
+        bias = adam_bias_table(*betas)                               # ValueError for betas it cannot serve
+        self._attach_grads("attach_adamw")
+        self.exp_avg_arena, self.exp_avg_sq_arena = torch.zeros_like(self.x), torch.zeros_like(self.x)
+        self.exp_avg_rows = self.exp_avg_arena[:, :self.numel]
+        self.exp_avg_sq_rows = self.exp_avg_sq_arena[:, :self.numel]
+        self._bias_dev = torch.from_numpy(bias).cuda()
+        self.opt_step = 0
+        self.opt_step_dev = torch.ones(1, dtype=torch.int64, device="cuda")
+        self.adamw_hyper = {"betas": betas, "eps": eps, "weight_decay": weight_decay, "decoupled": bool(decoupled),
+                            "zero_grads": bool(zero_grads)}
+        wd, omb1, beta2, omb2, eps32, dec, zg = adam_hyper(betas, eps, weight_decay, decoupled, zero_grads)
+        self._adamw = (omb1, beta2, omb2, eps32, wd, dec, zg)        # the entry points' order
+
+    def adamw_step(self, it, lr, stream=None):
+        """ONE launch: every local worker's AdamW update number opt_step + 1 at learning rate `lr`, then round `it`
+        on the updated rows; opt_step += 1.  A round with no active matching is the step alone (False is returned):
+        the same launch in its _at form, whose counter is entry `it` of a constant table, finds the record inactive."""
+        if self._adamw is None:
+            raise MXError("no AdamW state: call attach_adamw() first")
+        opt = (lr, None, self.opt_step + 1, None)
+        active = bool(self.engine.any_active[it])
+        if active:
+            self._quant_round(self.engine.round_index(it), None, stream, adamw=opt)
+        else:
+            self._quant_round(0, self._iter_entry(it), stream, adamw=opt, n_iters=self.engine.T + 1)
+        self.opt_step += 1
+        return active
+
+    def adamw_device_round(self, stream=None):
+        """Graph-replayable adamw_step: the round is read from `self.iter_dev`, the optimizer step from
+        `self.opt_step_dev` and the learning rate from `self.lr_dev` when the kernel runs, then both counters are
+        advanced (unconditionally, as sgd_device_round advances iter_dev).  A round counter outside the schedule or
+        a step below 1 makes the launch a no-op.  `self.opt_step` (adamw_step's host counter) is not touched."""
+        if self._adamw is None:
+            raise MXError("no AdamW state: call attach_adamw() first")
+        sp = stream_ptr(stream)
+        self._quant_round(0, self.iter_dev.data_ptr(), stream,
+                          adamw=(0.0, self.lr_dev.data_ptr(), 0, self.opt_step_dev.data_ptr()))
+        check(lib.mx_iter_advance(self.iter_dev.data_ptr(), 1, sp), "mx_iter_advance")
+        check(lib.mx_iter_advance(self.opt_step_dev.data_ptr(), 1, sp), "mx_iter_advance")
+
+    def adamw_communicate(self, lr):
+        """optimizer.step() + zero_grad() + communicate() of every worker at the group's own iteration counter, as
+        one launch; returns seconds like communicate()."""
+        it = self.iter
+        self.iter += 1
+        torch.cuda.synchronize()
+        tic = time.time()
+        self.adamw_step(it, lr)
+        self.wait_round()
+        return time.time() - tic
+
     def state_dict(self):
         """Checkpoint: rows (the fp32 `x`: under bfloat16 models the masters, with a "dtype" tag), the persistent
-        Choco state x_hat / s (communicator.py:179-182) and the iteration counter."""
+        Choco state x_hat / s (communicator.py:179-182) and the iteration counter; with attach_adamw the exp_avg /
+        exp_avg_sq rows and the optimizer step count."""
         P = self.numel
         state = {"kind": "choco", "iter": int(self.iter), "row_base": int(self.row_base), "k": int(self.k),
                  "workers": list(self.workers),
@@ -585,6 +690,10 @@ class ChocoWorkerGroup:
             state["dtype"] = "bfloat16"
         if self.momentum_rows is not None:   # attach_sgd with momentum; without it, key for key what it was
             state["momentum_rows"] = self.momentum_rows.detach().clone()
+        if self._adamw is not None:          # attach_adamw; every other group's checkpoint is key for key what it was
+            state["exp_avg_rows"] = self.exp_avg_rows.detach().clone()
+            state["exp_avg_sq_rows"] = self.exp_avg_sq_rows.detach().clone()
+            state["opt_step"] = int(self.opt_step)
         return state
 
     def load_state_dict(self, state):
@@ -598,7 +707,23 @@ class ChocoWorkerGroup:
             raise ValueError("checkpoint does not match this Choco worker group: it was saved %s SGD momentum rows, "
                              "this group is attached %s them" % (("with", "without") if "momentum_rows" in state
                                                                  else ("without", "with")))
+        adam = [state.get(k) for k in ("exp_avg_rows", "exp_avg_sq_rows")]
+        if any(a is None for a in adam) != all(a is None for a in adam):
+            # exp_avg without exp_avg_sq (or the other way round) would bias every later step
+            raise ValueError("checkpoint carries half of the Adam state: exp_avg_rows and exp_avg_sq_rows are only "
+                             "valid together")
+        if (adam[0] is not None) != (self._adamw is not None):
+            raise ValueError("checkpoint does not match this Choco worker group: it was saved %s AdamW state, this "
+                             "group is attached %s it" % (("with", "without") if adam[0] is not None
+                                                          else ("without", "with")))
+        if any(a is not None and tuple(a.shape) != (self.n_local, P) for a in adam):
+            raise ValueError("checkpoint does not match this Choco worker group: the shape of its Adam state")
         with torch.no_grad():
+            if self._adamw is not None:
+                self.exp_avg_rows.copy_(adam[0])
+                self.exp_avg_sq_rows.copy_(adam[1])
+                self.opt_step = int(state.get("opt_step") or 0)
+                self.opt_step_dev.fill_(self.opt_step + 1)
             if self.momentum_rows is not None:
                 self.momentum_rows.copy_(state["momentum_rows"])
             self.x[:, :P].copy_(state["rows"])

@@ -250,6 +250,40 @@ auto pick_nt(bool nt) {
 template <class IO, bool STEP, bool MOM>
 auto pick(int bits, bool nt) { return bits == 4 ? pick_nt<IO, 4, STEP, MOM>(nt) : pick_nt<IO, 8, STEP, MOM>(nt); }
 
+// the geometry of a launch, whatever its step: what every entry point checks of its shape, then the tile class,
+// the plan record and the persistent grid
+struct RoundGeo {
+    RoundDims dims;
+    const int32_t* rec;
+    unsigned grid;
+    bool nt;
+};
+inline int round_geo(const char* who, int64_t ld, int n_local, int64_t P, int bits, const int32_t* plan_dev,
+                     int64_t iter, const int64_t* iter_dev, int M, float alpha, float gamma, int64_t seed,
+                     int row_base, const float* norms, int64_t norm_ld, RoundGeo* out) {
+    MX_CHECK(bits == 4 || bits == 8, "%s: bits=%d (4 or 8)", who, bits);
+    MX_CHECK(n_local >= 1 && n_local <= kMaxRows, "%s: n_local=%d (1-%d rows; more take the two launches)", who,
+             n_local, kMaxRows);
+    MX_CHECK(P >= 1 && (n_local == 1 || ld >= P) && M >= 1 && row_base >= 0, "%s: P=%lld ld=%lld M=%d row_base=%d",
+             who, (long long)P, (long long)ld, M, row_base);
+    MX_CHECK(!norms || norm_ld >= n_buckets(P), "%s: norm_ld=%lld < %lld buckets", who, (long long)norm_ld,
+             (long long)n_buckets(P));
+    int bshift = 4;                                                  // 16 / row class buckets of a row per tile
+    while ((kItems >> bshift) < n_local) --bshift;
+    const int64_t tiles = (n_buckets(P) + (1 << bshift) - 1) >> bshift;
+    const int64_t words = mx::plan_words(n_local, M);
+    out->rec = iter_dev ? plan_dev : plan_dev + iter * words;        // with iter_dev: iter = n_iters
+    out->dims = RoundDims{ld, P, norm_ld, tiles, iter, iter, words, mix32((uint32_t)seed), n_local, M, row_base,
+                          bshift, alpha, gamma};
+    const int64_t target = mx::choco::g_quant_round_grid > 0
+                               ? (int64_t)mx::choco::g_quant_round_grid
+                               : (int64_t)mx::cu_count() * mx::choco::g_quant_round_blocks_per_cu;
+    out->grid = (unsigned)(tiles < target ? tiles : target);
+    // the existing rule: several workers' rows are far larger than the Infinity Cache, one row's are not
+    out->nt = n_local > 1;
+    return MX_OK;
+}
+
 // what the entry points of a form check alike, then the launch; STEP with g / m and the hyperparameters, a form
 // with an image with p
 template <class IO, bool STEP>
@@ -259,34 +293,19 @@ int round_launch(const char* who, float* x, typename IO::GT* g, float* m, float*
                  int64_t norm_ld, float lr, const float* lr_dev, float wd, float mom, int nesterov, int zero_grads,
                  void* stream) {
     MX_CHECK(x && xhat && s && plan_dev && (!STEP || g) && (!IO::kImage || p), "%s: null pointer", who);
-    MX_CHECK(bits == 4 || bits == 8, "%s: bits=%d (4 or 8)", who, bits);
-    MX_CHECK(n_local >= 1 && n_local <= kMaxRows, "%s: n_local=%d (1-%d rows; more take the two launches)", who,
-             n_local, kMaxRows);
-    MX_CHECK(P >= 1 && (n_local == 1 || ld >= P) && M >= 1 && row_base >= 0, "%s: P=%lld ld=%lld M=%d row_base=%d",
-             who, (long long)P, (long long)ld, M, row_base);
     if constexpr (STEP) {
         MX_CHECK((mom != 0.0f) == (m != nullptr), "%s: the momentum rows are given exactly when momentum != 0", who);
         MX_CHECK(mom != 0.0f || !nesterov, "%s: nesterov needs momentum", who);
     }
-    MX_CHECK(!norms || norm_ld >= n_buckets(P), "%s: norm_ld=%lld < %lld buckets", who, (long long)norm_ld,
-             (long long)n_buckets(P));
-    int bshift = 4;                                                  // 16 / row class buckets of a row per tile
-    while ((kItems >> bshift) < n_local) --bshift;
-    const int64_t tiles = (n_buckets(P) + (1 << bshift) - 1) >> bshift;
-    const int64_t words = mx::plan_words(n_local, M);
-    const int32_t* rec = iter_dev ? plan_dev : plan_dev + iter * words;   // with iter_dev: iter = n_iters
-    const RoundDims dims{ld, P, norm_ld, tiles, iter, iter, words, mix32((uint32_t)seed), n_local, M, row_base,
-                         bshift, alpha, gamma};
+    RoundGeo geo;
+    if (const int rc = round_geo(who, ld, n_local, P, bits, plan_dev, iter, iter_dev, M, alpha, gamma, seed, row_base,
+                                 norms, norm_ld, &geo))
+        return rc;
     const SgdHyper h{lr, wd, mom, lr_dev, nullptr, nesterov != 0, zero_grads != 0};
-    const int64_t target = mx::choco::g_quant_round_grid > 0
-                               ? (int64_t)mx::choco::g_quant_round_grid
-                               : (int64_t)mx::cu_count() * mx::choco::g_quant_round_blocks_per_cu;
-    // the existing rule: several workers' rows are far larger than the Infinity Cache, one row's are not
-    const bool nt = n_local > 1;
-    const auto kern = !STEP ? pick<IO, false, false>(bits, nt)
-                            : mom != 0.0f ? pick<IO, STEP, STEP>(bits, nt) : pick<IO, STEP, false>(bits, nt);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles < target ? tiles : target)), dim3(kTPB), 0, mx::as_stream(stream), x,
-                       g, m, xhat, s, norms, rec, iter_dev, dims, IO::tail(h, p));
+    const auto kern = !STEP ? pick<IO, false, false>(bits, geo.nt)
+                            : mom != 0.0f ? pick<IO, STEP, STEP>(bits, geo.nt) : pick<IO, STEP, false>(bits, geo.nt);
+    hipLaunchKernelGGL(kern, dim3(geo.grid), dim3(kTPB), 0, mx::as_stream(stream), x, g, m, xhat, s, norms, geo.rec,
+                       iter_dev, geo.dims, IO::tail(h, p));
     MX_LAUNCH_CHECK();
     return MX_OK;
 }

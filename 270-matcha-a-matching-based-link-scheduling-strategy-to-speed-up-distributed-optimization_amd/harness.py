@@ -221,7 +221,10 @@ class VirtualTrainer:
         all-bfloat16 models in mixed precision, attach_adamw(master_weights=True),
         csrc/adamw_mix_bf16.hip): betas (0.9, 0.999), eps 1e-8 and the harness's weight decay 5e-4 as the
         decoupled decay, or what adamw_hyper (attach_adamw's keyword arguments) overrides; checkpoints
-        save exp_avg / exp_avg_sq rows and the step count.
+        save exp_avg / exp_avg_sq rows and the step count.  With args.compress and compressor "quant" the
+        step runs in front of the one-launch quantized ChocoSGD round (ChocoWorkerGroup.attach_adamw,
+        csrc/choco_quant_adamw_round.hip; all-bfloat16 models: csrc/choco_quant_adamw_round_bf16.hip), under
+        fused_sgd's conditions there; top-k and sign stay refused.
 
         fused_lion=True (same conditions, not together with the other two): the same with the Lion update
         in the launch (VirtualWorkerGroup.attach_lion / lion_communicate, csrc/lion_mix.hip; all-bfloat16
@@ -288,9 +291,11 @@ class VirtualTrainer:
         self.fused_adamw = bool(fused_adamw)
         if self.fused_adamw and self.fused_sgd:
             raise ValueError("fused_adamw and fused_sgd are mutually exclusive: the group carries one optimizer")
-        if self.fused_adamw and (batched or args.compress):
-            raise ValueError("fused_adamw needs per-worker (non-batched), uncompressed training: the vmap path's "
-                             "gradients are fresh tensors every iteration and ChocoSGD mixes compressed messages")
+        if self.fused_adamw and (batched or (args.compress and getattr(args, "compressor", "topk") != "quant")):
+            raise ValueError("fused_adamw needs per-worker (non-batched) training, uncompressed or with the quant "
+                             "compressor: the vmap path's gradients are fresh tensors every iteration, and ChocoSGD has "
+                             "AdamW in its one-launch quantized round only (top-k and sign mix compressed messages "
+                             "from slots and have no Adam step launch)")
         self.fused_lion = bool(fused_lion)
         if self.fused_lion and (self.fused_sgd or self.fused_adamw):
             raise ValueError("fused_lion, fused_adamw and fused_sgd are mutually exclusive: the group carries one "
@@ -346,13 +351,14 @@ class VirtualTrainer:
             dts = {p.dtype for m in self.models for p in m.parameters()}
             # all-bfloat16 models: only the one-launch quant round has the mixed-precision form
             # (csrc/choco_quant_round_bf16.hip: fp32 x, x_hat, s and momentum, the models their rounded image)
-            bf16 = self.fused_sgd and compressor == "quant" and dts == {torch.bfloat16}
-            if self.fused_sgd and dts != {torch.float32} and not bf16:
+            step = self.fused_sgd or self.fused_adamw                # (fused_adamw: the quant compressor, checked above)
+            bf16 = step and compressor == "quant" and dts == {torch.bfloat16}
+            if step and dts != {torch.float32} and not bf16:
                 raise ValueError("fused_sgd with compress needs float32 models: ChocoWorkerGroup's rows and its SGD "
                                  "step are fp32-only, but for the quant compressor, which also takes all-bfloat16 "
                                  "models")
             extra = {"bits": getattr(args, "quant_bits", 8)} if compressor == "quant" else {}
-            if self.fused_sgd and compressor == "quant":         # step + quantizer + round: csrc/choco_quant_round.hip
+            if step and compressor == "quant":   # step + quantizer + round: csrc/choco_quant_round.hip, _adamw_round.hip
                 extra["one_launch"] = True
             if bf16:
                 extra["dtype"] = torch.bfloat16
@@ -380,8 +386,16 @@ class VirtualTrainer:
             # all-bfloat16 models: fp32 master weights, as above (csrc/adamw_mix_bf16.hip)
             hyper = {"betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 5e-4, "decoupled": True}
             hyper.update(adamw_hyper or {})
-            self.group.attach_adamw(**hyper, master_weights=mixed, clip_grad_norm=clip_grad_norm,
-                                    param_groups=param_groups)
+            if args.compress:
+                # ChocoSGD: the step runs inside the one-launch quant round (csrc/choco_quant_adamw_round.hip; a
+                # bfloat16 group keeps its own fp32 x); no clipping, no groups
+                if clip_grad_norm is not None or param_groups is not None or slowmo_every is not None:
+                    raise ValueError("fused_adamw with compress takes no clip_grad_norm, param_groups or "
+                                     "slowmo_every: ChocoWorkerGroup.attach_adamw has none of them")
+                self.group.attach_adamw(**hyper)
+            else:
+                self.group.attach_adamw(**hyper, master_weights=mixed, clip_grad_norm=clip_grad_norm,
+                                        param_groups=param_groups)
         if self.fused_lion:
             # all-bfloat16 models: fp32 master weights, as above (csrc/lion_mix_bf16.hip)
             hyper = {"betas": (0.9, 0.99), "weight_decay": 5e-4}

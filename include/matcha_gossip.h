@@ -1349,6 +1349,44 @@ int mx_choco_quant_sgd_round_bf16_at(float* x, uint16_t* g, float* m, float* xha
                                      int64_t seed, int row_base, float* norms, int64_t norm_ld, float lr,
                                      const float* lr_dev, float weight_decay, float momentum, int nesterov,
                                      int zero_grads, void* stream);
+/* torch.optim.AdamW's step (decoupled = 0: torch.optim.Adam's, the decay as an L2 term) of every row, then that
+ * round, in the same launch (csrc/choco_quant_adamw_round.hip; train_mpi.py:131-142 with AdamW as the optimizer,
+ * then communicator.py:175-230): mx_adamw_mix's update of x, m (exp_avg) and v (exp_avg_sq) from g at optimizer
+ * step `step` (step_dev non-NULL: *step_dev when the kernel runs), with (bc1, bc2s) from entry min(step, n_bias) - 1
+ * of bias_dev (float [n_bias][2] on the device, engine.adam_bias_table) and omb1 / omb2 the fp32 roundings of
+ * 1 - beta1 / 1 - beta2; the round on the updated x from the registers.  x, x_hat, s and the norms are the bits of
+ * mx_choco_quant_round on that x, m and v the bits of mx_adamw_mix's.  A round of the schedule with no active
+ * matching is the step alone; a counter outside [0, n_iters), a record with receive slots or the peer-reads bit,
+ * or an optimizer step below 1: nothing is written.  Refused before any launch: everything the sgd entry points
+ * refuse, g, m, v or bias_dev NULL, n_bias < 1, step < 1 without step_dev.  The _bf16 forms are the sgd _bf16
+ * forms' contract: g bfloat16, p = bf16_rne(x) wherever x is written, every fp32 array the fp32 launch's bits. */
+int mx_choco_quant_adamw_round(float* x, float* g, float* m, float* v, float* xhat, float* s, int64_t ld, int n_local,
+                               int64_t P, int bits, const int32_t* plan_dev, int64_t iter, int M, float alpha,
+                               float gamma, int64_t seed, int row_base, float* norms, int64_t norm_ld, float lr,
+                               const float* lr_dev, float omb1, float beta2, float omb2, float eps, float weight_decay,
+                               int decoupled, int zero_grads, const float* bias_dev, int64_t n_bias, int64_t step,
+                               const int64_t* step_dev, void* stream);
+int mx_choco_quant_adamw_round_at(float* x, float* g, float* m, float* v, float* xhat, float* s, int64_t ld,
+                                  int n_local, int64_t P, int bits, const int32_t* plan_dev, const int64_t* iter_dev,
+                                  int64_t n_iters, int M, float alpha, float gamma, int64_t seed, int row_base,
+                                  float* norms, int64_t norm_ld, float lr, const float* lr_dev, float omb1,
+                                  float beta2, float omb2, float eps, float weight_decay, int decoupled,
+                                  int zero_grads, const float* bias_dev, int64_t n_bias, int64_t step,
+                                  const int64_t* step_dev, void* stream);
+int mx_choco_quant_adamw_round_bf16(float* x, uint16_t* g, float* m, float* v, float* xhat, float* s, uint16_t* p,
+                                    int64_t ld, int n_local, int64_t P, int bits, const int32_t* plan_dev,
+                                    int64_t iter, int M, float alpha, float gamma, int64_t seed, int row_base,
+                                    float* norms, int64_t norm_ld, float lr, const float* lr_dev, float omb1,
+                                    float beta2, float omb2, float eps, float weight_decay, int decoupled,
+                                    int zero_grads, const float* bias_dev, int64_t n_bias, int64_t step,
+                                    const int64_t* step_dev, void* stream);
+int mx_choco_quant_adamw_round_bf16_at(float* x, uint16_t* g, float* m, float* v, float* xhat, float* s, uint16_t* p,
+                                       int64_t ld, int n_local, int64_t P, int bits, const int32_t* plan_dev,
+                                       const int64_t* iter_dev, int64_t n_iters, int M, float alpha, float gamma,
+                                       int64_t seed, int row_base, float* norms, int64_t norm_ld, float lr,
+                                       const float* lr_dev, float omb1, float beta2, float omb2, float eps,
+                                       float weight_decay, int decoupled, int zero_grads, const float* bias_dev,
+                                       int64_t n_bias, int64_t step, const int64_t* step_dev, void* stream);
 
 /* ---------------------------------------------------------------- cross-GPU exchange (RCCL)
  * One process per GPU; workers partitioned by owner[].  mx_exchange_round posts, inside one

@@ -7,6 +7,8 @@
     python tools/train_gpu.py --compress --compressor sign --fused-sgd --momentum 0.9
                                                                                 # ChocoSGD, SGD step fused into the compress pass
     python tools/train_gpu.py --compress --compressor quant --fused-sgd --bf16  # one-launch quantized round, bf16 models
+    python tools/train_gpu.py --lr 1e-3 --no-warmup --compress --compressor quant --fused-adamw --wd 1e-2 [--bf16]
+                                                                                # the same round with AdamW's step in it
     python tools/train_gpu.py --lr 1e-3 --no-warmup --fused-adamw --wd 1e-2       # AdamW step fused into the round
     python tools/train_gpu.py --lr 1e-3 --no-warmup --fused-adamw --wd 1e-2 --bf16 # the same, bf16 models + fp32 masters
     python tools/train_gpu.py --lr 1e-4 --no-warmup --fused-lion --wd 1e-2 --bf16 --lion-bf16-momentum
@@ -156,9 +158,9 @@ def main():
     if a.bf16:
         if world > 1:
             ap.error("--bf16: bfloat16 worker rows are mixed on one GPU only")
-        if a.compress and not (a.compressor == "quant" and a.fused_sgd):
+        if a.compress and not (a.compressor == "quant" and (a.fused_sgd or a.fused_adamw)):
             ap.error("--bf16 --compress: ChocoSGD has bfloat16 models in its one-launch quantized round only: "
-                     "--compressor quant --fused-sgd")
+                     "--compressor quant --fused-sgd (or --fused-adamw)")
         fp32_fn = model_fn
 
         def model_fn():
