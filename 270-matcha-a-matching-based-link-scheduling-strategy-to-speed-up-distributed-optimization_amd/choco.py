@@ -285,25 +285,30 @@ class ChocoWorkerGroup:
         at = (iter_dev, self.engine.T if n_iters is None else n_iters) if iter_dev else (int(it),)
         tail = (self.engine.M, self.engine.alpha32, self.gamma32, self.seed, self.row_base,
                 self.round_norms.data_ptr(), self.round_norms.shape[1])
-        if adamw is not None:
-            if self._adamw is None:
-                raise MXError("no AdamW state: call attach_adamw() first")
-            fn = "mx_choco_quant_adamw_round" + ("_bf16" if bf else "") + ("_at" if iter_dev else "")
-            check(getattr(lib, fn)(self.x.data_ptr(), self.grad_arena.data_ptr(), self.exp_avg_arena.data_ptr(),
-                                   self.exp_avg_sq_arena.data_ptr(), *head, *at, *tail, float(adamw[0]), adamw[1],
-                                   *self._adamw, self._bias_dev.data_ptr(), self._bias_dev.shape[0], int(adamw[2]),
-                                   adamw[3], stream_ptr(stream)), fn)
-            return
-        if sgd is None:
-            fn = "mx_choco_quant_round" + ("_bf16" if bf else "") + ("_at" if iter_dev else "")
-            check(getattr(lib, fn)(self.x.data_ptr(), *head, *at, *tail, stream_ptr(stream)), fn)
-            return
+        step, par = ("adamw", adamw) if adamw is not None else ("sgd", sgd) if sgd is not None else (None, None)
+        stem, build = self._QUANT_STEPS[step]
+        rows, hyper = build(self, par)           # the step's arrays after x, its constants after the round's
+        fn = stem + ("_bf16" if bf else "") + ("_at" if iter_dev else "")
+        check(getattr(lib, fn)(self.x.data_ptr(), *rows, *head, *at, *tail, *hyper, stream_ptr(stream)), fn)
+
+    def _quant_sgd_args(self, par):
         if self._sgd is None:
             raise MXError("no SGD state: call attach_sgd() first")
         m = self.mom_arena.data_ptr() if self.mom_arena is not None else None
-        fn = "mx_choco_quant_sgd_round" + ("_bf16" if bf else "") + ("_at" if iter_dev else "")
-        check(getattr(lib, fn)(self.x.data_ptr(), self.grad_arena.data_ptr(), m, *head, *at, *tail, float(sgd[0]),
-                               sgd[1], *self._sgd, stream_ptr(stream)), fn)
+        return (self.grad_arena.data_ptr(), m), (float(par[0]), par[1], *self._sgd)
+
+    def _quant_adamw_args(self, par):
+        if self._adamw is None:
+            raise MXError("no AdamW state: call attach_adamw() first")
+        return ((self.grad_arena.data_ptr(), self.exp_avg_arena.data_ptr(), self.exp_avg_sq_arena.data_ptr()),
+                (float(par[0]), par[1], *self._adamw, self._bias_dev.data_ptr(), self._bias_dev.shape[0], int(par[2]),
+                 par[3]))
+
+    # the steps of the one-launch round: the entry point's name stem and the builder of the step's arguments from
+    # the caller's tuple (sgd: (lr, lr_dev); adamw: (lr, lr_dev, step, step_dev)).  A new step is one row
+    _QUANT_STEPS = {None: ("mx_choco_quant_round", lambda self, par: ((), ())),
+                    "sgd": ("mx_choco_quant_sgd_round", _quant_sgd_args),
+                    "adamw": ("mx_choco_quant_adamw_round", _quant_adamw_args)}
 
     def _quant_compress(self, it, iter_dev, stream=None):
         """mx_choco_quant_compress at round `it`, or at the device counter (`iter_dev`: its address)"""

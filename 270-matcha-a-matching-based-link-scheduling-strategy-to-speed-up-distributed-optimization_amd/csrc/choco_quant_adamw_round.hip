@@ -16,7 +16,7 @@
 // as x' and x_hat.  g, m and v STREAM: two register sets of (g, m, v) alternate over the items, item q + 1's
 // three loads are issued before item q's update, and item q's set is dead once m', v' and the zeros over g are
 // stored, which happens before its differences are quantized.  Payload in phase 1: 32 + 2 x 12 registers.  Phase
-// 2 is quant_round's unchanged (s of all four items, the partners' codes from LDS, three stores).
+// 2 is the round's own (s of all four items, the partners' codes from LDS, three stores).
 // The update's divisions and square root (correctly rounded, adam_update.h) sit between the loads and the
 // quantizer's butterflies; nothing of them reaches memory but m' and v'.
 //
@@ -24,13 +24,11 @@
 // step below 1 -- the launch writes nothing.  A round of the schedule with no active matching is the step alone:
 // x', m', v' and the zeros over g.  Rows off a 16-byte boundary (x, x_hat, s, g, m or v) and the bucket that
 // holds P go element by element; nothing is written at or past P.  No atomics, no workspace, no second launch.
-// The kernel and its host side live in choco_quant_adamw_round.h over a storage form; this file instantiates
-// them for fp32 gradients and no image.
+// The kernel and its host side are choco_quant_round.h's quant_round and round_launch under
+// choco_quant_adamw_round.h's AdamStep; this file instantiates them for fp32 gradients and no image.
 #include "choco_quant_adamw_round.h"
 
-namespace {
-constexpr auto launch = mx::choco::qround::adamw_round_launch<mx::choco::qround::AdamFp32Io>;
-}  // namespace
+using namespace mx::choco::qround;
 
 extern "C" int mx_choco_quant_adamw_round(float* x, float* g, float* m, float* v, float* xhat, float* s, int64_t ld,
                                           int n_local, int64_t P, int bits, const int32_t* plan_dev, int64_t iter,
@@ -40,9 +38,12 @@ extern "C" int mx_choco_quant_adamw_round(float* x, float* g, float* m, float* v
                                           const float* bias_dev, int64_t n_bias, int64_t step,
                                           const int64_t* step_dev, void* stream) {
     MX_CHECK(iter >= 0, "mx_choco_quant_adamw_round: iter < 0");
-    return launch("mx_choco_quant_adamw_round", x, g, m, v, xhat, s, nullptr, ld, n_local, P, bits, plan_dev, iter,
-                  nullptr, M, alpha, gamma, seed, row_base, norms, norm_ld, lr, lr_dev, omb1, beta2, omb2, eps,
-                  weight_decay, decoupled, zero_grads, bias_dev, n_bias, step, step_dev, stream);
+    return round_launch<Fp32Io, AdamStep>(
+        "mx_choco_quant_adamw_round", x, g, xhat, s, nullptr, ld, n_local, P, bits, plan_dev, iter, nullptr, M,
+        alpha, gamma, seed, row_base, norms, norm_ld,
+        adam_hyper(lr, lr_dev, omb1, beta2, omb2, eps, weight_decay, decoupled, zero_grads, bias_dev, n_bias, step,
+                   step_dev),
+        stream, m, v);
 }
 
 extern "C" int mx_choco_quant_adamw_round_at(float* x, float* g, float* m, float* v, float* xhat, float* s,
@@ -54,7 +55,10 @@ extern "C" int mx_choco_quant_adamw_round_at(float* x, float* g, float* m, float
                                              const float* bias_dev, int64_t n_bias, int64_t step,
                                              const int64_t* step_dev, void* stream) {
     MX_CHECK(iter_dev && n_iters >= 0, "mx_choco_quant_adamw_round_at: bad iteration counter");
-    return launch("mx_choco_quant_adamw_round_at", x, g, m, v, xhat, s, nullptr, ld, n_local, P, bits, plan_dev,
-                  n_iters, iter_dev, M, alpha, gamma, seed, row_base, norms, norm_ld, lr, lr_dev, omb1, beta2, omb2,
-                  eps, weight_decay, decoupled, zero_grads, bias_dev, n_bias, step, step_dev, stream);
+    return round_launch<Fp32Io, AdamStep>(
+        "mx_choco_quant_adamw_round_at", x, g, xhat, s, nullptr, ld, n_local, P, bits, plan_dev, n_iters, iter_dev, M,
+        alpha, gamma, seed, row_base, norms, norm_ld,
+        adam_hyper(lr, lr_dev, omb1, beta2, omb2, eps, weight_decay, decoupled, zero_grads, bias_dev, n_bias, step,
+                   step_dev),
+        stream, m, v);
 }

@@ -17,15 +17,13 @@
 //
 // Traffic per parameter: g 2 + 2, m 8, v 8, x 8, x_hat 8, s 8, p 2 = 46 bytes where the fp32 launch moves 48.
 //
-// The kernel is choco_quant_adamw_round.h's over AdamBf16Io: a lane still owns 4 consecutive columns of an item,
-// one 8-byte access on g and p and 16 bytes on the fp32 arrays; the vector path needs g and p 8-byte aligned on
-// top of the fp32 arrays' 16, everything else goes element by element (2-byte accesses on g and p).  g streams as
-// its 2 registers and is widened at its use; p is packed from the registers that hold the final x.
+// The kernel is choco_quant_round.h's quant_round over Bf16Io under AdamStep: a lane still owns 4 consecutive
+// columns of an item, one 8-byte access on g and p and 16 bytes on the fp32 arrays; the vector path needs g and p
+// 8-byte aligned on top of the fp32 arrays' 16, everything else goes element by element (2-byte accesses on g and
+// p).  g streams as its 2 registers and is widened at its use; p is packed from the registers that hold the final x.
 #include "choco_quant_adamw_round.h"
 
-namespace {
-constexpr auto launch = mx::choco::qround::adamw_round_launch<mx::choco::qround::AdamBf16Io>;
-}  // namespace
+using namespace mx::choco::qround;
 
 extern "C" int mx_choco_quant_adamw_round_bf16(float* x, uint16_t* g, float* m, float* v, float* xhat, float* s,
                                                uint16_t* p, int64_t ld, int n_local, int64_t P, int bits,
@@ -36,9 +34,12 @@ extern "C" int mx_choco_quant_adamw_round_bf16(float* x, uint16_t* g, float* m, 
                                                int decoupled, int zero_grads, const float* bias_dev, int64_t n_bias,
                                                int64_t step, const int64_t* step_dev, void* stream) {
     MX_CHECK(iter >= 0, "mx_choco_quant_adamw_round_bf16: iter < 0");
-    return launch("mx_choco_quant_adamw_round_bf16", x, g, m, v, xhat, s, p, ld, n_local, P, bits, plan_dev, iter,
-                  nullptr, M, alpha, gamma, seed, row_base, norms, norm_ld, lr, lr_dev, omb1, beta2, omb2, eps,
-                  weight_decay, decoupled, zero_grads, bias_dev, n_bias, step, step_dev, stream);
+    return round_launch<Bf16Io, AdamStep>(
+        "mx_choco_quant_adamw_round_bf16", x, g, xhat, s, p, ld, n_local, P, bits, plan_dev, iter, nullptr, M,
+        alpha, gamma, seed, row_base, norms, norm_ld,
+        adam_hyper(lr, lr_dev, omb1, beta2, omb2, eps, weight_decay, decoupled, zero_grads, bias_dev, n_bias, step,
+                   step_dev),
+        stream, m, v);
 }
 
 extern "C" int mx_choco_quant_adamw_round_bf16_at(float* x, uint16_t* g, float* m, float* v, float* xhat, float* s,
@@ -51,7 +52,10 @@ extern "C" int mx_choco_quant_adamw_round_bf16_at(float* x, uint16_t* g, float* 
                                                   const float* bias_dev, int64_t n_bias, int64_t step,
                                                   const int64_t* step_dev, void* stream) {
     MX_CHECK(iter_dev && n_iters >= 0, "mx_choco_quant_adamw_round_bf16_at: bad iteration counter");
-    return launch("mx_choco_quant_adamw_round_bf16_at", x, g, m, v, xhat, s, p, ld, n_local, P, bits, plan_dev,
-                  n_iters, iter_dev, M, alpha, gamma, seed, row_base, norms, norm_ld, lr, lr_dev, omb1, beta2, omb2,
-                  eps, weight_decay, decoupled, zero_grads, bias_dev, n_bias, step, step_dev, stream);
+    return round_launch<Bf16Io, AdamStep>(
+        "mx_choco_quant_adamw_round_bf16_at", x, g, xhat, s, p, ld, n_local, P, bits, plan_dev, n_iters, iter_dev, M,
+        alpha, gamma, seed, row_base, norms, norm_ld,
+        adam_hyper(lr, lr_dev, omb1, beta2, omb2, eps, weight_decay, decoupled, zero_grads, bias_dev, n_bias, step,
+                   step_dev),
+        stream, m, v);
 }

@@ -1,9 +1,12 @@
-// choco_quant_round.h -- the one-launch quantized ChocoSGD round as one kernel over a storage form, and its host
-// side: what choco_quant_round.hip (fp32 models: Fp32Io) and choco_quant_round_bf16.hip (bfloat16 models and
-// gradients over fp32 x, x_hat, s and m: Bf16Io) share.  The design is at the head of choco_quant_round.hip, the
+// choco_quant_round.h -- the one-launch quantized ChocoSGD round as one kernel over a storage form and a step
+// policy, and its host side: what choco_quant_round.hip (fp32 models: Fp32Io), choco_quant_round_bf16.hip
+// (bfloat16 models and gradients over fp32 x, x_hat, s and m: Bf16Io) and the AdamW forms
+// (choco_quant_adamw_round.h: AdamStep) share.  The design is at the head of choco_quant_round.hip, the
 // mixed-precision contract at the head of choco_quant_round_bf16.hip.  A form says how g is held and widened and
 // whether an image of the final x is written; everything between the widening and the x store is the same
-// instructions in both, so x, x_hat, s, m and the norms are the same bits for gradients of the same values.
+// instructions in both, so x, x_hat, s, m and the norms are the same bits for gradients of the same values.  A step
+// says what happens between "x and x_hat are loaded" and "x' is known"; the schedule lookup, the quantizer, the
+// barrier and the apply phase exist once, in quant_round.
 #pragma once
 #include "choco_quant.h"
 #include "mx_common.h"
@@ -74,32 +77,38 @@ __device__ __forceinline__ void store_q(const U2& v, uint16_t* p, int64_t c, boo
 }
 
 // the storage forms.  GT / GC: the gradient's element and a lane's 4 of them, al_g: a row of them takes the
-// form's wide access (16 bytes, 8 bytes); kImage: the launch writes p = bf16_rne(x) wherever it writes x.  Tail is
-// the kernel's last argument, the step's constants and in a form with an image p: a member, not a parameter of
-// its own, so the fp32 kernel's argument block is what it was before there was a second form
+// form's wide access (16 bytes, 8 bytes); kImage: the launch writes p = bf16_rne(x) wherever it writes x
 struct Fp32Io {
     using GT = float;
     using GC = F4;
-    struct Tail {
-        SgdHyper h;
-    };
     static constexpr bool kImage = false;
     static __device__ __forceinline__ GC zero() { return F4{0.0f, 0.0f, 0.0f, 0.0f}; }
     static __device__ __forceinline__ bool al_g(const GT* g) { return al16(g); }
-    static Tail tail(const SgdHyper& h, uint16_t*) { return {h}; }
 };
 struct Bf16Io {
     using GT = uint16_t;
     using GC = U2;
-    struct Tail {
-        SgdHyper h;
-        uint16_t* p;
-    };
     static constexpr bool kImage = true;
     static __device__ __forceinline__ GC zero() { return U2{0u, 0u}; }
     static __device__ __forceinline__ bool al_g(const GT* g) { return mx::fused::al8(g); }
-    static Tail tail(const SgdHyper& h, uint16_t* p) { return {h, p}; }
 };
+
+// the kernel's last argument: the step's constants and in a form with an image p: a member, not a parameter of
+// its own, so the fp32 kernel's argument block is what it was before there was a second form
+template <class H, bool IMAGE>
+struct Tail {
+    H h;
+};
+template <class H>
+struct Tail<H, true> {
+    H h;
+    uint16_t* p;
+};
+template <class IO, class H>
+Tail<H, IO::kImage> make_tail(const H& h, uint16_t* p) {
+    if constexpr (IO::kImage) return {h, p};
+    else return {h};
+}
 
 // message item `it` of LDS image (cw, un) applied to a lane's four columns
 template <int BITS, bool OWN>
@@ -117,25 +126,37 @@ __device__ __forceinline__ void apply_item(const uint32_t (*cw)[64], const float
 }
 
 // x and, in a form with an image, its rounded image next to it: packed from the registers that hold x
-template <class IO, bool NT>
-__device__ __forceinline__ void store_x(const F4& xv, float* x, const typename IO::Tail& tl, int64_t off, int64_t c,
-                                        bool vec, int64_t P) {
+template <class IO, bool NT, class TL>
+__device__ __forceinline__ void store_x(const F4& xv, float* x, const TL& tl, int64_t off, int64_t c, bool vec,
+                                        int64_t P) {
     store_q<NT>(xv, x + off, c, vec, P);
     if constexpr (IO::kImage) store_q<NT>(mx::fused::pack4(xv), tl.p + off, c, vec, P);
 }
 
-template <class IO, int BITS, bool STEP, bool MOM, bool NT>
+// A step policy is a struct of types and static functions (fused_round.h's idiom); it supplies
+//   Hyper, State, no_step, setup   the launch's constants, "this launch does nothing", what a launch derives
+//   kSteps                         false: the round alone, an inactive round of the schedule writes nothing
+//   Held<IO>, clear, hold          what of a wave's four items stays in flight across the tile, loaded with x and
+//                                  x_hat before the first use (SGD: g and m)
+//   Stream<IO>, load               what of one item streams (AdamW: g, m, v): two sets alternate, item q + 1's
+//                                  loads are issued before item q's update
+//   al                             the item's alignment conjunction so far, and the step's arrays' part of it
+//   step                           x to x' in a lane's four columns, then the stores: the state rows, the zeros over g
+// (StepBase: nothing held, nothing streamed, no part in the alignment -- a step overrides what it has)
+//   given, check, kernel           the host side: its pointers, its argument checks, its instantiation
+// The state rows (m; m and v) are the kernel's own __restrict__ parameters, one per element of the pack F.
+// NoStep keeps SgdStep's argument block (g, m and SgdHyper, unused): the round alone is launched as it always was.
+template <class IO, class Step, int BITS, bool NT, class... F>
 __global__ __launch_bounds__(kTPB) void quant_round(float* __restrict__ x, typename IO::GT* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ xh,
+                                                    F* __restrict__... rows, float* __restrict__ xh,
                                                     float* __restrict__ s, float* __restrict__ norms,
                                                     const int32_t* __restrict__ rec_in,
                                                     const int64_t* __restrict__ iter_dev, RoundDims a,
-                                                    typename IO::Tail tl) {
-    const SgdHyper& h = tl.h;
-    static_assert(STEP || !MOM, "momentum belongs to the step");
+                                                    Tail<typename Step::Hyper, IO::kImage> tl) {
+    const typename Step::Hyper& h = tl.h;
     __shared__ uint32_t codes[2][kItems][64];                        // one byte per column, a word per lane
     __shared__ float units[2][kItems];                               // fmul(norm, c) of each item
-    // round_rec's rules (choco_round.h), except that under STEP an inactive round of the schedule still steps
+    // round_rec's rules (choco_round.h), except that under a step an inactive round of the schedule still steps
     int64_t rnd = a.round;
     const int32_t* __restrict__ rec = rec_in;
     bool on = true;
@@ -146,9 +167,10 @@ __global__ __launch_bounds__(kTPB) void quant_round(float* __restrict__ x, typen
         on = rec[0] != 0;
     }
     if (rec[1] != 0 || (rec[2] & 2)) return;                         // receive slots, peer reads: not this kernel's
-    if (!STEP && !on) return;
-    SgdState st{0.0f};
-    if constexpr (STEP) mx::fused::sgd_setup(st, h);                 // -lr, from lr_dev when given
+    if (!Step::kSteps && !on) return;
+    typename Step::State st;
+    if (Step::no_step(st, h)) return;                                // (AdamW: an optimizer step below 1) nothing
+    Step::setup(st, h);                                              // -lr / the bias corrections, lr from lr_dev
     const uint32_t kr = mix32(a.seed_mix ^ (uint32_t)rnd);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -161,8 +183,9 @@ __global__ __launch_bounds__(kTPB) void quant_round(float* __restrict__ x, typen
         // the wave's items: row, first column of the lane, live (a row of the group, a bucket below P), vec
         int64_t off[kIPW], col[kIPW];
         bool live[kIPW], vec[kIPW];
-        F4 xv[kIPW], hv[kIPW], mv[kIPW];
-        typename IO::GC gv[kIPW];
+        F4 xv[kIPW], hv[kIPW];
+        typename Step::template Held<IO> hd;
+        typename Step::template Stream<IO> sm[2];
 #pragma unroll
         for (int q = 0; q < kIPW; ++q) {
             const int i = wave * kIPW + q;
@@ -171,27 +194,29 @@ __global__ __launch_bounds__(kTPB) void quant_round(float* __restrict__ x, typen
             off[q] = (int64_t)r * a.ld;
             col[q] = b0 + lane * 4;
             live[q] = r < a.n_local && b0 < a.P;
-            vec[q] = b0 + kBucket <= a.P && al16(x + off[q]) && al16(xh + off[q]) && al16(s + off[q]);
-            if constexpr (STEP) vec[q] = vec[q] && IO::al_g(g + off[q]) && (!MOM || al16(m + off[q]));
+            vec[q] = Step::template al<IO>(
+                b0 + kBucket <= a.P && al16(x + off[q]) && al16(xh + off[q]) && al16(s + off[q]), g, rows..., off[q]);
             if constexpr (IO::kImage) vec[q] = vec[q] && mx::fused::al8(tl.p + off[q]);
-            xv[q] = hv[q] = mv[q] = zero;
-            gv[q] = IO::zero();
+            xv[q] = hv[q] = zero;
+            Step::template clear<IO>(hd, q);
             if (live[q]) {
                 xv[q] = load_q<NT>(x + off[q], col[q], vec[q], a.P);
                 hv[q] = load_q<NT>(xh + off[q], col[q], vec[q], a.P);
-                if constexpr (STEP) gv[q] = load_q<NT>(g + off[q], col[q], vec[q], a.P);
-                if constexpr (MOM) mv[q] = load_q<NT>(m + off[q], col[q], vec[q], a.P);
+                Step::template hold<IO, NT>(hd, q, g, rows..., off[q], col[q], vec[q], a.P);
             }
         }
+        // what a step streams alternates between two sets: item q + 1's loads are issued before item q's update, and
+        // an item's set is free again as soon as its state rows and the zeros over g are stored
+        if (live[0]) sm[0] = Step::template load<IO, NT>(g, rows..., off[0], col[0], vec[0], a.P);
 #pragma unroll
         for (int q = 0; q < kIPW; ++q) {
+            if (q + 1 < kIPW && live[q + 1])
+                sm[(q + 1) & 1] = Step::template load<IO, NT>(g, rows..., off[q + 1], col[q + 1], vec[q + 1], a.P);
             if (!live[q]) continue;                                  // wave-uniform
             const int i = wave * kIPW + q;
             const int r = i >> a.bshift;
-            if constexpr (STEP) {
-                xv[q] = mx::fused::sgd4<MOM>(xv[q], mx::fused::widen4(gv[q]), mv[q], st.nlr, h);
-                if constexpr (MOM) store_q<NT>(mv[q], m + off[q], col[q], vec[q], a.P);
-                if (h.zero_grads) store_q<NT>(IO::zero(), g + off[q], col[q], vec[q], a.P);
+            if constexpr (Step::kSteps) {
+                Step::template step<IO, NT>(xv[q], hd, q, sm[q & 1], st, h, g, rows..., off[q], col[q], vec[q], a.P);
                 if (!on) {                                           // no active matching: the step alone
                     store_x<IO, NT>(xv[q], x, tl, off[q], col[q], vec[q], a.P);
                     continue;
@@ -216,6 +241,7 @@ __global__ __launch_bounds__(kTPB) void quant_round(float* __restrict__ x, typen
         }
         if (!on) continue;                                           // kernel-uniform
         __syncthreads();
+        // phase 2: the step's lanes are gone, so s of all four items fits beside x' and x_hat
         F4 sv[kIPW];
 #pragma unroll
         for (int q = 0; q < kIPW; ++q)
@@ -243,12 +269,94 @@ __global__ __launch_bounds__(kTPB) void quant_round(float* __restrict__ x, typen
     }
 }
 
-template <class IO, int BITS, bool STEP, bool MOM>
-auto pick_nt(bool nt) {
-    return nt ? quant_round<IO, BITS, STEP, MOM, true> : quant_round<IO, BITS, STEP, MOM, false>;
+template <class IO, class Step, class... F>
+auto pick(int bits, bool nt) {
+    return bits == 4 ? (nt ? quant_round<IO, Step, 4, true, F...> : quant_round<IO, Step, 4, false, F...>)
+                     : (nt ? quant_round<IO, Step, 8, true, F...> : quant_round<IO, Step, 8, false, F...>);
 }
-template <class IO, bool STEP, bool MOM>
-auto pick(int bits, bool nt) { return bits == 4 ? pick_nt<IO, 4, STEP, MOM>(nt) : pick_nt<IO, 8, STEP, MOM>(nt); }
+
+// what a step inherits: nothing held, nothing streamed, no part in the alignment
+struct StepBase {
+    struct None {};
+    template <class IO>
+    using Held = None;
+    template <class IO>
+    using Stream = None;
+    template <class IO, class... A>
+    static __device__ __forceinline__ bool al(bool base, A...) { return base; }
+    template <class IO>
+    static __device__ __forceinline__ void clear(None&, int) {}
+    template <class IO, bool NT, class... A>
+    static __device__ __forceinline__ void hold(None&, int, A...) {}
+    template <class IO, bool NT, class... A>
+    static __device__ __forceinline__ None load(A...) { return {}; }
+};
+
+struct NoStep : StepBase {
+    using Hyper = SgdHyper;
+    struct State {};
+    static constexpr bool kSteps = false;
+    static __device__ __forceinline__ bool no_step(State&, const Hyper&) { return false; }
+    static __device__ __forceinline__ void setup(State&, const Hyper&) {}
+    template <class IO, bool NT, class... A>
+    static __device__ __forceinline__ void step(A...) {}
+    static bool given(const Hyper&, const void*, const float*) { return true; }
+    static int check(const char*, const Hyper&, const float*) { return MX_OK; }
+    template <class IO, class... F>
+    static auto kernel(const Hyper&, int bits, bool nt) { return pick<IO, NoStep, F...>(bits, nt); }
+};
+
+// torch.optim.SGD's step (sgd_update.h): g, and with MOM m, of all four items held in flight with x and x_hat
+template <bool MOM>
+struct SgdStep : StepBase {
+    using Hyper = SgdHyper;
+    using State = SgdState;
+    template <class IO>
+    struct Held {
+        typename IO::GC g[kIPW];
+        F4 m[kIPW];
+    };
+    static constexpr bool kSteps = true;
+    static __device__ __forceinline__ bool no_step(State& st, const Hyper& h) { return mx::fused::sgd_no_step(st, h); }
+    static __device__ __forceinline__ void setup(State& st, const Hyper& h) { mx::fused::sgd_setup(st, h); }
+    template <class IO>
+    static __device__ __forceinline__ bool al(bool base, const typename IO::GT* g, const float* m, int64_t off) {
+        return base && IO::al_g(g + off) && (!MOM || al16(m + off));
+    }
+    template <class IO>
+    static __device__ __forceinline__ void clear(Held<IO>& hd, int q) {
+        hd.m[q] = F4{0.0f, 0.0f, 0.0f, 0.0f};
+        hd.g[q] = IO::zero();
+    }
+    template <class IO, bool NT>
+    static __device__ __forceinline__ void hold(Held<IO>& hd, int q, const typename IO::GT* g, const float* m,
+                                                int64_t off, int64_t c, bool vec, int64_t P) {
+        hd.g[q] = load_q<NT>(g + off, c, vec, P);
+        if constexpr (MOM) hd.m[q] = load_q<NT>(m + off, c, vec, P);
+    }
+    template <class IO, bool NT>
+    static __device__ __forceinline__ void step(F4& xv, Held<IO>& hd, int q, None&, const State& st, const Hyper& h,
+                                                typename IO::GT* g, float* m, int64_t off, int64_t c, bool vec,
+                                                int64_t P) {
+        xv = mx::fused::sgd4<MOM>(xv, mx::fused::widen4(hd.g[q]), hd.m[q], st.nlr, h);
+        if constexpr (MOM) store_q<NT>(hd.m[q], m + off, c, vec, P);
+        if (h.zero_grads) store_q<NT>(IO::zero(), g + off, c, vec, P);
+    }
+};
+// its host side, and its name in round_launch: momentum picks the policy
+struct Sgd {
+    using Hyper = SgdHyper;
+    static bool given(const Hyper&, const void* g, const float*) { return g != nullptr; }
+    static int check(const char* who, const Hyper& h, const float* m) {
+        MX_CHECK((h.mom != 0.0f) == (m != nullptr), "%s: the momentum rows are given exactly when momentum != 0", who);
+        MX_CHECK(h.mom != 0.0f || !h.nesterov, "%s: nesterov needs momentum", who);
+        return MX_OK;
+    }
+    template <class IO, class... F>
+    static auto kernel(const Hyper& h, int bits, bool nt) {
+        return h.mom != 0.0f ? pick<IO, SgdStep<true>, F...>(bits, nt) : pick<IO, SgdStep<false>, F...>(bits, nt);
+    }
+};
 
 // the geometry of a launch, whatever its step: what every entry point checks of its shape, then the tile class,
 // the plan record and the persistent grid
@@ -284,28 +392,27 @@ inline int round_geo(const char* who, int64_t ld, int n_local, int64_t P, int bi
     return MX_OK;
 }
 
-// what the entry points of a form check alike, then the launch; STEP with g / m and the hyperparameters, a form
-// with an image with p
-template <class IO, bool STEP>
-int round_launch(const char* who, float* x, typename IO::GT* g, float* m, float* xhat, float* s, uint16_t* p,
-                 int64_t ld, int n_local, int64_t P, int bits, const int32_t* plan_dev, int64_t iter,
-                 const int64_t* iter_dev, int M, float alpha, float gamma, int64_t seed, int row_base, float* norms,
-                 int64_t norm_ld, float lr, const float* lr_dev, float wd, float mom, int nesterov, int zero_grads,
-                 void* stream) {
-    MX_CHECK(x && xhat && s && plan_dev && (!STEP || g) && (!IO::kImage || p), "%s: null pointer", who);
-    if constexpr (STEP) {
-        MX_CHECK((mom != 0.0f) == (m != nullptr), "%s: the momentum rows are given exactly when momentum != 0", who);
-        MX_CHECK(mom != 0.0f || !nesterov, "%s: nesterov needs momentum", who);
-    }
+// the SGD entry points' arguments as the step's constants
+inline SgdHyper sgd_hyper(float lr, const float* lr_dev, float wd, float mom, int nesterov, int zero_grads) {
+    return {lr, wd, mom, lr_dev, nullptr, nesterov != 0, zero_grads != 0};
+}
+
+// what every entry point checks alike, then the launch: the step's pointers and argument checks are the step's,
+// a form with an image has p, the step's state rows come last (m; m and v)
+template <class IO, class Step, class... F>
+int round_launch(const char* who, float* x, typename IO::GT* g, float* xhat, float* s, uint16_t* p, int64_t ld,
+                 int n_local, int64_t P, int bits, const int32_t* plan_dev, int64_t iter, const int64_t* iter_dev,
+                 int M, float alpha, float gamma, int64_t seed, int row_base, float* norms, int64_t norm_ld,
+                 const typename Step::Hyper& h, void* stream, F*... rows) {
+    MX_CHECK(x && xhat && s && plan_dev && (!IO::kImage || p) && Step::given(h, g, rows...), "%s: null pointer", who);
+    if (const int rc = Step::check(who, h, rows...)) return rc;
     RoundGeo geo;
     if (const int rc = round_geo(who, ld, n_local, P, bits, plan_dev, iter, iter_dev, M, alpha, gamma, seed, row_base,
                                  norms, norm_ld, &geo))
         return rc;
-    const SgdHyper h{lr, wd, mom, lr_dev, nullptr, nesterov != 0, zero_grads != 0};
-    const auto kern = !STEP ? pick<IO, false, false>(bits, geo.nt)
-                            : mom != 0.0f ? pick<IO, STEP, STEP>(bits, geo.nt) : pick<IO, STEP, false>(bits, geo.nt);
-    hipLaunchKernelGGL(kern, dim3(geo.grid), dim3(kTPB), 0, mx::as_stream(stream), x, g, m, xhat, s, norms, geo.rec,
-                       iter_dev, geo.dims, IO::tail(h, p));
+    hipLaunchKernelGGL((Step::template kernel<IO, F...>(h, bits, geo.nt)), dim3(geo.grid), dim3(kTPB), 0,
+                       mx::as_stream(stream), x, g, rows..., xhat, s, norms, geo.rec, iter_dev, geo.dims,
+                       make_tail<IO>(h, p));
     MX_LAUNCH_CHECK();
     return MX_OK;
 }

@@ -31,9 +31,10 @@
 // No atomics, no workspace, no finish launch.  The plan must be all-local: a record with receive slots
 // (n_remote != 0) or the peer-reads bit lives in device memory, so it is the launch that refuses it -- it
 // writes nothing.
-// The kernel and its host side live in choco_quant_round.h, written over a storage form, because
-// choco_quant_round_bf16.hip runs the same round for bfloat16 models; this file instantiates it for fp32 gradients
-// and no image, and defines the fp32 entry points and the two knobs.
+// The kernel and its host side live in choco_quant_round.h, written over a storage form and a step policy
+// (NoStep, SgdStep; choco_quant_adamw_round.h adds AdamStep), because choco_quant_round_bf16.hip runs the same
+// round for bfloat16 models; this file instantiates it for fp32 gradients and no image, and defines the fp32
+// entry points and the two knobs.
 #include "choco_quant_round.h"
 
 namespace mx {
@@ -44,18 +45,17 @@ int g_quant_round_grid = 0;               // "round_grid": > 0 is the exact grid
 }  // namespace mx
 
 namespace {
-// the kernel and its host side are choco_quant_round.h's over a storage form: here fp32 gradients and no image
-template <bool STEP>
-constexpr auto round_launch = mx::choco::qround::round_launch<mx::choco::qround::Fp32Io, STEP>;
+using namespace mx::choco::qround;
+float* const kNoRows = nullptr;           // the round alone: no state rows
 }  // namespace
 
 extern "C" int mx_choco_quant_round(float* x, float* xhat, float* s, int64_t ld, int n_local, int64_t P, int bits,
                                     const int32_t* plan_dev, int64_t iter, int M, float alpha, float gamma,
                                     int64_t seed, int row_base, float* norms, int64_t norm_ld, void* stream) {
     MX_CHECK(iter >= 0, "mx_choco_quant_round: iter < 0");
-    return round_launch<false>("mx_choco_quant_round", x, nullptr, nullptr, xhat, s, nullptr, ld, n_local, P, bits,
-                               plan_dev, iter, nullptr, M, alpha, gamma, seed, row_base, norms, norm_ld, 0.0f, nullptr,
-                               0.0f, 0.0f, 0, 0, stream);
+    return round_launch<Fp32Io, NoStep>("mx_choco_quant_round", x, nullptr, xhat, s, nullptr, ld, n_local, P, bits,
+                                        plan_dev, iter, nullptr, M, alpha, gamma, seed, row_base, norms, norm_ld, {},
+                                        stream, kNoRows);
 }
 
 extern "C" int mx_choco_quant_round_at(float* x, float* xhat, float* s, int64_t ld, int n_local, int64_t P, int bits,
@@ -63,9 +63,9 @@ extern "C" int mx_choco_quant_round_at(float* x, float* xhat, float* s, int64_t 
                                        float alpha, float gamma, int64_t seed, int row_base, float* norms,
                                        int64_t norm_ld, void* stream) {
     MX_CHECK(iter_dev && n_iters >= 0, "mx_choco_quant_round_at: bad iteration counter");
-    return round_launch<false>("mx_choco_quant_round_at", x, nullptr, nullptr, xhat, s, nullptr, ld, n_local, P, bits,
-                               plan_dev, n_iters, iter_dev, M, alpha, gamma, seed, row_base, norms, norm_ld, 0.0f,
-                               nullptr, 0.0f, 0.0f, 0, 0, stream);
+    return round_launch<Fp32Io, NoStep>("mx_choco_quant_round_at", x, nullptr, xhat, s, nullptr, ld, n_local, P, bits,
+                                        plan_dev, n_iters, iter_dev, M, alpha, gamma, seed, row_base, norms, norm_ld,
+                                        {}, stream, kNoRows);
 }
 
 extern "C" int mx_choco_quant_sgd_round(float* x, float* g, float* m, float* xhat, float* s, int64_t ld, int n_local,
@@ -74,9 +74,10 @@ extern "C" int mx_choco_quant_sgd_round(float* x, float* g, float* m, float* xha
                                         int64_t norm_ld, float lr, const float* lr_dev, float weight_decay,
                                         float momentum, int nesterov, int zero_grads, void* stream) {
     MX_CHECK(iter >= 0, "mx_choco_quant_sgd_round: iter < 0");
-    return round_launch<true>("mx_choco_quant_sgd_round", x, g, m, xhat, s, nullptr, ld, n_local, P, bits, plan_dev,
-                              iter, nullptr, M, alpha, gamma, seed, row_base, norms, norm_ld, lr, lr_dev, weight_decay,
-                              momentum, nesterov, zero_grads, stream);
+    return round_launch<Fp32Io, Sgd>(
+        "mx_choco_quant_sgd_round", x, g, xhat, s, nullptr, ld, n_local, P, bits, plan_dev, iter, nullptr, M, alpha,
+        gamma, seed, row_base, norms, norm_ld, sgd_hyper(lr, lr_dev, weight_decay, momentum, nesterov, zero_grads),
+        stream, m);
 }
 
 extern "C" int mx_choco_quant_sgd_round_at(float* x, float* g, float* m, float* xhat, float* s, int64_t ld,
@@ -86,7 +87,8 @@ extern "C" int mx_choco_quant_sgd_round_at(float* x, float* g, float* m, float* 
                                            const float* lr_dev, float weight_decay, float momentum, int nesterov,
                                            int zero_grads, void* stream) {
     MX_CHECK(iter_dev && n_iters >= 0, "mx_choco_quant_sgd_round_at: bad iteration counter");
-    return round_launch<true>("mx_choco_quant_sgd_round_at", x, g, m, xhat, s, nullptr, ld, n_local, P, bits, plan_dev,
-                              n_iters, iter_dev, M, alpha, gamma, seed, row_base, norms, norm_ld, lr, lr_dev,
-                              weight_decay, momentum, nesterov, zero_grads, stream);
+    return round_launch<Fp32Io, Sgd>(
+        "mx_choco_quant_sgd_round_at", x, g, xhat, s, nullptr, ld, n_local, P, bits, plan_dev, n_iters, iter_dev, M,
+        alpha, gamma, seed, row_base, norms, norm_ld,
+        sgd_hyper(lr, lr_dev, weight_decay, momentum, nesterov, zero_grads), stream, m);
 }

@@ -37,9 +37,8 @@
 #include "choco_quant_round.h"
 
 namespace {
-using mx::choco::qround::Bf16Io;
-template <bool STEP>
-constexpr auto round_launch = mx::choco::qround::round_launch<Bf16Io, STEP>;
+using namespace mx::choco::qround;
+float* const kNoRows = nullptr;           // the round alone: no state rows
 }  // namespace
 
 extern "C" int mx_choco_quant_round_bf16(float* x, float* xhat, float* s, uint16_t* p, int64_t ld, int n_local,
@@ -47,9 +46,9 @@ extern "C" int mx_choco_quant_round_bf16(float* x, float* xhat, float* s, uint16
                                          float gamma, int64_t seed, int row_base, float* norms, int64_t norm_ld,
                                          void* stream) {
     MX_CHECK(iter >= 0, "mx_choco_quant_round_bf16: iter < 0");
-    return round_launch<false>("mx_choco_quant_round_bf16", x, nullptr, nullptr, xhat, s, p, ld, n_local, P, bits,
-                               plan_dev, iter, nullptr, M, alpha, gamma, seed, row_base, norms, norm_ld, 0.0f, nullptr,
-                               0.0f, 0.0f, 0, 0, stream);
+    return round_launch<Bf16Io, NoStep>("mx_choco_quant_round_bf16", x, nullptr, xhat, s, p, ld, n_local, P, bits,
+                                        plan_dev, iter, nullptr, M, alpha, gamma, seed, row_base, norms, norm_ld, {},
+                                        stream, kNoRows);
 }
 
 extern "C" int mx_choco_quant_round_bf16_at(float* x, float* xhat, float* s, uint16_t* p, int64_t ld, int n_local,
@@ -57,9 +56,9 @@ extern "C" int mx_choco_quant_round_bf16_at(float* x, float* xhat, float* s, uin
                                             int64_t n_iters, int M, float alpha, float gamma, int64_t seed,
                                             int row_base, float* norms, int64_t norm_ld, void* stream) {
     MX_CHECK(iter_dev && n_iters >= 0, "mx_choco_quant_round_bf16_at: bad iteration counter");
-    return round_launch<false>("mx_choco_quant_round_bf16_at", x, nullptr, nullptr, xhat, s, p, ld, n_local, P,
-                               bits, plan_dev, n_iters, iter_dev, M, alpha, gamma, seed, row_base, norms, norm_ld,
-                               0.0f, nullptr, 0.0f, 0.0f, 0, 0, stream);
+    return round_launch<Bf16Io, NoStep>("mx_choco_quant_round_bf16_at", x, nullptr, xhat, s, p, ld, n_local, P, bits,
+                                        plan_dev, n_iters, iter_dev, M, alpha, gamma, seed, row_base, norms, norm_ld,
+                                        {}, stream, kNoRows);
 }
 
 extern "C" int mx_choco_quant_sgd_round_bf16(float* x, uint16_t* g, float* m, float* xhat, float* s, uint16_t* p,
@@ -69,9 +68,10 @@ extern "C" int mx_choco_quant_sgd_round_bf16(float* x, uint16_t* g, float* m, fl
                                              float weight_decay, float momentum, int nesterov, int zero_grads,
                                              void* stream) {
     MX_CHECK(iter >= 0, "mx_choco_quant_sgd_round_bf16: iter < 0");
-    return round_launch<true>("mx_choco_quant_sgd_round_bf16", x, g, m, xhat, s, p, ld, n_local, P, bits,
-                              plan_dev, iter, nullptr, M, alpha, gamma, seed, row_base, norms, norm_ld, lr, lr_dev,
-                              weight_decay, momentum, nesterov, zero_grads, stream);
+    return round_launch<Bf16Io, Sgd>(
+        "mx_choco_quant_sgd_round_bf16", x, g, xhat, s, p, ld, n_local, P, bits, plan_dev, iter, nullptr, M, alpha,
+        gamma, seed, row_base, norms, norm_ld, sgd_hyper(lr, lr_dev, weight_decay, momentum, nesterov, zero_grads),
+        stream, m);
 }
 
 extern "C" int mx_choco_quant_sgd_round_bf16_at(float* x, uint16_t* g, float* m, float* xhat, float* s, uint16_t* p,
@@ -81,7 +81,8 @@ extern "C" int mx_choco_quant_sgd_round_bf16_at(float* x, uint16_t* g, float* m,
                                                 float lr, const float* lr_dev, float weight_decay, float momentum,
                                                 int nesterov, int zero_grads, void* stream) {
     MX_CHECK(iter_dev && n_iters >= 0, "mx_choco_quant_sgd_round_bf16_at: bad iteration counter");
-    return round_launch<true>("mx_choco_quant_sgd_round_bf16_at", x, g, m, xhat, s, p, ld, n_local, P, bits,
-                              plan_dev, n_iters, iter_dev, M, alpha, gamma, seed, row_base, norms, norm_ld, lr, lr_dev,
-                              weight_decay, momentum, nesterov, zero_grads, stream);
+    return round_launch<Bf16Io, Sgd>(
+        "mx_choco_quant_sgd_round_bf16_at", x, g, xhat, s, p, ld, n_local, P, bits, plan_dev, n_iters, iter_dev, M,
+        alpha, gamma, seed, row_base, norms, norm_ld,
+        sgd_hyper(lr, lr_dev, weight_decay, momentum, nesterov, zero_grads), stream, m);
 }

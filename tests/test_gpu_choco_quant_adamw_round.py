@@ -7,6 +7,7 @@ import pytest
 from adamref import adam_ref, bias_table
 from bf16ref import rne_bf16, same_bf16, upcast
 from conftest import Topo
+from sgdref import sgd_ref
 from test_gpu_choco_quant import BITS, FLAGS3, SEED, _knob, _rows
 from test_gpu_choco_quant_round import _check_round, _topo
 from test_gpu_choco_quant_round_bf16 import _bits, _group, _masters, _put_bits
@@ -156,6 +157,64 @@ def test_graph_replay_equals_the_host_steps(pkg, dtype):
             b.adamw_communicate(LR / (t + 1))
         _same(a, b, STATE + ("rows", "grads"), f"replay {t}")
     assert int(a.iter_dev.item()) == T + 1 == int(a.opt_step_dev.item()) - 1 and bool(a.grads.any())
+
+
+@pytest.mark.parametrize("step", ["none", "sgd", "adamw"])
+def test_inactive_and_out_of_schedule_rounds_per_step(pkg, step):
+    """The kernel's no-op rules, once per step policy, through the _at entry points (a device counter).  3 rows,
+    P = 257: a bucket of 16-byte accesses and the bucket that holds P.  A counter outside the schedule writes
+    nothing, g included; a round of the schedule with no active matching leaves x_hat, s and the norms alone and is
+    exactly the reference step (nothing, without a step); an AdamW optimizer step below 1 writes nothing."""
+    P, lr, (mom, wd) = 257, 0.05, (0.9, 5e-4)
+    flags = np.array([[1, 1, 1], [0, 0, 0]], np.uint8)
+    X, G = _rows(500, 3, P), _rows(510, 3, P)
+    grp = _group(pkg, flags, P, 4, rows=X, dtype=torch.float32)
+    arrays, launch = {"x": grp.x, "x_hat": grp.x_hat, "s": grp.s, "round_norms": grp.round_norms}, grp.device_round
+    if step == "sgd":
+        grp.attach_sgd(momentum=mom, weight_decay=wd)
+        arrays.update(g=grp.grad_arena, m=grp.mom_arena)
+        launch = grp.sgd_device_round
+    if step == "adamw":
+        grp.attach_adamw(betas=BETAS, eps=EPS, weight_decay=HYPERS[0][0], decoupled=HYPERS[0][1])
+        arrays.update(g=grp.grad_arena, m=grp.exp_avg_arena, v=grp.exp_avg_sq_arena)
+        launch = grp.adamw_device_round
+    grp.x_hat[:, :P].copy_(torch.from_numpy(F32(0.5) * _rows(520, 3, P)))
+    grp.s[:, :P].copy_(torch.from_numpy(F32(0.25) * _rows(530, 3, P)))
+    grp.round_norms.fill_(7.25)
+    if step != "none":
+        grp.grads.copy_(torch.from_numpy(G))
+        grp.lr_dev.fill_(lr)
+
+    def run(counter):
+        """the launch at `counter`: the arrays' bits before it and after it"""
+        grp.iter_dev.fill_(counter)
+        torch.cuda.synchronize()
+        before = {k: v.clone() for k, v in arrays.items()}
+        launch()
+        torch.cuda.synchronize()
+        same = lambda k: torch.equal(arrays[k].view(torch.int32), before[k].view(torch.int32))
+        return before, {k for k in arrays if not same(k)}
+
+    for counter in (len(flags), -1):                                 # 1: outside the schedule
+        assert run(counter)[1] == set(), (step, counter)
+    if step == "adamw":                                              # 3: no such optimizer step, on an active round
+        grp.opt_step_dev.fill_(0)
+        assert run(0)[1] == set(), "optimizer step 0"
+        grp.opt_step_dev.fill_(1)
+    before, changed = run(1)                                         # 2: a round with no active matching
+    if step == "none":
+        assert changed == set()
+        return
+    assert changed == set(arrays) - {"x_hat", "s", "round_norms"}, changed
+    if step == "sgd":
+        want = dict(zip("xm", sgd_ref(X, G, np.zeros_like(X), lr, wd, mom, False)))
+    else:
+        Z = np.zeros_like(X)
+        want = dict(zip("xmv", adam_ref(X, G, Z, Z, 1, lr, (*BETAS, EPS, *HYPERS[0]), TABLE)))
+    want["g"] = np.zeros_like(X)
+    for k, w in want.items():                                        # the step's P columns; the padding as it was
+        before[k][:, :P].copy_(torch.from_numpy(np.asarray(w, F32)))
+        assert torch.equal(arrays[k].view(torch.int32), before[k].view(torch.int32)), (step, k)
 
 
 def test_refusals_and_checkpoints(pkg):
