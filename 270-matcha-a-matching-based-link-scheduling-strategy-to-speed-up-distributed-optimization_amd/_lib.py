@@ -90,6 +90,8 @@ SIGNATURES = {
                                         c_int, c_int, c_f32, c_f32, c_p]),
     "mx_choco_quant_set": (c_int, [ctypes.c_char_p, c_int]),
     "mx_choco_quant_get": (c_int, [ctypes.c_char_p]),
+    "mx_choco_randk_compress": (c_int, [c_p, c_p, c_i64, c_int, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64,
+                                        c_int, c_p]),
     "mx_choco_quant_round": (c_int, [c_p, c_p, c_p, c_i64, c_int, c_i64, c_int, c_p, c_i64, c_int, c_f32, c_f32,
                                      c_i64, c_int, c_p, c_i64, c_p]),
     "mx_choco_quant_round_at": (c_int, [c_p, c_p, c_p, c_i64, c_int, c_i64, c_int, c_p, c_p, c_i64, c_int, c_f32,

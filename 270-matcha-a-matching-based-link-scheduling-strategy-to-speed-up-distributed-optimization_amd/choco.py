@@ -19,6 +19,10 @@ serves models held in bfloat16 (dtype=torch.bfloat16, csrc/choco_quant_round_bf1
 momentum stay fp32, the gradients come in as bfloat16 and the same launch rewrites the models as bf16_rne(x).
 attach_adamw() puts torch.optim.AdamW's (or Adam's) step in front of that one launch instead of SGD's
 (csrc/choco_quant_adamw_round.hip, csrc/choco_quant_adamw_round_bf16.hip: exp_avg and exp_avg_sq fp32).
+With compressor="randk" the message is random sparsification (csrc/choco_randk.hip): top-k's k = topk_count(P, ratio)
+columns and top-k's layout, but the columns are drawn from a counter-based hash of (seed, round, worker, column) and
+never depend on the data; mx_choco_randk_compress is one launch that touches only the selected columns, with no
+workspace and nothing for check_topk() to check, and every later step of the round is top-k's own.
 Under PullTransport (N > 1, one process per GPU of a node) the messages are not sent: every rank
 publishes the messages its peers read this round into its IPC-shared snapshot buffer
 (mx_snapshot_publish_rows), the device
@@ -43,7 +47,7 @@ def topk_count(P, ratio):
     return max(1, int(P * (1 - ratio)))
 
 
-COMPRESSORS = ("topk", "sign", "quant")
+COMPRESSORS = ("topk", "sign", "quant", "randk")
 
 
 class ChocoWorkerGroup:
@@ -51,9 +55,11 @@ class ChocoWorkerGroup:
                  comm=None, adopt=True, placement=None, pull_read="fetch", dtype=torch.float32,
                  compressor="topk", bits=None, seed=0, one_launch=False):
         """compressor: "topk" (compressors.get_top_k; `ratio` required), "sign" (the scaled-sign
-        quantizer) or "quant" (the bucketed stochastic quantizer: `bits` 4 or 8, default 8; `seed` of its
-        counter-based random numbers); the last two take no `ratio`, have k = 0 and nothing for check_topk()
-        to check, and PullTransport is not built for them.
+        quantizer), "quant" (the bucketed stochastic quantizer: `bits` 4 or 8, default 8; `seed` of its
+        counter-based random numbers) or "randk" (random sparsification: `ratio` required, k and the message
+        layout as top-k's, the columns drawn from `seed`, the round and the worker); "sign" and "quant" take no
+        `ratio` and have k = 0; only "topk" has something for check_topk() to check, and PullTransport is built
+        for "topk" alone.
         one_launch (compressor="quant", nranks = 1, at most 16 rows): a round, and with attach_sgd() the SGD
         step in front of it, is ONE launch (csrc/choco_quant_round.hip) that keeps the messages on chip --
         the same bits in x, x_hat and s as the two launches; there are no message slots, so message(),
@@ -74,9 +80,9 @@ class ChocoWorkerGroup:
             raise ValueError("pull_read must be 'fetch' or 'direct'")
         if compressor not in COMPRESSORS:
             raise ValueError(f"compressor must be one of {COMPRESSORS}, not {compressor!r}")
-        if compressor == "topk" and ratio is None:
-            raise ValueError("ChocoWorkerGroup: compressor='topk' needs a ratio")
-        if compressor != "topk" and ratio is not None:
+        if compressor in ("topk", "randk") and ratio is None:
+            raise ValueError(f"ChocoWorkerGroup: compressor={compressor!r} needs a ratio")
+        if compressor not in ("topk", "randk") and ratio is not None:
             raise ValueError(f"ChocoWorkerGroup: compressor={compressor!r} takes no ratio")
         if compressor != "topk" and isinstance(comm, PullTransport):
             raise NotImplementedError(f"ChocoWorkerGroup: compressor={compressor!r} under PullTransport -- the "
@@ -100,6 +106,7 @@ class ChocoWorkerGroup:
         self.compressor = compressor
         self.sign = compressor == "sign"
         self.quant = compressor == "quant"
+        self.randk = compressor == "randk"
         self.bits = (8 if bits is None else int(bits)) if self.quant else None
         self.seed = int(seed)
         self.pull_read = pull_read
@@ -172,7 +179,7 @@ class ChocoWorkerGroup:
             # vals f32[kpad] | idx int64[k] | tile bounds int32[ceil(P/4096) + 1] (written by the top-k)
             self.msg_bytes = int(lib.mx_choco_msg_bytes(P, self.k))
             self.bnd_off = 4 * self.kpad + 8 * self.k
-            self.work_ld = int(lib.mx_topk_work_bytes(P))
+            self.work_ld = 0 if self.randk else int(lib.mx_topk_work_bytes(P))    # rand-k selects without scratch
         self.msg_ld = (self.msg_bytes + 255) // 256 * 256
         self.round_norms = None
         if self.one_launch:                  # no message slots: the norms are all of a message that reaches memory
@@ -256,10 +263,12 @@ class ChocoWorkerGroup:
     def compress(self, it, stream=None):
         """prepare_comm_buffer (communicator.py:175-196): every local row's top-k message of
         x - x_hat into its message slot (compressor="sign": its scaled-sign message; "quant": its quantized
-        message of round `it`)."""
+        message of round `it`; "randk": its k random columns of round `it`)."""
         self._needs_slots("compress")
         if self.quant:
             return self._quant_compress(int(it), None, stream)
+        if self.randk:
+            return self._randk_compress(int(it), None, stream)
         if self.sign:
             check(lib.mx_choco_sign_compress(self.x.data_ptr(), self.x_hat.data_ptr(), self.ld, self.n_local,
                                              self.numel, self.msgs.data_ptr(), self.msg_ld, self.work.data_ptr(),
@@ -317,10 +326,19 @@ class ChocoWorkerGroup:
                                           self.engine.T if iter_dev else 0, self.row_base, stream_ptr(stream)),
               "mx_choco_quant_compress")
 
+    def _randk_compress(self, it, iter_dev, stream=None):
+        """mx_choco_randk_compress at round `it`, or at the device counter (`iter_dev`: its address)"""
+        check(lib.mx_choco_randk_compress(self.x.data_ptr(), self.x_hat.data_ptr(), self.ld, self.n_local, self.numel,
+                                          self.k, self.msgs.data_ptr(), self.msg_ld, self.seed, it, iter_dev,
+                                          self.engine.T if iter_dev else 0, self.row_base, stream_ptr(stream)),
+              "mx_choco_randk_compress")
+
     def _compress_at(self, stream=None):
-        """compress() of a graph-replayable round: the quantizer reads its round from the device counter"""
+        """compress() of a graph-replayable round: the quantizer and rand-k read their round from the device counter"""
         if self.quant:
             return self._quant_compress(0, self.iter_dev.data_ptr(), stream)
+        if self.randk:
+            return self._randk_compress(0, self.iter_dev.data_ptr(), stream)
         self.compress(0, stream)
 
     def wait_round(self, stream=None):
@@ -350,8 +368,8 @@ class ChocoWorkerGroup:
     def check_topk(self, stream=None):
         """Synchronise and raise MXError if a top-k row barrier's bounded wait expired since the
         last check (mx_topk_check: that round's messages are undefined; never a GPU hang).  Nothing to
-        check with compressor="sign" or "quant": their kernels have no barrier and no wait."""
-        if self.k == 0:
+        check with compressor="sign", "quant" or "randk": their kernels have no barrier and no wait."""
+        if self.k == 0 or self.randk:
             return
         check(lib.mx_topk_check(self.work.data_ptr(), self.work_ld, self.n_local, self.numel, stream_ptr(stream)),
               "mx_topk_check")
@@ -691,6 +709,8 @@ class ChocoWorkerGroup:
             state["compressor"] = "sign"
         if self.quant:
             state.update(compressor="quant", bits=self.bits, seed=self.seed)
+        if self.randk:
+            state.update(compressor="randk", seed=self.seed)
         if self.dtype == torch.bfloat16:     # `rows` are the fp32 masters either way: an fp32 group loads them
             state["dtype"] = "bfloat16"
         if self.momentum_rows is not None:   # attach_sgd with momentum; without it, key for key what it was
@@ -737,7 +757,7 @@ class ChocoWorkerGroup:
             if self.arena is not self.x:     # the image of the loaded masters
                 self.arena[:, :P].copy_(self.x[:, :P].to(self.dtype))
         self.iter = int(state["iter"])
-        if self.quant:
+        if self.quant or self.randk:
             self.seed = int(state["seed"])       # the resumed run draws the saved run's random numbers
 
     def communicate(self):

@@ -1292,6 +1292,23 @@ int mx_choco_quant_apply_at(float* x, float* xhat, float* s, int64_t ld, int64_t
  * "round_grid" are the one-launch round's persistent grid, in the same two senses. */
 int mx_choco_quant_set(const char* key, int value);
 int mx_choco_quant_get(const char* key);
+/* ---------------------------------------------------------------- ChocoSGD, random sparsification (rand-k)
+ * prepare_comm_buffer (communicator.py:175-196) with k columns drawn at random in place of
+ * compressors.get_top_k's k largest, ONE launch with no scratch and nothing to check afterwards.  Row r reads
+ * x + r*ld (and x_hat + r*ld; x_hat may be NULL: zeros) and writes every byte of a message in mx_choco_msg_bytes'
+ * layout at msgs + r*msg_ld_bytes (8-byte aligned, msg_ld_bytes a multiple of 8 and >= mx_choco_msg_bytes(P, k);
+ * ignored for one row): vals f32[kpad] | idx int64[k] ascending | bnd int32[T + 1], T = ceil(P/4096) -- what
+ * mx_choco_apply, mx_choco_apply_at and mx_choco_apply_slots read.  With mix32 and the key chain of the
+ * quantizer above:
+ *   rk = mix32(mix32(mix32(u32(seed)) ^ u32(round)) ^ u32(row_base + r));  o = (u64(mix32(rk ^ 0xA5A5A5A5)) P) >> 32
+ *   bnd[t] = floor((k min(4096 t, P) + o) / P), t = 0 .. T;  tile t sends its bnd[t+1] - bnd[t] columns j with
+ *   the smallest v(j) = (mix32(mix32(rk ^ u32(t + 1)) + j) & 0xFFFFF000) | j, j the column inside the tile
+ *   vals[i] = fsub(x[idx[i]], x_hat[idx[i]]); the pad element of an odd k is +0
+ * The round is `round`, or with round_dev non-NULL *round_dev when the kernel runs -- outside [0, n_rounds) the
+ * launch writes nothing.  1 <= k <= P < 2^31 (the bounds are int32). */
+int mx_choco_randk_compress(const float* x, const float* x_hat, int64_t ld, int nrows, int64_t P, int64_t k,
+                            void* msgs, int64_t msg_ld_bytes, int64_t seed, int64_t round, const int64_t* round_dev,
+                            int64_t n_rounds, int row_base, void* stream);
 /* prepare_comm_buffer + averaging (communicator.py:175-230) of a whole group in ONE launch, when every worker's
  * row lives on this GPU: mx_choco_quant_compress (x_hat given) followed by mx_choco_quant_apply, with the same
  * bits in x, x_hat and s, and no message in memory -- a workgroup quantizes one column tile of all n_local rows
